@@ -17,7 +17,7 @@ and their q heads, zero-copy slices, fattn.shard): every timed step is the
 rank's FLASH_ATTN_EXT followed by the RCCL all_gather over xGMI of that step's
 output and its permute into the ggml dst layout, K gathers inside the timed
 region.  value = the config-5 bytes x K / the slowest rank's wall time.  The
-N = 1 line carries `strong_scaling_ref` (config 5 on one GPU) as the
+N = 1 `--full` line carries `strong_scaling_ref` (config 5 on one GPU) as the
 denominator.  Beside the value line: `kernel_only` (the same launches with no
 gather, graph-replayed: SURVEY's "near-linear applies to the kernel part") and
 `weak_scaling_config3` (every rank decodes its own config-3 sequence, one
@@ -26,7 +26,13 @@ no launcher starts N child ranks itself (before touching the GPU).
 
 Prints ONE JSON line (rank 0).  `value` = whole-job algorithmic bytes / wall
 time (GB/s); `roofline` prices the dominant kernel from HIP events on its
-launch stream; `cpu_baseline` times the reference's own CPU oracle
+launch stream.  A plain N = 1 run stops there: it sets up, warms up, times the
+K steps (one graph replay), writes `--dump-outputs DIR` (DIR/out.npy: the
+last timed step's output, f32) and prints the line.  `--full` adds the rest
+to the same line: the per-launch kernel median, the measured HBM ceilings,
+`strong_scaling_ref`, `config5_seq64`, `prefill` and `cpu_baseline`, each a
+measurement of its own.
+`cpu_baseline` times the reference's own CPU oracle
 (src/utils.h compiled from /root/reference into oracle/_ref) on the host
 cores, single-thread and on the box's thread share, median of >= 5 runs;
 `prefill` (N=1) prices fattn_pf_kernel against the dense f16 MFMA peak on the
@@ -451,7 +457,17 @@ def parse_args(argv=None):
     ap.add_argument("--no-scale-ref", action="store_true", help="N=1: skip the config-5 strong-scaling reference")
     ap.add_argument("--no-copy-peak", action="store_true", help="skip the measured copy-kernel peak")
     ap.add_argument("--dump-out", default="", help="rank 0 writes rotation 0's inputs and gathered output (.npz)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: beside the value line, everything else the bench measures -- the per-launch kernel "
+                         "median, the measured HBM ceilings, config 5 on one GPU and its 64-sequence reading, the "
+                         "prefill lines, the CPU baselines (the --no-* flags drop single legs of it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step computed (the attention "
+                         "output, gathered over the ranks when there are several) as DIR/out.npy, float32")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.prefill_only:
+        ap.error("--dump-outputs writes the timed decode path's output; --prefill-only times no decode step")
+    return args
 
 
 def apply_options(args):
@@ -516,13 +532,16 @@ def _gather(x, mode="head", buf=None, out=None):
     return out
 
 
-def run_decode(args, dev, shape, rank=0, world=1, mode="head", dist_on=False):
+def run_decode(args, dev, shape, rank=0, world=1, mode="head", dist_on=False, median=True, dump_dir=""):
     """Time K steps of the decode workload `shape` (one FLASH_ATTN_EXT per step)
     over `world` ranks: mode "head" shards its heads (strong scaling, every rank
     a slice of one global problem), mode "batch" gives every rank a whole
     problem of its own -- its own sequence of the batch (weak scaling).
     `dist_on`: a process group exists (world > 1, or --dist at world 1): every
     timed step gathers its output over it.
+    `median`: also the per-launch kernel median, HIP events around each of the
+    eager launches before the timed replay (off: no events, median None).
+    `dump_dir`: rank 0 writes the last timed step's output there (out.npy).
     Returns the measurement dict (rank 0 holds the max over ranks)."""
     import torch
     import torch.distributed as dist
@@ -588,20 +607,22 @@ def run_decode(args, dev, shape, rank=0, world=1, mode="head", dist_on=False):
 
     # 1) dominant-kernel duration, eager launches with HIP events recorded by
     #    libfattn around the kernel (not part of the timed region): median
+    #    (median off: the same launches without events -- the clocks the timed
+    #    replay starts from stay what they were; 200 launches are ~2 ms)
     n_ev = min(args.steps, 200)
-    hip, evs = hip_events(2 * n_ev)
+    hip, evs = hip_events(2 * n_ev if median else 2)
     stream = torch.cuda.current_stream(dev).cuda_stream
     for i in range(args.warmup):
         step(i, stream)
     for i in range(n_ev):
-        step(i, stream, (evs[2 * i], evs[2 * i + 1]))
+        step(i, stream, (evs[2 * i], evs[2 * i + 1]) if median else None)
     torch.cuda.synchronize()
     f = C.c_float()
     kms = []
-    for i in range(n_ev):
+    for i in range(n_ev if median else 0):
         hip.hipEventElapsedTime(C.byref(f), evs[2 * i], evs[2 * i + 1])
         kms.append(f.value)
-    kern_ms_median = statistics.median(kms)
+    kern_ms_median = statistics.median(kms) if kms else None
 
     # 2) the kernel alone: the K steps (step i reads KV cache i % R) captured
     #    back-to-back into one HIP graph and replayed; HIP events around the
@@ -733,6 +754,14 @@ def run_decode(args, dev, shape, rank=0, world=1, mode="head", dist_on=False):
         np.savez(path, q=q.cpu().numpy(), k=kv_sets[last][0].cpu().numpy(), v=kv_sets[last][1].cpu().numpy(),
                  mask=masks[last].cpu().view(torch.int16).numpy().view(np.uint16), out=out0,
                  shape=np.array([D, NQ, H, Hkv, N, typ, world]), kernel=np.array(kname), mode=np.array(mode))
+    if dump_dir and rank == 0:
+        # what a caller of the timed path holds after its last step: the dst
+        # tensor [1][NQ][H][D] (batch mode: [world][1][NQ][H][D]), f32, a few
+        # hundred KB at most.  The inputs come from seeded device generators,
+        # so equal arguments give equal inputs from run to run.
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "out.npy"),
+                (full if dist_on else outs[last]).cpu().numpy().astype(np.float32, copy=False))
     if dist_on:
         assert tuple(full.shape) == ((1, NQ, H, D) if mode == "head" else (world, 1, NQ, H, D))
         # 3) per-step cost of the gather, and kernel + gather per step (eager),
@@ -784,8 +813,9 @@ def roofline(res, args, traffic=None, peaks=None):
         return {"bound": "mfma", "achieved": round(ach_tf, 2), "peak": MFMA_F16_PEAK_TFLOPS, "unit": "TFLOP/s",
                 "frac": round(ach_tf / MFMA_F16_PEAK_TFLOPS, 4), "traffic": traffic, "kernel": res["kernel"]}
     r = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-         "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "kernel": res["kernel"],
-         "frac_median_kernel": round(res["rank_bytes"] / (res["kernel_ms_median"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+         "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "kernel": res["kernel"]}
+    if res["kernel_ms_median"] is not None:
+        r["frac_median_kernel"] = round(res["rank_bytes"] / (res["kernel_ms_median"] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
     if peaks and peaks.get("oneshot"):
         os_ = peaks["oneshot"]
         best_us = os_["us_per_launch"][os_["best"]]
@@ -862,7 +892,10 @@ def main():
     mode = args.multi if multi else "head"
     workload = args.workload if args.workload != "auto" else ("config5" if mode == "head" and multi else "config3")
     shape = shape_of(args, workload)
-    res = run_decode(args, dev, shape, rank, world, mode, multi)
+    # a plain N = 1 run does what the value line needs: set up, warm up, time
+    # the K steps; every other measurement is behind --full
+    full = args.full or multi
+    res = run_decode(args, dev, shape, rank, world, mode, multi, median=full, dump_dir=args.dump_outputs)
     side = None
     if multi and not args.no_side_line:
         # the other multi-GPU reading beside the value line: head mode (the line)
@@ -874,8 +907,8 @@ def main():
 
     if rank == 0:
         traffic = committed_traffic(res["workload"], res["kernel"]) if not multi else None
-        peaks = None if args.no_copy_peak or multi else measured_hbm_peaks()
-        if not args.no_copy_peak and not multi:
+        peaks = None if args.no_copy_peak or not args.full or multi else measured_hbm_peaks()
+        if args.full and not args.no_copy_peak and not multi:
             one = oneshot_ceiling(shape)
             if one:
                 peaks = dict(peaks or {}, oneshot=one)
@@ -904,9 +937,9 @@ def main():
                        "bytes_per_step": res["job_bytes"], "flops_per_step": res["flops"]},
             "tflops": round(res["flops"] * K / res["elapsed"] / 1e12, 4),
             "kernel_ms_avg": round(res["kernel_ms_avg"], 5),
-            "kernel_ms_median": round(res["kernel_ms_median"], 5),
-            "kernel_timing": "avg: HIP events around the timed graph replay on the launch stream, / steps; "
-                             "median: per-launch HIP events, eager",
+            "kernel_ms_median": round(res["kernel_ms_median"], 5) if full else None,
+            "kernel_timing": "avg: HIP events around the timed graph replay on the launch stream, / steps"
+                             + ("; median: per-launch HIP events, eager" if full else " (median: --full)"),
             "roofline": roofline(res, args, traffic, peaks),
             "source_hash": source_hash(),
         }
@@ -962,7 +995,9 @@ def main():
         if multi:
             print(json.dumps(line), flush=True)
 
-    if not multi:
+    if not multi and not args.full:
+        print(json.dumps(line), flush=True)
+    elif not multi:
         if not args.no_scale_ref and workload == "config3":
             # the strong-scaling reference: config 5 (the multi-GPU workload) on this one GPU
             r5 = run_decode(args, dev, shape_of(argparse.Namespace(**{k: None for k in WORKLOADS["config5"]}),
