@@ -457,6 +457,21 @@ int make_plan(const fattn_params* p, Plan& pl) {
         if (mk.type != FATTN_TYPE_F16 || mk.ne[0] < N + (N & 1) || mk.ne[1] < NQ) return FATTN_ERR_INVALID_ARG;
         if ((uintptr_t)mk.data % 4 || mk.nb[1] % 4) return FATTN_ERR_ALIGNMENT;
     }
+    // mask planes: ne[2] per head, ne[3] per sequence, read by the query's
+    // indices as ggml does (iq2 % ne[2], iq3 % ne[3]); a count below 1 reads
+    // as 1 (zeroed structs), and a count of 1 has no stride to look at
+    int64_t m_ne2 = 1, m_ne3 = 1, m_nb2 = 0, m_nb3 = 0;
+    if (has_mask) {
+        m_ne2 = std::max<int64_t>(1, mk.ne[2]);
+        m_ne3 = std::max<int64_t>(1, mk.ne[3]);
+        if (H % m_ne2 || S % m_ne3) return FATTN_ERR_INVALID_ARG;
+        if (m_ne2 > 1) m_nb2 = mk.nb[2];
+        if (m_ne3 > 1) m_nb3 = mk.nb[3];
+        if (m_nb2 % 4 || m_nb3 % 4) return FATTN_ERR_ALIGNMENT;
+        if (m_nb2 < 0 || m_nb3 < 0) return FATTN_ERR_BAD_STRIDE;
+        // (mask_head_off takes iq2 % ne[2] through a float quotient)
+        if (m_ne2 > 1 && H >= (int64_t)1 << 24) return FATTN_ERR_INVALID_ARG;
+    }
 
     // fast path: 16-B pieces.  Quantised rows: contiguous per head (a step of
     // 32 rows is one run of bytes); f16 rows: 16-B aligned
@@ -470,6 +485,7 @@ int make_plan(const fattn_params* p, Plan& pl) {
     else
         g16 = g16 && v.nb[2] % 16 == 0 && v.nb[3] % 16 == 0;
     if (has_mask) g16 = g16 && (uintptr_t)mk.data % 16 == 0 && mk.nb[1] % 16 == 0 && N % kStep == 0;
+    if (has_mask) g16 = g16 && m_nb2 % 16 == 0 && m_nb3 % 16 == 0;  // (every plane's base 16-B aligned)
     if (!g16 && v_trans) return FATTN_ERR_BAD_STRIDE;
     // the dword-granular path needs dword rows (D = 96 Q8_0 / Q4_0 rows are 102 / 54 B:
     // contiguous 16-B-aligned caches only)
@@ -486,6 +502,10 @@ int make_plan(const fattn_params* p, Plan& pl) {
     a.k_nb1 = k.nb[1]; a.k_nb2 = k.nb[2]; a.k_nb3 = k.nb[3];
     a.v_nb0 = v.nb[0]; a.v_nb1 = v.nb[1]; a.v_nb2 = v.nb[2]; a.v_nb3 = v.nb[3];
     a.m_nb1 = has_mask ? mk.nb[1] : 0;
+    a.m_nb2 = m_nb2; a.m_nb3 = m_nb3;
+    a.m_ne2 = (int)m_ne2; a.m_ne3 = (int)m_ne3;
+    a.m_ne2_inv = 1.0f / (float)m_ne2;
+    a.m_hg = 1;
     a.NQ = (int)NQ; a.H = (int)H; a.S = (int)S; a.N = (int)N;
     a.rk2 = (int)(H / Hkv);
     a.rk3 = (int)(S / Skv);
@@ -501,13 +521,17 @@ int make_plan(const fattn_params* p, Plan& pl) {
     // byte spans addressed through the 32-bit buffer descriptors
     const int64_t k_span = (N - 1) * k.nb[1] + (int64_t)rowK;
     const int64_t v_span = v_trans ? (D - 1) * v.nb[0] + N * 2 : (N - 1) * v.nb[1] + (int64_t)rowV;
+    // (one plane's; a sequence plane moves the descriptor's base, the head
+    // planes are offsets inside it: m_span_h)
     const int64_t m_span = has_mask ? (NQ - 1) * mk.nb[1] + mk.ne[0] * 2 : 0;
+    const int64_t m_span_h = m_span + (m_ne2 - 1) * m_nb2;
     const int64_t q_span = (NQ - 1) * q.nb[1] + (H - 1) * q.nb[2] + D * 4;
     const int64_t span_max = (int64_t)0xFFFFFFF0;
-    if (k_span > span_max || v_span > span_max || m_span > span_max || q_span > span_max) return FATTN_ERR_BAD_STRIDE;
+    if (k_span > span_max || v_span > span_max || m_span_h > span_max || q_span > span_max) return FATTN_ERR_BAD_STRIDE;
     a.k_span = (uint32_t)k_span;
     a.v_span = (uint32_t)v_span;
     a.m_span = (uint32_t)m_span;
+    a.m_span_h = (uint32_t)m_span_h;
     a.q_span = (uint32_t)q_span;
 
     pl.kt = k.type;
@@ -534,7 +558,10 @@ int make_plan(const fattn_params* p, Plan& pl) {
     const int64_t qpt64 = (quant_ok || f16_ok) ? 64 / a.rk2 : 1;  // query rows per 64-row tile (rk2 <= 64)
     const int64_t y64 = Hkv * ((NQ + qpt64 - 1) / qpt64);
     const bool wide = N * y64 * S >= (int64_t)2 * kBdKeys * pl.cus;
-    pl.mq = mq_ok && NQ * a.rk2 >= g_opt_mq_min_rows &&
+    // (the multi-query kernel shares one mask row among a query row's heads:
+    // with head planes the planner leaves it, for the batched-decode or the
+    // split kernel, as scale <= 0 leaves the prefill kernels)
+    pl.mq = mq_ok && m_ne2 == 1 && NQ * a.rk2 >= g_opt_mq_min_rows &&
             (wide || NQ * a.rk2 >= 256 || g_opt_mq_min_rows_set);  // (an explicit threshold wins)
     if (pl.mq) {
         // 256 rows per workgroup once that still gives one workgroup per CU
@@ -605,6 +632,13 @@ int make_plan(const fattn_params* p, Plan& pl) {
     }
     const int64_t Y = (int64_t)Hkv * a.n_hsub * a.n_qt;
     if (Y > 65535 || S > 65535) return FATTN_ERR_INVALID_ARG;
+    // split kernel with head planes: one staged mask row per packed (query row,
+    // head) pair; its rows past the tile take offset m_span_h plus a step's
+    // position, which must stay past the descriptor in 32 bits
+    if (!pl.mq && !pl.pf && !pl.bd && m_ne2 > 1) {
+        a.m_hp = 1;
+        if (m_span_h + m_span + 64 > span_max) return FATTN_ERR_BAD_STRIDE;
+    }
     if (pl.bd) return size_bd(pl, p->kv_chunk, Y, S, N);
     if (pl.pf) {
         a.chunk_len = (int)N;
@@ -661,7 +695,9 @@ int make_plan(const fattn_params* p, Plan& pl) {
         // later decode supersedes whatever the flags left there (its epoch
         // stamp, arrival_begin in fattn_split.h), so nothing is re-zeroed.
         pl.pf_flags = has_mask && !g_opt_pf_no_skip;
-        if (pl.pf_flags) pl.cnt_bytes = ((size_t)a.n_qt * (N / kPfKeys) + 255) / 256 * 256;
+        // (one table per sequence plane and group of head planes, pf_flag_table)
+        if (m_ne2 % a.rk2 == 0) a.m_hg = (int)(m_ne2 / a.rk2);
+        if (pl.pf_flags) pl.cnt_bytes = ((size_t)m_ne3 * a.m_hg * a.n_qt * (N / kPfKeys) + 255) / 256 * 256;
         pl.ws_bytes = pl.cnt_bytes;
         if (pl.pf_stage) {
             pl.stage_off = pl.cnt_bytes;
@@ -866,8 +902,10 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
                       pl.nld ? "fattn_split_ld_kernel" : "fattn_split_kernel", tn(pl.kt), tn(pl.vt),
                       pl.D, pl.gran, hm, pl.nwv, pl.nld ? "+4loaders" : "", pl.a.xcd_group ? " (xcd order)" : "",
                       pl.a.merge_launch == 1 ? (pl.a.part_f16 ? " + fattn_merge_kernel(f16 partials)" : pl.merge_plain ? " + fattn_merge_kernel(plain)" : " + fattn_merge_kernel") : pl.a.merge_launch == 2 ? " (in-kernel merge)" : "");
-    const int n = std::snprintf(out, cap, "%s grid(%u,%u,%u) lds %d chunk %d steps/slots %d ws %zu", kern, pl.grid.x,
-                                pl.grid.y, pl.grid.z, pl.lds, pl.a.chunk_len, pl.a.nbuf, pl.ws_bytes);
+    char planes[48] = "";
+    if (pl.a.m_ne2 > 1 || pl.a.m_ne3 > 1) std::snprintf(planes, sizeof planes, " mask planes (%d,%d)", pl.a.m_ne2, pl.a.m_ne3);
+    const int n = std::snprintf(out, cap, "%s grid(%u,%u,%u) lds %d chunk %d steps/slots %d ws %zu%s", kern, pl.grid.x,
+                                pl.grid.y, pl.grid.z, pl.lds, pl.a.chunk_len, pl.a.nbuf, pl.ws_bytes, planes);
     return n < 0 || (size_t)n >= cap ? FATTN_ERR_INVALID_ARG : FATTN_OK;
 }
 

@@ -404,7 +404,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
     const uint32_t lds0 = lds_addr(smem);
     constexpr int kRing = C::nRaw ? C::nRaw : 1;  // (f16: no raw slots)
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % kRing) * C::rawBytes; };
@@ -443,14 +443,15 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     const uint32_t mslot = lds0 + C::maskOff + wave * C::maskSlot;
     uint32_t mrow_l;
     {
-        mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 : a.m_span;
+        // (head planes: the row of this packed row's own q head's plane)
+        mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 + mask_head_off(a, ik2 * a.rk2 + (p - rq0 * a.R)) : a.m_span_h;
     }
     auto mask_issue = [&](int s) {
         if constexpr (HM) {
             const uint32_t n2 = (uint32_t)(c_lo + s * kBdKeys + 32 * kq) * 2;
 #pragma unroll
             for (int i = 0; i < 2; i++)
-                dma<16>(rs.m, mslot + i * 1024, mrow_l == a.m_span ? a.m_span : mrow_l + n2 + 16 * (2 * i + h));
+                dma<16>(rs.m, mslot + i * 1024, mrow_l == a.m_span_h ? a.m_span_h : mrow_l + n2 + 16 * (2 * i + h));
         }
     };
 

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
     const uint32_t lds0 = lds_addr(smem);
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % C::nRaw) * C::rawBytes; };
     auto raw_ptr = [&](int s) { return smem + C::rawOff + (s % C::nRaw) * C::rawBytes; };
@@ -295,14 +295,15 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     // tile, slot (wave, s & 1); DMA instruction i, lane l: octet 2 i + (l >> 5)
     const uint32_t mslot0 = lds0 + C::maskOff + (wave & 3) * 2 * C::maskSlot;
     uint32_t mrow_l;
-    mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 : a.m_span;
+    // (head planes: the row of this packed row's own q head's plane)
+    mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 + mask_head_off(a, ik2 * a.rk2 + (p - rq0 * a.R)) : a.m_span_h;
     auto mask_issue = [&](int s) {
         if constexpr (HM) {
             const uint32_t n2 = (uint32_t)(c_lo + s * kBdpKeys + 32 * kh) * 2;
 #pragma unroll
             for (int i = 0; i < 2; i++)
                 dma<16>(rs.m, mslot0 + (s & 1) * C::maskSlot + i * 1024,
-                        mrow_l == a.m_span ? a.m_span : mrow_l + n2 + 16 * (2 * i + h));
+                        mrow_l == a.m_span_h ? a.m_span_h : mrow_l + n2 + 16 * (2 * i + h));
         }
     };
 

@@ -32,8 +32,9 @@ struct Plan {
     size_t ws_bytes, cnt_bytes, ml_bytes;
     int cus;  // compute units of the device the plan is for
     int nwv;  // split kernel: waves per workgroup (4, 8, 16)
+    // split kernel: loader waves beside the nwv compute waves (fattn_split_ld_kernel), 0 = none
     int nld = 0;
-    bool merge_plain = false;  // second-launch merges (split, batched decode): plain loads (FATTN_OPT_MERGE_PLAIN)  // split kernel: loader waves beside the nwv compute waves (fattn_split_ld_kernel), 0 = none
+    bool merge_plain = false;  // second-launch merges (split, batched decode): plain loads (FATTN_OPT_MERGE_PLAIN)
     bool mq;  // multi-query kernel (fattn_mq.h)
     bool pf;  // prefill kernel (fattn_pf.h)
     bool bd;  // batched-decode kernel (fattn_bd.h)
@@ -246,8 +247,10 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             pa.k_nb2 = pl.stage_k_nb2, pa.k_nb3 = pl.stage_k_nb3, pa.v_nb2 = pl.stage_v_nb2, pa.v_nb3 = pl.stage_v_nb3;
             pa.k16 = (uint16_t*)pl.a.k, pa.v16 = (uint16_t*)pl.a.v;
             pa.mask = pl.a.mask, pa.m_nb1 = pl.a.m_nb1, pa.NQ = pl.a.NQ, pa.QPT = pl.a.QPT;
-            pa.ntiles = pl.a.N / kPfKeys, pa.flags = (uint8_t*)pl.a.pf_flags;
-            const int64_t nfl = flags ? (int64_t)pa.ntiles * pl.a.n_qt : 0;
+            pa.m_nb2 = pl.a.m_nb2, pa.m_nb3 = pl.a.m_nb3, pa.m_ne2 = pl.a.m_ne2, pa.m_ne3 = pl.a.m_ne3, pa.m_hg = pl.a.m_hg;
+            pa.ntiles = pl.a.N / kPfKeys, pa.n_qt = pl.a.n_qt, pa.flags = (uint8_t*)pl.a.pf_flags;
+            // one flag table per (sequence plane, head-plane group)
+            const int64_t nfl = flags ? (int64_t)pa.ntiles * pl.a.n_qt * pl.a.m_ne3 * pl.a.m_hg : 0;
             const int64_t nst = staged ? 2 * (int64_t)pa.per_head * pa.hkv * pa.skv : 0;
             const dim3 g((unsigned)(nst + nfl));
             if (!staged) hipLaunchKernelGGL(pf_prepass_kernel<0>, g, dim3(256), 0, st, pa);

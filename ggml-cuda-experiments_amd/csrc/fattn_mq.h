@@ -98,7 +98,7 @@ __device__ __forceinline__ void mq_issue(const SplitArgs& a, const StepSrc& rs, 
             const int mr = q / 4, off = (q % 4) * 16;  // 64-B mask row = 4 pieces
             // rows past the tile's QPT query rows: outside the descriptor (no traffic)
             const uint32_t moff =
-                mr < a.QPT ? (uint32_t)(mrow0 + mr) * (uint32_t)a.m_nb1 + (uint32_t)n0 * 2 + off : a.m_span;
+                mr < a.QPT ? (uint32_t)(mrow0 + mr) * (uint32_t)a.m_nb1 + (uint32_t)n0 * 2 + off : a.m_span_h;
             dma<16>(rs.m, lb + 2 * C::kvRaw + i * NT * 16, moff);
         }
     }
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
     const int mrow0 = qt * a.QPT;
     auto raw = [&](int s) { return smem + (s % C::nRaw) * C::rawBytes; };
     auto k16_of = [&](int s) { return smem + C::imgOff + (s & 1) * 2 * C::img; };

@@ -219,6 +219,19 @@ __device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 
+// The live-block flag table [n_qt][N / 64] of the tiles of kv head ik2 in
+// sequence iq3.  The pre-pass writes one table per (sequence plane, group of
+// head planes): with m_ne2 % rk2 == 0 a tile's rk2 heads read the planes of
+// group ik2 % m_hg (m_hg = m_ne2 / rk2) and a block's flag is the OR over them;
+// otherwise one group, the OR over all m_ne2 planes (exact when m_ne2 divides
+// rk2, a superset of the tile's planes else: flags may only say "live" or
+// "nonzero" more often, never less)
+__device__ __forceinline__ const uint8_t* pf_flag_table(const SplitArgs& a, int iq3, int ik2) {
+    if (a.m_ne3 == 1 && a.m_hg == 1) return a.pf_flags;
+    const int t = (iq3 % a.m_ne3) * a.m_hg + ik2 % a.m_hg;
+    return a.pf_flags + (int64_t)t * a.n_qt * (a.N / kPfKeys);
+}
+
 template <int KT, int D, bool HM>
 __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const SplitArgs a) {
     using C = PfCfg<KT, D>;
@@ -276,7 +289,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     // that are -inf for a whole wave are skipped below.
     int t0 = 0, ntiles = a.N / kPfKeys;
     if (a.pf_flags) {
-        const uint8_t* fl = a.pf_flags + (int64_t)qt * ntiles;
+        const uint8_t* fl = pf_flag_table(a, iq3, ik2) + (int64_t)qt * ntiles;
         int lo = ntiles, hi = -1;
         for (int b = 0; b < ntiles; b += kWave) {  // wave-uniform; every wave computes the same range
             const bool f = b + lane < ntiles && fl[b + lane] != 0;
@@ -297,7 +310,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     // Bit s of zb[s / 64]: tile t0 + s (the first 256 live tiles).
     uint64_t zb[4] = {0, 0, 0, 0};
     if (a.pf_flags) {
-        const uint8_t* fl = a.pf_flags + (int64_t)qt * (a.N / kPfKeys) + t0;
+        const uint8_t* fl = pf_flag_table(a, iq3, ik2) + (int64_t)qt * (a.N / kPfKeys) + t0;
 #pragma unroll
         for (int w = 0; w < 4; w++) {
             const int b = 64 * w + lane;
@@ -308,7 +321,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
     const uint32_t lds0 = lds_addr(smem);
     constexpr int kNRaw = C::nRaw ? C::nRaw : 1;
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % kNRaw) * C::rawBytes; };
@@ -347,7 +360,8 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
             int q1, q2;
             const bool ok = row_of(kPfRowsW * wave + rr, q1, q2);
             const int pc = (lane & 7) ^ ((rr >> 1) & 7);
-            moff[k] = ok ? (uint32_t)q1 * (uint32_t)a.m_nb1 + 16 * pc : a.m_span;
+            // (head planes: the row of the packed row's own q head's plane)
+            moff[k] = ok ? (uint32_t)q1 * (uint32_t)a.m_nb1 + mask_head_off(a, q2) + 16 * pc : a.m_span_h;
         }
     }
     // tile s's mask block is +-0 everywhere (flag 2; wave-uniform)
@@ -371,7 +385,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
             if (kSkipZero && zero) return;
 #pragma unroll
             for (int k = 0; k < C::NIM; k++) {
-                const uint32_t off = (moff[k] == a.m_span || zero) ? a.m_span : moff[k] + n2;
+                const uint32_t off = (moff[k] == a.m_span_h || zero) ? a.m_span_h : moff[k] + n2;
                 dma<16>(rs.m, mslot + k * 1024, off);
             }
 #endif
@@ -774,15 +788,18 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
 // block adds nothing), 2 when every value is +-0 (the mask adds nothing: its
 // DMA is skipped), else 1.  One workgroup per block; every flag is written on
 // every launch, so the array needs no initialisation.  Reads the mask once
-// (f16 [NQ][N]).
-__device__ __forceinline__ void pf_mask_flags_block(const uint8_t* __restrict__ mask, int64_t m_nb1, int NQ, int QPT,
-                                                    int ntiles, uint8_t* __restrict__ flags, int s, int qt) {
+// (f16 [NQ][N]).  `planes` head planes, m_nb2 bytes apart from `mask` on, are
+// OR-ed into the one flag (pf_flag_table); `flags` is the block's own table.
+__device__ __forceinline__ void pf_mask_flags_block(const uint8_t* __restrict__ mask, int64_t m_nb1, int64_t m_nb2,
+                                                    int planes, int NQ, int QPT, int ntiles,
+                                                    uint8_t* __restrict__ flags, int s, int qt) {
     // thread -> (row qt*QPT + r, 16-B piece pc of the tile's 128 B): 8 pieces
     // per row; batches of 8 loads issued before one wait (a load per loop trip
     // made the block 8 serial memory round trips); rows past the mask re-read
     // its last row and count for nothing
     constexpr int kB = 8;
     uint32_t open = 0, nonzero = 0;
+    for (int pl = 0; pl < planes; pl++, mask += m_nb2)
     for (int i0 = threadIdx.x; i0 < QPT * 8; i0 += 256 * kB) {
         u32x4 w[kB];
         bool ok[kB];
@@ -810,7 +827,7 @@ __device__ __forceinline__ void pf_mask_flags_block(const uint8_t* __restrict__ 
 }
 static __global__ __launch_bounds__(256) void pf_mask_flags_kernel(const uint8_t* __restrict__ mask, int64_t m_nb1, int NQ,
                                                             int QPT, int ntiles, uint8_t* __restrict__ flags) {
-    pf_mask_flags_block(mask, m_nb1, NQ, QPT, ntiles, flags, blockIdx.x, blockIdx.y);
+    pf_mask_flags_block(mask, m_nb1, 0, 1, NQ, QPT, ntiles, flags, blockIdx.x, blockIdx.y);
 }
 
 // The prefill's pre-pass in ONE launch (round 6): the K rows staged to f16,
@@ -832,8 +849,10 @@ struct PfPrepassArgs {
     int hkv, skv;
     const uint8_t* mask;
     int64_t m_nb1;
-    int NQ, QPT, ntiles, flags_on;
-    uint8_t* flags;
+    int64_t m_nb2, m_nb3;  // mask planes (SplitArgs): one flag table per (sequence plane, head-plane group)
+    int m_ne2, m_ne3, m_hg;
+    int NQ, QPT, ntiles, n_qt, flags_on;
+    uint8_t* flags;        // [m_ne3][m_hg][n_qt][ntiles]
 };
 template <int STK>
 __global__ __launch_bounds__(256) void pf_prepass_kernel(const PfPrepassArgs p) {
@@ -852,7 +871,20 @@ __global__ __launch_bounds__(256) void pf_prepass_kernel(const PfPrepassArgs p) 
         }
         b -= 2 * nsk;
     }
-    pf_mask_flags_block(p.mask, p.m_nb1, p.NQ, p.QPT, p.ntiles, p.flags, (int)(b % p.ntiles), (int)(b / p.ntiles));
+    // b = ((sequence plane * m_hg + head-plane group) * n_qt + query tile) * ntiles + KV tile
+    const int s = (int)(b % p.ntiles);
+    const int64_t bq = b / p.ntiles;
+    int qt = (int)bq, tbl = 0;
+    const uint8_t* mask = p.mask;
+    int planes = 1;
+    if (p.m_ne3 != 1 || p.m_ne2 != 1) {
+        qt = (int)(bq % p.n_qt);
+        tbl = (int)(bq / p.n_qt);
+        planes = p.m_ne2 / p.m_hg;  // head planes per group
+        mask += (int64_t)(tbl / p.m_hg) * p.m_nb3 + (int64_t)(tbl % p.m_hg) * planes * p.m_nb2;
+    }
+    pf_mask_flags_block(mask, p.m_nb1, p.m_nb2, planes, p.NQ, p.QPT, p.ntiles,
+                        p.flags + (int64_t)tbl * p.n_qt * p.ntiles, s, qt);
 }
 
 }  // namespace fattn

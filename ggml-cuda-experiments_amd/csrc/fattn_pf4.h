@@ -249,7 +249,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
     int t0 = 0, nt = a.N / kPfKeys;
     uint64_t zb[4] = {0, 0, 0, 0};
     if (a.pf_flags) {
-        const uint8_t* fl = a.pf_flags + (int64_t)qt * nt;
+        const uint8_t* fl = pf_flag_table(a, iq3, ik2) + (int64_t)qt * nt;
         int lo = nt, hi = -1;
         for (int b = 0; b < nt; b += kWave) {  // wave-uniform
             const bool f = b + lane < nt && fl[b + lane] != 0;
@@ -260,9 +260,8 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
             }
         }
         t0 = lo;
-        const int all = nt;
         nt = hi >= lo ? hi - lo + 1 : 0;
-        const uint8_t* fz = a.pf_flags + (int64_t)qt * all + t0;
+        const uint8_t* fz = fl + t0;
 #pragma unroll
         for (int w = 0; w < 4; w++) zb[w] = __builtin_amdgcn_ballot_w64(64 * w + lane < nt && fz[64 * w + lane] == 2);
     }
@@ -271,7 +270,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
     const uint32_t lds0 = lds_addr(smem);
     typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
@@ -341,7 +340,8 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
             int q1, q2;
             const bool ok = row_of(kPf4RowsW * wave + rr, q1, q2);
             const int pc = (lane & 7) ^ ((rr >> 1) & 7);
-            moff[k] = ok ? (uint32_t)q1 * (uint32_t)a.m_nb1 + 16 * pc : a.m_span;
+            // (head planes: the row of the packed row's own q head's plane)
+            moff[k] = ok ? (uint32_t)q1 * (uint32_t)a.m_nb1 + mask_head_off(a, q2) + 16 * pc : a.m_span_h;
         }
     }
 
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
                 if constexpr (MM) {
                     const uint32_t n2 = (uint32_t)(t0 + s) * kPfKeys * 2;
                     const uint32_t dst = lds0 + C::mOff + (wave * C::MS + s % C::MS) * C::maskSlot + k * 1024;
-                    dma<16>(rs.m, dst, (skip || moff[k] == a.m_span) ? a.m_span : moff[k] + n2);
+                    dma<16>(rs.m, dst, (skip || moff[k] == a.m_span_h) ? a.m_span_h : moff[k] + n2);
                 }
             };
             // prologue: K 0 | K 1, mask 0 | K 2, mask 1 (the last two groups as

@@ -65,7 +65,19 @@ struct SplitArgs {
     int64_t k_nb1, k_nb2, k_nb3;
     int64_t v_nb0, v_nb1, v_nb2, v_nb3;
     int64_t m_nb1;
-    uint32_t k_span, v_span, m_span, q_span;  // bytes addressed per (kv head, seq) / mask / seq of Q
+    // mask planes (ggml's mask ne[2] / ne[3]): query head iq2 of sequence iq3 reads
+    // plane (iq2 % m_ne2, iq3 % m_ne3), m_nb2 / m_nb3 bytes apart (any order, gaps,
+    // 0 = one plane repeated).  A workgroup serves one iq3, so the sequence plane
+    // moves its descriptor's base (mask_seq_base); the head plane is a per-row
+    // offset (mask_head_off) inside a descriptor of m_span_h bytes
+    int64_t m_nb2, m_nb3;
+    int m_ne2, m_ne3;       // plane counts, >= 1 (1, 1: one plane for every head and sequence)
+    float m_ne2_inv;        // 1 / m_ne2 (mask_head_off)
+    uint32_t m_span_h;      // m_span + (m_ne2 - 1) * m_nb2: the bytes of one sequence plane's descriptor
+    int m_hp;               // split kernel: 1 = head planes -- one staged mask row per packed (query
+                            // row, head) pair instead of one per query row (mask_row_off)
+    int m_hg;               // prefill: flag tables per sequence plane (groups of head planes, pf_flag_table)
+    uint32_t k_span, v_span, m_span, q_span;  // bytes addressed per (kv head, seq) / mask plane / seq of Q
     int NQ, H, S;       // q ne1, ne2, ne3
     int N;              // kv length
     int rk2, rk3;       // H/Hkv, S/Skv
@@ -82,7 +94,7 @@ struct SplitArgs {
     int nbuf;           // steps in flight per wave (1..4); LDS per wave = wave_bytes
     int wave_bytes;
     int pf_stagger;     // prefill kernel: SIMD partner waves run their phases staggered
-    const uint8_t* pf_flags;  // prefill: [n_qt][N/64] live-block flags (pf_mask_flags_kernel), or null
+    const uint8_t* pf_flags;  // prefill: [m_ne3][m_hg][n_qt][N/64] live-block flags (pf_mask_flags_block), or null
     int split_prio;     // split kernel wave priorities: 0 staggered 3/2/1/0, 1 none, 2 staggered while issuing
     int wave_merge;     // split kernel epilogue: 0 = LDS merge of the waves + combine_tile;
                         // 1 = one-row tiles: every wave publishes its own partial and the
@@ -298,6 +310,8 @@ __device__ __forceinline__ void dma(const i32x4& srd, uint32_t lds_any, uint32_t
 
 struct StepSrc {
     i32x4 k, v, m;
+    int mh0, mhn;  // split kernel, head planes: the tile's first q head and its head count (mask_row_off)
+    int mrows;     // split kernel, 16-B path: staged mask rows that are requested
 };
 
 // ---------------------------------------------------------------- arrivals
@@ -365,11 +379,66 @@ __device__ __forceinline__ int tile_arrive_wait(const SplitArgs& a, int64_t tile
     return 0;
 }
 
+// ---------------------------------------------------------------- mask planes
+__device__ __forceinline__ int div_R(const SplitArgs& a, int m);
+
+// base of the sequence plane that the workgroup's iq3 reads (the query's
+// sequence, not the KV's: sequences that share one KV may differ in mask)
+__device__ __forceinline__ const uint8_t* mask_seq_base(const SplitArgs& a, int iq3) {
+    return a.m_ne3 == 1 ? a.mask : a.mask + (int64_t)(iq3 % a.m_ne3) * a.m_nb3;
+}
+
+// byte offset of q head iq2's plane, (iq2 % m_ne2) * m_nb2, without a runtime
+// division: the quotient by float, at most one off (iq2 < 2^24), then corrected
+__device__ __forceinline__ uint32_t mask_head_off(const SplitArgs& a, int iq2) {
+    if (a.m_ne2 == 1) return 0u;
+    int r = iq2 - (int)(((float)iq2 + 0.5f) * a.m_ne2_inv) * a.m_ne2;
+    r = r < 0 ? r + a.m_ne2 : r >= a.m_ne2 ? r - a.m_ne2 : r;
+    return (uint32_t)r * (uint32_t)a.m_nb2;
+}
+
+// split kernel: descriptor and tile geometry of the mask rows it stages
+template <bool HM>
+__device__ __forceinline__ void split_mask_src(const SplitArgs& a, StepSrc& rs, int iq3, int ik2, int hs) {
+    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    rs.mh0 = ik2 * a.rk2 + hs * a.R;
+    rs.mhn = min(a.R, a.rk2 - hs * a.R);
+    rs.mrows = a.m_hp ? kRows : a.QPT;
+}
+
+// split kernel: byte offset of the mask row staged as row r of a step's 16.
+// One plane for all heads: query row mrow0 + r (the R packed heads share it).
+// Head planes (a.m_hp): packed row r = (query row r / R, head r % R) in its own
+// head's plane; rows the tile does not have point past the descriptor (zeros,
+// no traffic -- the planner keeps m_span_h + a row's bytes inside 32 bits)
+__device__ __forceinline__ uint32_t mask_row_off(const SplitArgs& a, const StepSrc& rs, int mrow0, int r) {
+    if (!a.m_hp) return (uint32_t)(mrow0 + r) * (uint32_t)a.m_nb1;
+    const int rq = div_R(a, r), hh = r - rq * a.R;
+    const bool ok = rq < a.QPT && mrow0 + rq < a.NQ && hh < rs.mhn;
+    return ok ? (uint32_t)(mrow0 + rq) * (uint32_t)a.m_nb1 + mask_head_off(a, rs.mh0 + hh) : a.m_span_h;
+}
+
+// split kernel: this lane's byte offset (row + piece) in each of a step's NIM
+// mask instructions, position 0 -- computed once per wave, ahead of the loop
+// (computed per step, the head-plane geometry stayed live in SGPRs across the
+// loop and the dword-path bodies spilled)
+template <int KT, int VT, int D, int GRAN>
+__device__ __forceinline__ void mask_lane_offsets(const SplitArgs& a, const StepSrc& rs, int mrow0, int lane,
+                                                  uint32_t (&ml)[StepPlan<KT, VT, D, GRAN>::NIM]) {
+    using P = StepPlan<KT, VT, D, GRAN>;
+#pragma unroll
+    for (int i = 0; i < P::NIM; i++) {
+        const int q = i * kWave + lane;
+        ml[i] = mask_row_off(a, rs, mrow0, q / P::MPR) + (q % P::MPR) * P::MG;
+    }
+}
+
 // One step = [K rows | V rows | mask rows] for positions [n0, n0+32), copied
 // as raw bytes.  GRAN = 16: 16-B pieces (quantised rows contiguous, f16 rows
 // 16-B aligned); GRAN = 4: dword pieces for any ggml row stride.
 template <int KT, int VT, int D, int GRAN, bool HM>
-__device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs, int n0, int mrow0, uint8_t* buf,
+__device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs, int n0,
+                                           const uint32_t (&ml)[StepPlan<KT, VT, D, GRAN>::NIM], uint8_t* buf,
                                            int lane, bool kv_live = true) {
 #ifdef FATTN_DIAG_NOMEM
     return;  // diagnostic build only: compute on whatever LDS holds (compute latency)
@@ -407,14 +476,13 @@ __device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs
         uint8_t* mbuf = buf + C::kBytes + C::vBytes;
 #pragma unroll
         for (int i = 0; i < P::NIM; i++) {
-            const int q = i * kWave + lane;
-            const int mr = q / P::MPR;
-            const int off = (q % P::MPR) * P::MG;
-            const uint32_t moff = (uint32_t)(mrow0 + mr) * (uint32_t)a.m_nb1 + (uint32_t)n0 * 2 + off;
+            const int mr = (i * kWave + lane) / P::MPR;
+            const uint32_t moff = ml[i] + (uint32_t)n0 * 2;
             // 16-B path (one instruction, rows 0..15): lanes of rows past the
             // tile's query rows stay idle -- row 0's lanes always issue it, so
             // the per-step instruction count (vmcnt budget) is unchanged
-            if (GRAN != 16 || mr < a.QPT) dma<P::MG>(rs.m, lds_addr(mbuf + i * kWave * P::MG), moff);
+            // (head planes: all 16 rows, one per packed (query row, head) pair)
+            if (GRAN != 16 || mr < rs.mrows) dma<P::MG>(rs.m, lds_addr(mbuf + i * kWave * P::MG), moff);
         }
     }
     uint8_t* vbuf = buf + C::kBytes;
@@ -1255,11 +1323,13 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
 // One 32-position step of one wave: S^T = K.Q^T for the step's two 16-row
 // key tiles, scale + mask, online softmax of the wave's 16 packed columns,
 // O^T += V^T.P^T.  `buf` is the step's LDS image [K rows | V rows | mask rows];
-// `wait_v()` runs between the softmax and P.V (the split kernel waits there
-// for the step's V, which it issues last).  `first`: o, l are still zero.
+// `mrow`: the staged mask row of this lane's column (its query row's, or with
+// head planes its own packed row's).  `wait_v()` runs between the softmax and
+// P.V (the split kernel waits there for the step's V, which it issues last).
+// `first`: o, l are still zero.
 // Used by fattn_split_kernel.
 template <int KT, int VT, int D, bool HM, typename WaitV>
-__device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mq,
+__device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mrow,
                                            int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
                                            f32x4 (&o)[D / 16], float (&corr)[(D + QK - 1) / QK], WaitV&& wait_v) {
     using C = SplitCfg<KT, VT, D>;
@@ -1295,7 +1365,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
 #pragma unroll
     for (int t = 0; t < 2; t++) {
         if constexpr (HM) {
-            const uint8_t* mp = mb + (mq < a.QPT ? mq : 0) * (kStep * 2) + (16 * t + 4 * g) * 2;
+            const uint8_t* mp = mb + mrow * (kStep * 2) + (16 * t + 4 * g) * 2;
             const u32x2 mw = *(const u32x2*)mp;
             const f16x2 m01 = as_h2(mw.x), m23 = as_h2(mw.y);
             sv[4 * t + 0] = __builtin_fmaf(st[t][0], a.scale, (float)m01.x);
@@ -1475,6 +1545,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     const int iq1 = qt * a.QPT + mq;
     const int iq2 = ik2 * a.rk2 + mh;
     const bool row_ok = (m < a.QPT * a.R) && (iq1 < a.NQ) && (mh < a.rk2);
+    const int mrow = a.m_hp ? m : (mq < a.QPT ? mq : 0);  // this column's staged mask row (split_step)
 
     // ---- this wave's KV slice
     const int wl = a.chunk_len / NWV;
@@ -1487,9 +1558,11 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    split_mask_src<HM>(a, rs, iq3, ik2, hs);
     uint8_t* wbuf = smem + wave * a.wave_bytes;
     const int mrow0 = qt * a.QPT;
+    uint32_t ml[P::NIM];
+    mask_lane_offsets<KT, VT, D, GRAN>(a, rs, mrow0, lane, ml);
 
     // Staggered priorities: the waves of a CU otherwise interleave their DMA
     // issue, so every wave's last piece lands near the end of the burst and
@@ -1539,18 +1612,20 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     // ahead of the first wait).  Reading the words after step 0 instead, or
     // skipping by control flow in the loop, measured slower everywhere.
     const int pro = min(nbuf, nsteps);  // steps issued before the loop
-    const int n_rows = HM ? min(a.QPT, a.NQ - mrow0) : 0;
+    // (head planes: one staged row per packed (query row, head) pair -- all of
+    // them are looked at)
+    const int n_rows = !HM ? 0 : a.m_hp ? tile_rows(a, qt, hs) : min(a.QPT, a.NQ - mrow0);
     const bool pre = HM && a.step_skip && nsteps >= 4 && n_rows * nsteps <= kWave;
     u32x4 mraw[4] = {};
     if (pre) {
         const int r = lane / nsteps, st = lane - r * nsteps;
-        const uint32_t moff = r < n_rows ? (uint32_t)(mrow0 + r) * (uint32_t)a.m_nb1 + (uint32_t)(w_lo + st * kStep) * 2
-                                         : a.m_span;  // past the descriptor: no traffic
+        const uint32_t moff = r < n_rows ? mask_row_off(a, rs, mrow0, r) + (uint32_t)(w_lo + st * kStep) * 2
+                                         : a.m_span_h;  // past the descriptor: no traffic
 #pragma unroll
         for (int j = 0; j < 4; j++) mraw[j] = ld_buf_untracked<kTagMaskWords>(rs.m, moff + 16 * j);
     }
     for (int s = 0; s < pro; s++) {
-        issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + s * kStep, mrow0, wbuf + s * C::stepBytes, lane);
+        issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + s * kStep, ml, wbuf + s * C::stepBytes, lane);
     }
     // this launch's stamp on the tile's arrival word, by each lane that will
     // count an arrival: issued after the prologue's DMA, so no wait is spent
@@ -1612,7 +1687,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
         // diagnostic build only: memory-side ceiling of this access pattern
         wait_steps<NI>(ahead);
         if (s + nbuf < nsteps) {
-            issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + (s + nbuf) * kStep, mrow0, wbuf + cur * C::stepBytes, lane);
+            issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + (s + nbuf) * kStep, ml, wbuf + cur * C::stepBytes, lane);
         }
         cur = (cur + 1 == nbuf) ? 0 : cur + 1;
         continue;
@@ -1620,7 +1695,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;  // hides "first step" from loop peeling (a second copy of the body)
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM>(a, wbuf + cur * C::stepBytes, qop, mq, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
+        split_step<KT, VT, D, HM>(a, wbuf + cur * C::stepBytes, qop, mrow, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
                                   m_run, l_run, o, corr, [&] { wait_steps<NI>(ahead); });
         if (nsteps <= 4 && s < 2) FATTN_SSTAMP(6 + 2 * s);  // (stamps build: step s computed)
 
@@ -1628,7 +1703,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
         if (s + nbuf < nsteps) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int sn = s + nbuf;
-            issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + sn * kStep, mrow0, wbuf + cur * C::stepBytes, lane,
+            issue_step<KT, VT, D, GRAN, HM>(a, rs, w_lo + sn * kStep, ml, wbuf + cur * C::stepBytes, lane,
                                             sn >= 64 || ((live >> sn) & 1));
             if (nsteps <= 4 && s < 2) FATTN_SSTAMP(7 + 2 * s);  // (stamps build: step s + nbuf issued)
         }
@@ -1714,7 +1789,9 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
     StepSrc rs;
     rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
     rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(a.mask, HM ? a.m_span : 0);
+    split_mask_src<HM>(a, rs, iq3, ik2, hs);
+    uint32_t ml[P::NIM];
+    mask_lane_offsets<KT, VT, D, 16>(a, rs, mrow0, lane, ml);
 
     if (wave >= NWV) {
         // ---- loader: zero the flags, meet the compute waves once they have
@@ -1729,7 +1806,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
         for (int k = 0; k < U; k++) {
             const int u = L + NLD * k, w = u % NWV, s = 1 + u / NWV;
             const int n0 = chunk * a.chunk_len + w * wl + s * kStep;
-            issue_step<KT, VT, D, 16, HM>(a, rs, n0, mrow0, smem + w * a.wave_bytes + s * C::stepBytes, lane);
+            issue_step<KT, VT, D, 16, HM>(a, rs, n0, ml, smem + w * a.wave_bytes + s * C::stepBytes, lane);
         }
         FATTN_SSTAMP(1);
         for (int k = 0; k < U; k++) {
@@ -1752,6 +1829,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
     const int iq1 = qt * a.QPT + mq;
     const int iq2 = ik2 * a.rk2 + mh;
     const bool row_ok = (m < a.QPT * a.R) && (iq1 < a.NQ) && (mh < a.rk2);
+    const int mrow = a.m_hp ? m : (mq < a.QPT ? mq : 0);  // this column's staged mask row (split_step)
     const int w_lo = chunk * a.chunk_len + wave * wl;
     const int w_hi = min(c_hi, w_lo + wl);
     const int nsteps = w_hi > w_lo ? (w_hi - w_lo + kStep - 1) / kStep : 0;
@@ -1770,7 +1848,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
             qraw[b][1] = ld_buf_untracked<kTagQ>(qs, qb + 16);
         }
     }
-    issue_step<KT, VT, D, 16, HM>(a, rs, w_lo, mrow0, wbuf, lane);
+    issue_step<KT, VT, D, 16, HM>(a, rs, w_lo, ml, wbuf, lane);
     if (a.n_chunks > 1 && lane == 0 && wave == 0) arrival_begin(a, (int64_t)iq3 * gridDim.y + y);
     FATTN_SSTAMP(1);
     __syncthreads();  // every compute wave's step 0 is in the queue: the loaders may issue
@@ -1806,7 +1884,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM>(a, wbuf + s * C::stepBytes, qop, mq, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
+        split_step<KT, VT, D, HM>(a, wbuf + s * C::stepBytes, qop, mrow, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
                                   m_run, l_run, o, corr, [&] {
                                       if (s == 0) wait_vmcnt_c<0>();
                                       else wait_lds_flag(f + 1);

@@ -277,7 +277,15 @@ def q_view(q) -> View:
 
 
 def mask_view(mask) -> View:
-    """mask: torch f16 [rows][N_padded] (ggml ne = [N, rows])."""
+    """mask: torch f16 [rows][N_padded] (ggml ne = [N, rows]): one plane for
+    every head and sequence -- or contiguous [S'][H'][rows][N_padded] (ggml ne =
+    [N, rows, H', S']): query head iq2 of sequence iq3 reads plane
+    (iq2 % H', iq3 % S'); H' divides H, S' divides S (include/fattn.h)."""
+    if mask.dim() == 4:
+        if not mask.is_contiguous():
+            raise ValueError("mask_view: a 4-D mask must be contiguous (build a View for other strides)")
+        Sm, Hm, rows, Np = mask.shape
+        return View(_tptr(mask), TYPE_F16, (Np, rows, Hm, Sm), (2, Np * 2, Np * rows * 2, Np * rows * Hm * 2))
     rows, Np = mask.shape
     return View(_tptr(mask), TYPE_F16, (Np, rows, 1, 1), (2, Np * 2, Np * rows * 2, Np * rows * 2))
 

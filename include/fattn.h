@@ -90,7 +90,23 @@ typedef struct fattn_tensor {
  *        128 and 256: the split-KV kernel takes every such pair
  *   mask F16 ne = [N', rows >= n_q] with N' >= N rounded up to even (ggml pads
  *        mask rows to GGML_KQ_MASK_PAD), 4-byte aligned rows; row = query
- *        index, broadcast over heads and sequences; or data == NULL for no mask
+ *        index; or data == NULL for no mask.  ne[2] and ne[3] are plane counts,
+ *        read as ggml's FLASH_ATTN_EXT reads them: query head iq2 of sequence
+ *        iq3 takes its row from
+ *            data + iq1*nb[1] + (iq2 % ne[2])*nb[2] + (iq3 % ne[3])*nb[3]
+ *        -- ne[3] planes per stream (each sequence its own length, padding or
+ *        window), ne[2] per head (ALiBi-style biases); the indices are the
+ *        query's, so sequences that share one KV (S > Skv) may still differ in
+ *        mask.  ne[2] must divide H and ne[3] must divide S
+ *        (FATTN_ERR_INVALID_ARG); a count < 1 reads as 1 (zeroed structs), and
+ *        (1, 1) is one plane for every head and sequence.  nb[2] / nb[3]: any
+ *        non-negative multiples of 4 (FATTN_ERR_ALIGNMENT) -- either order of
+ *        planes, gaps, or 0 to repeat a plane -- looked at only where the
+ *        count exceeds 1; a stride that is no multiple of 16 turns the 16-B
+ *        path off, as nb[1] % 16 does.  One sequence plane with all its head
+ *        planes, (rows - 1)*nb[1] + N'*2 + (ne[2] - 1)*nb[2] bytes, must stay
+ *        below 4 GiB (FATTN_ERR_BAD_STRIDE).  The masked prefill's workspace
+ *        grows with the plane count (fattn_workspace_size)
  *   dst  f32 contiguous [S][n_q][H][D]
  *   H % Hkv == 0 (GQA broadcast), S % Skv == 0.
  *   softmax(scale * q.k^T + mask) . v per (seq, head, query row).  A row whose
@@ -127,7 +143,8 @@ int fattn_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 int fattn_ext(const fattn_params* p, void* stream);
 
 /* flash-llama.h:7-32 argument list (K and V share nb11..nb13, flash-llama.h:123-125;
- * mask rows padded to ne31, nb31 bytes per row). */
+ * mask rows padded to ne31, nb31 bytes per row; one mask plane -- the list has
+ * no ne32 / ne33 -- as for fattn_row below). */
 int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void* mask, float* dst, float scale,
                          int ne00, int ne01, int ne02, int ne03, int ne10, int ne11, int ne12, int ne13, int ne31,
                          int nb31, int nb01, int nb02, int nb03, int nb11, int nb12, int nb13, int ne0, int ne1,

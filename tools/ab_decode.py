@@ -9,6 +9,14 @@ them alike.  Prints one line per (round, variant) and a median summary.
 
   python tools/ab_decode.py --workload config3 \
       --variant base: --variant spec:SPLIT_SPEC=2 --variant xcd:SPLIT_XCD=2 --rounds 5
+
+A workload with S > 1 is a batch of S sequences, each with its own KV.  The
+variant key mask=ragged gives every sequence its own mask plane (mask ne[3] = S):
+the variant's random values, -inf from the sequence's live length on, the
+lengths spread evenly over (0, N]; mask=shared (the default) is one full-length
+plane for all of them:
+
+  python tools/ab_decode.py --workload config3_s64 --variant shared: --variant ragged:mask=ragged
 """
 import argparse
 import os
@@ -28,6 +36,7 @@ SHAPES = {
     "config5_s4": dict(kv_type="q8_0", H=8, Hkv=8, N=4096, NQ=64, D=128),
     "config5_s2": dict(kv_type="q8_0", H=16, Hkv=16, N=4096, NQ=64, D=128),
     "config5_d256": dict(kv_type="q8_0", H=32, Hkv=32, N=4096, NQ=64, D=256),
+    "config3_s64": dict(kv_type="q8_0", H=32, Hkv=32, N=4096, NQ=1, D=128, S=64),
 }
 
 
@@ -35,11 +44,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="config3", choices=sorted(SHAPES))
     ap.add_argument("--variant", action="append", default=[],
-                    help="name:OPT=val,OPT=val (OPT without the OPT_ prefix); 'kv_chunk=' sets the chunk")
+                    help="name:OPT=val,OPT=val (OPT without the OPT_ prefix); 'kv_chunk=' sets the chunk, "
+                         "'mask=ragged' a mask plane per sequence")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--lib", default="", help="FATTN_LIB override (a variant library under lib/)")
-    for k in ("kv_type", "H", "Hkv", "N", "NQ", "D"):
+    for k in ("kv_type", "H", "Hkv", "N", "NQ", "D", "S"):
         ap.add_argument("--" + k, default=None)
     args = ap.parse_args()
     if args.lib:
@@ -49,57 +59,67 @@ def main():
     import fattn
     from bench import hip_events
 
-    shape = dict(SHAPES[args.workload])
+    shape = {"S": 1, **SHAPES[args.workload]}
     for k in shape:
         v = getattr(args, k)
         if v is not None:
             shape[k] = v if k == "kv_type" else int(v)
-    D, H, Hkv, N, NQ = shape["D"], shape["H"], shape["Hkv"], shape["N"], shape["NQ"]
+    D, H, Hkv, N, NQ, S = shape["D"], shape["H"], shape["Hkv"], shape["N"], shape["NQ"], shape["S"]
     typ = fattn.TYPE_NAMES[shape["kv_type"]]
     rb = fattn.row_size(typ, D)
     dev = torch.device("cuda", 0)
-    R = max(16, -(-(512 << 20) // (2 * Hkv * N * rb)))
+    R = max(16 if S == 1 else 2, -(-(512 << 20) // (2 * S * Hkv * N * rb)))
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
     kvs = []
     for _ in range(R):
         pair = []
         for _ in range(2):
-            x = torch.rand((Hkv * N, D), generator=g, device=dev) * 2 - 1
+            x = torch.rand((S * Hkv * N, D), generator=g, device=dev) * 2 - 1
             pair.append(x.to(torch.float16).view(torch.uint8).reshape(-1) if typ == fattn.TYPE_F16
                         else fattn.quantize(x, typ).reshape(-1))
         kvs.append(pair)
-    q = torch.rand((1, NQ, H, D), generator=g, device=dev) * 2 - 1
+    q = torch.rand((S, NQ, H, D), generator=g, device=dev) * 2 - 1
     npad = (N + 63) // 64 * 64
     masks = [(torch.rand((NQ, npad), generator=g, device=dev) * 2 - 1).to(torch.float16) for _ in range(R)]
-    outs = torch.empty((R, 1, NQ, H, D), dtype=torch.float32, device=dev)
-    alg = 2 * NQ * H * D * 4 + 2 * Hkv * N * rb + NQ * N * 2
+    # mask=ragged: the same values as a plane per sequence, -inf from the sequence's live length on
+    lens = [-(-(s + 1) * N // S) for s in range(S)]
+    ragged = []
+    for m in masks:
+        pl = m.reshape(1, 1, NQ, npad).repeat(S, 1, 1, 1)
+        for s, L in enumerate(lens):
+            pl[s, :, :, L:] = float("-inf")
+        ragged.append(pl.contiguous())
+    outs = torch.empty((R, S, NQ, H, D), dtype=torch.float32, device=dev)
+    alg = S * (2 * NQ * H * D * 4 + 2 * Hkv * N * rb) + NQ * N * 2
 
     variants = []
     for spec in args.variant or ["base:"]:
         name, _, opts = spec.partition(":")
-        od, chunk = {}, 0
+        od, chunk, mk = {}, 0, masks
         for kv in filter(None, opts.split(",")):
             k, _, v = kv.partition("=")
             if k == "kv_chunk":
                 chunk = int(v)
+            elif k == "mask":
+                mk = {"shared": masks, "ragged": ragged}[v]
             else:
                 od[getattr(fattn, "OPT_" + k)] = int(v)
-        variants.append((name, od, chunk))
+        variants.append((name, od, chunk, mk))
 
     hip, evs = hip_events(2)
     gs = torch.cuda.Stream(dev)
     graphs = []
-    for name, od, chunk in variants:
+    for name, od, chunk, mk in variants:
         with fattn.options(od):
-            att = fattn.Attention(fattn.q_view(q), fattn.kv_view(kvs[0][0], typ, D, N, Hkv),
-                                  fattn.kv_view(kvs[0][1], typ, D, N, Hkv), fattn.mask_view(masks[0]), outs[0],
+            att = fattn.Attention(fattn.q_view(q), fattn.kv_view(kvs[0][0], typ, D, N, Hkv, S),
+                                  fattn.kv_view(kvs[0][1], typ, D, N, Hkv, S), fattn.mask_view(mk[0]), outs[0],
                                   1.0 / D ** 0.5, kv_chunk=chunk)
             desc = att.describe()
 
-            def step(i):
+            def step(i, att=att, mk=mk):
                 att.retarget(k=kvs[i % R][0].data_ptr(), v=kvs[i % R][1].data_ptr(), dst=outs[i % R].data_ptr(),
-                             mask=masks[i % R].data_ptr())
+                             mask=mk[i % R].data_ptr())
                 att()
 
             gs.wait_stream(torch.cuda.current_stream(dev))
