@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -149,7 +150,9 @@ int size_split(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N, int64_t 
     const int rv_max = std::min<int64_t>(kRows, (int64_t)a.R * std::min<int64_t>(a.QPT, NQ));
     const int64_t total = steps * Y * S;
     int nwv = 4;
-    if (pl.gran == 16) {
+    // (max_bias / logit_softcap live: 4 waves, the form whose bodies carry the
+    // score transform -- launch_split_e; FATTN_OPT_SPLIT_WAVES does not apply)
+    if (pl.gran == 16 && !a.xf.live) {
         if (g_opt_split_waves > 0) {
             nwv = g_opt_split_waves;
         } else if (kv_chunk <= 0) {
@@ -434,6 +437,11 @@ int make_plan(const fattn_params* p, Plan& pl) {
     const bool mixed = k.type != v.type;
     if (mixed && D != 64 && D != 128 && D != 256) return FATTN_ERR_UNSUPPORTED_TYPE;
     if ((uintptr_t)q.data % 16 || q.nb[1] % 16 || q.nb[2] % 16 || q.nb[3] % 16) return FATTN_ERR_ALIGNMENT;
+    // ggml's op_params[1], [2] and the global head numbering of the slopes
+    if (!std::isfinite(p->max_bias) || p->max_bias < 0.0f) return FATTN_ERR_INVALID_ARG;
+    if (!std::isfinite(p->logit_softcap) || p->logit_softcap < 0.0f) return FATTN_ERR_INVALID_ARG;
+    const int64_t n_head_total = p->n_head_total == 0 ? H : (int64_t)p->n_head_total;
+    if (p->head_first < 0 || (int64_t)p->head_first + H > n_head_total) return FATTN_ERR_INVALID_ARG;
 
     const size_t rowK = fattn_row_size(k.type, D), rowV = fattn_row_size(v.type, D);
     // K rows must be contiguous (nb[0] = element size / block granular)
@@ -517,6 +525,22 @@ int make_plan(const fattn_params* p, Plan& pl) {
     a.has_mask = has_mask ? 1 : 0;
     a.scale_log2 = p->scale * 1.4426950408889634f;
     a.scale = p->scale;
+    // the score transform (ScoreXf): the cap whenever given, the slopes only
+    // with a mask to scale (max_bias without one: the plan of max_bias = 0)
+    if (p->logit_softcap > 0.0f) {
+        a.xf.live |= 1;
+        a.xf.cap = p->logit_softcap;
+        a.xf.scale_cap = p->scale / p->logit_softcap;
+    }
+    if (p->max_bias > 0.0f && has_mask) {
+        int n2 = 1;
+        while ((int64_t)n2 * 2 <= n_head_total) n2 *= 2;
+        a.xf.live |= 2;
+        a.xf.m0_log2 = -(p->max_bias / (float)n2);
+        a.xf.m1_log2 = -(p->max_bias / 2.0f / (float)n2);
+        a.xf.n2 = n2;
+        a.xf.head_first = p->head_first;
+    }
 
     // byte spans addressed through the 32-bit buffer descriptors
     const int64_t k_span = (N - 1) * k.nb[1] + (int64_t)rowK;
@@ -686,7 +710,9 @@ int make_plan(const fattn_params* p, Plan& pl) {
         // take 1.5 % (f16) to 3.6 % (Q8_0 zero mask) off it, profiles/r06_c;
         // form 1 keeps the 8-wave body)
         const int form = g_opt_pf_form == 0 ? 6 : (int)g_opt_pf_form;
-        pl.pf4 = pl.kt == FATTN_TYPE_F16 && D == 128 && form >= 4;
+        // (max_bias / logit_softcap live: fattn_pf_kernel, which has the score
+        // transform -- the one-wave-per-SIMD bodies' asm chains do not)
+        pl.pf4 = pl.kt == FATTN_TYPE_F16 && D == 128 && form >= 4 && !a.xf.live;
         pl.pf4_sched = form - 2;  // 4: pipelined (SCHED 2), 5: balanced (SCHED 3), 6: lean (SCHED 4)
         if (pl.pf4) pl.lds = Pf4Cfg<128>::ldsBytes;
         pl.grid = dim3(1, (unsigned)Y, (unsigned)S);
@@ -835,7 +861,7 @@ int fattn_set_option(int option, int value) {
     }
 }
 
-const char* fattn_version(void) { return "fattn-gfx950 0.1"; }
+const char* fattn_version(void) { return "fattn-gfx950 0.2"; }
 
 const char* fattn_strerror(int s) {
     switch (s) {
@@ -904,8 +930,13 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
                       pl.a.merge_launch == 1 ? (pl.a.part_f16 ? " + fattn_merge_kernel(f16 partials)" : pl.merge_plain ? " + fattn_merge_kernel(plain)" : " + fattn_merge_kernel") : pl.a.merge_launch == 2 ? " (in-kernel merge)" : "");
     char planes[48] = "";
     if (pl.a.m_ne2 > 1 || pl.a.m_ne3 > 1) std::snprintf(planes, sizeof planes, " mask planes (%d,%d)", pl.a.m_ne2, pl.a.m_ne3);
-    const int n = std::snprintf(out, cap, "%s grid(%u,%u,%u) lds %d chunk %d steps/slots %d ws %zu%s", kern, pl.grid.x,
-                                pl.grid.y, pl.grid.z, pl.lds, pl.a.chunk_len, pl.a.nbuf, pl.ws_bytes, planes);
+    // (only what is live in the plan: max_bias without a mask names nothing)
+    char xf[64] = "";
+    int xn = 0;
+    if (pl.a.xf.live & 1) xn = std::snprintf(xf, sizeof xf, " softcap %g", (double)p->logit_softcap);
+    if (pl.a.xf.live & 2) std::snprintf(xf + xn, sizeof xf - xn, " alibi %g", (double)p->max_bias);
+    const int n = std::snprintf(out, cap, "%s grid(%u,%u,%u) lds %d chunk %d steps/slots %d ws %zu%s%s", kern, pl.grid.x,
+                                pl.grid.y, pl.grid.z, pl.lds, pl.a.chunk_len, pl.a.nbuf, pl.ws_bytes, planes, xf);
     return n < 0 || (size_t)n >= cap ? FATTN_ERR_INVALID_ARG : FATTN_OK;
 }
 

@@ -357,6 +357,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     }
     const float log2e = 1.4426950408889634f;
     const float scale = a.scale;
+    const float slope = xf_slope(a.xf, ik2 * a.rk2 + (p - rq0 * a.R));  // this lane's row's q head's ALiBi slope (1: off)
     // per-lane K read base (key 32 kh + c32, half h; halves swapped per
     // bdp_kswz) and V^T gather bases (fattn_bd.h's gather, 64-key images,
     // chunks swizzled per bdp_vswz: keys 32 kh + 16 q + row, the first two
@@ -457,6 +458,20 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
                 } else {
 #pragma unroll
                     for (int r = 0; r < 4; r++) u[4 * uu + r] = st[4 * uu + r] * scale;
+                }
+            }
+            // max_bias / logit_softcap (wave-uniform, a kernel argument; off:
+            // the fma above stands): the scores again through xf_score
+            if (a.xf.live) {
+#pragma unroll
+                for (int uu = 0; uu < 4; uu++) {
+                    float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if constexpr (HM) {
+                        const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
+                        mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r++) u[4 * uu + r] = xf_score(a.xf, scale, st[4 * uu + r], mv[r], slope);
                 }
             }
             float tmax = kNegInf;

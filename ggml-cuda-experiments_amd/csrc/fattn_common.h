@@ -216,6 +216,55 @@ __device__ __forceinline__ void reg_fence(T& v) {
     asm volatile("; RETIRED(%1) %0" : "+v"(v) : "n"(TAG));
 }
 
+// ---------------------------------------------------------------- score transform
+// ggml's FLASH_ATTN_EXT scalars beside `scale` (op_params[1], [2]): ALiBi
+// (max_bias) and the logit soft cap.  Every kernel turns an MFMA accumulator
+// s = q.k into a score at one statement, u = fma(s, scale, mask); with either
+// scalar live that statement becomes xf_score():
+//     x = s * scale                        (no cap)
+//     x = cap * tanh(s * (scale / cap))    (cap > 0)
+//     u = x + slope(h) * mask
+// `live` is a kernel argument (wave-uniform): with both off the kernels keep
+// their one fma and branch around this code.  The host (make_plan) fills the
+// struct; live bit 1 is set only with a mask (max_bias without one changes
+// nothing, as in ggml).
+struct ScoreXf {
+    int live;         // bit 0: soft cap, bit 1: ALiBi slopes; 0: u = s * scale + mask
+    float cap;        // logit_softcap
+    float scale_cap;  // scale / cap
+    // log2 of ggml's slope bases m0 = 2^-(max_bias / n2), m1 = 2^-(max_bias / 2 / n2),
+    // n2 = 2^floor(log2 n_head_total): slope(h) = m0^(h + 1) for h < n2, else m1^(2 (h - n2) + 1)
+    float m0_log2, m1_log2;
+    int n2;
+    int head_first;   // global index of q head 0 (head-sharded launches)
+};
+
+// slope of q head iq2 (the launch's index): one v_exp_f32, once per lane and
+// kernel.  Always > 0, so a -inf mask value stays -inf and +-0 stays +-0.
+__device__ __forceinline__ float xf_slope(const ScoreXf& x, int iq2) {
+    if (!(x.live & 2)) return 1.0f;
+    const int h = x.head_first + iq2;
+    const float e = h < x.n2 ? x.m0_log2 * (float)(h + 1) : x.m1_log2 * (float)(2 * (h - x.n2) + 1);
+    return __builtin_amdgcn_exp2f(e);
+}
+
+// the score (natural units) of accumulator s under mask value m.  tanh from
+// v_exp_f32 / v_rcp_f32, no libm: tanh(t) = 1 - 2 / (1 + 2^(2 log2e t)), which
+// saturates to +-1 exactly as the exponential overflows to inf or underflows
+// to 0.  Both instructions are good to 1 ulp, and for small t the subtraction
+// from 1 leaves an absolute error of about 1e-7 in tanh, so about cap * 1e-7
+// in the logit -- 4e-5 at cap = 400, far below the f16 rounding of P.
+__device__ __forceinline__ float xf_score(const ScoreXf& x, float scale, float s, float m, float slope) {
+    float v;
+    if (x.live & 1) {
+        const float e = __builtin_amdgcn_exp2f(s * x.scale_cap * 2.8853900817779268f);
+        v = __builtin_fmaf(-2.0f * x.cap, __builtin_amdgcn_rcpf(1.0f + e), x.cap);
+    } else {
+        v = s * scale;
+    }
+    return __builtin_fmaf(slope, m, v);
+}
+
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }

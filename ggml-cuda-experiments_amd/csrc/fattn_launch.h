@@ -103,7 +103,13 @@ int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
         }
     }
     if (pl.nld) return FATTN_ERR_INVALID_ARG;
-    auto kern = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI>;
+    void (*kern)(SplitArgs) = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI>;
+    // max_bias / logit_softcap live: the bodies with the score transform, which
+    // exist for 4 waves (the planner sizes such a launch so: size_split)
+    if (pl.a.xf.live) {
+        if constexpr (NWV == 4) kern = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI, true>;
+        else return FATTN_ERR_INVALID_ARG;
+    }
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(NWV * kWave), pl.lds, st, pl.a);
         if constexpr (EPI == 0) {
@@ -224,7 +230,9 @@ int launch_mq(const Plan& pl, hipStream_t st, const Events& ev) {
 
 template <int KT, int D, bool HM>
 int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
-    auto kern = fattn_pf_kernel<KT, D, HM>;
+    // (max_bias / logit_softcap live: the body with the score transform; the
+    // planner keeps such launches off the one-wave-per-SIMD bodies)
+    void (*kern)(SplitArgs) = pl.a.xf.live ? fattn_pf_kernel<KT, D, HM, true> : fattn_pf_kernel<KT, D, HM, false>;
     const void* main_kern = (const void*)kern;
     if constexpr (KT == FATTN_TYPE_F16 && D == 128) {
         if (pl.pf4)

@@ -368,6 +368,23 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
 #pragma unroll
                 for (int r = 0; r < 4; r++) sv[4 * t + r] = st[gi][t][r] * a.scale_log2 + mk[r] * log2e;
             }
+            // max_bias / logit_softcap (wave-uniform, a kernel argument; off:
+            // the line above stands).  A query row's heads share one staged
+            // mask row; the slope is applied per lane, by the q head of the
+            // lane's own packed row, so GQA tiles need no other plan.  (The
+            // slope is derived here, per tile, from iq2 -- live anyway for the
+            // epilogue -- rather than held in NG more registers across the loop.)
+            if (a.xf.live) {
+                const float slope = xf_slope(a.xf, iq2[gi]);
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    const f16x2 m01 = as_h2(mk_cur[gi][t].x), m23 = as_h2(mk_cur[gi][t].y);
+                    const float mk[4] = {(float)m01.x, (float)m01.y, (float)m23.x, (float)m23.y};
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        sv[4 * t + r] = xf_score(a.xf, a.scale, st[gi][t][r], mk[r], slope) * log2e;
+                }
+            }
             float tmax = fmaxf(fmaxf(fmaxf(sv[0], sv[1]), fmaxf(sv[2], sv[3])),
                                fmaxf(fmaxf(sv[4], sv[5]), fmaxf(sv[6], sv[7])));
             tmax = grp4_max(tmax);

@@ -232,7 +232,11 @@ __device__ __forceinline__ const uint8_t* pf_flag_table(const SplitArgs& a, int 
     return a.pf_flags + (int64_t)t * a.n_qt * (a.N / kPfKeys);
 }
 
-template <int KT, int D, bool HM>
+// XF: max_bias / logit_softcap live (SplitArgs::xf; xf_score).  A template
+// parameter here, not the other kernels' wave-uniform branch: a branch would
+// cut the tile body's basic block, and with it the sched_group_barrier
+// interleaving of the scores with the S^T chains.
+template <int KT, int D, bool HM, bool XF = false>
 __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const SplitArgs a) {
     using C = PfCfg<KT, D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -441,6 +445,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     }
     const float log2e = 1.4426950408889634f;
     const float scale = a.scale_log2 / log2e;
+    const float slope = XF ? xf_slope(a.xf, iq2) : 1.0f;  // this lane's row's q head's ALiBi slope
 
 #ifdef FATTN_STAMPS
     // diagnostic build only: shader-clock cycles per phase, summed over tiles
@@ -560,7 +565,18 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
         // scores (natural units) u = scale * s + mask; element j of subtile t is
         // key 32t + 8(j/4) + 4h + (j%4) of this lane's row
         auto scores = [&](const f32x16& stt, int t, float (&ut)[16]) {
-            if constexpr (HM) {
+            if constexpr (XF) {  // always explicit scores, also without a mask (c = log2e below)
+#pragma unroll
+                for (int uu = 0; uu < 4; uu++) {
+                    float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                    if constexpr (HM) {
+                        const f16x2 m01 = as_h2(mk[t][uu].x), m23 = as_h2(mk[t][uu].y);
+                        mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r++) ut[4 * uu + r] = xf_score(a.xf, scale, stt[4 * uu + r], mv[r], slope);
+                }
+            } else if constexpr (HM) {
 #pragma unroll
                 for (int uu = 0; uu < 4; uu++) {
                     const f16x2 m01 = as_h2(mk[t][uu].x), m23 = as_h2(mk[t][uu].y);
@@ -627,7 +643,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
         for (int j = 0; j < 16; j++) tmax = fmaxf(tmax, u1[j]);
         // exponent argument: x * c - m (log2 domain); c = log2e with a mask,
         // scale * log2e without (scale > 0: the planner's condition)
-        const float c = HM ? log2e : a.scale_log2;
+        const float c = (HM || XF) ? log2e : a.scale_log2;
         tmax = xor32_pair(tmax, true) * c;
         // deferred max (cdna_hip_programming.md T13), as in the multi-query kernel
         if (__builtin_amdgcn_ballot_w64(tmax > m_run + kDeferLog2)) {

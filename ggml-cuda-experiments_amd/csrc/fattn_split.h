@@ -108,6 +108,8 @@ struct SplitArgs {
     int xcd_group;      // workgroups in XCD-grouped order (tile_coords; grid size % 8 == 0): batched decode, split kernel
     int part_f16;       // merge_launch 1: each chunk partial stored as O / l in f16 beside its (m, l) in f32
                         // (half the partial bytes; store_part_f16, merge_row_parts_h)
+    ScoreXf xf;         // max_bias / logit_softcap (xf_score, fattn_common.h); xf.live == 0: off.  Last: the
+                        // fields above keep their kernarg offsets
 };
 
 // XOR mask of the 16-B chunk swizzle of an LDS row of `cpr` chunks: the largest
@@ -1328,9 +1330,13 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
 // P.V (the split kernel waits there for the step's V, which it issues last).
 // `first`: o, l are still zero.
 // Used by fattn_split_kernel.
-template <int KT, int VT, int D, bool HM, typename WaitV>
+// XF: max_bias / logit_softcap live -- the scores through xf_score (`slope`:
+// this column's q head's); a template parameter, because the arguments and
+// the slope held across the loop by a wave-uniform branch cost the bodies at
+// their register limit spills (profiles/op_params/registers.txt).
+template <int KT, int VT, int D, bool HM, bool XF, typename WaitV>
 __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mrow,
-                                           int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
+                                           float slope, int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
                                            f32x4 (&o)[D / 16], float (&corr)[(D + QK - 1) / QK], WaitV&& wait_v) {
     using C = SplitCfg<KT, VT, D>;
     constexpr int NB = (D + QK - 1) / QK;  // k-steps of S^T (D = 80: the last one half zero)
@@ -1375,6 +1381,21 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
         } else {
 #pragma unroll
             for (int r = 0; r < 4; r++) sv[4 * t + r] = st[t][r] * a.scale;
+        }
+    }
+    // max_bias / logit_softcap: the scores through xf_score instead (the fmas
+    // above are then dead code)
+    if constexpr (XF) {
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (HM) {
+                const u32x2 mw = *(const u32x2*)(mb + mrow * (kStep * 2) + (16 * t + 4 * g) * 2);
+                const f16x2 m01 = as_h2(mw.x), m23 = as_h2(mw.y);
+                mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) sv[4 * t + r] = xf_score(a.xf, a.scale, st[t][r], mv[r], slope);
         }
     }
     if (nvalid < kStep) {  // wave-uniform: only a slice's partial last step
@@ -1504,7 +1525,9 @@ constexpr int split_waves_per_simd() {
 // issuing waves (tools/hbm_probe: a 35.7 MB read takes 8.3 us from 256 4-wave
 // workgroups, 6.4 us from 16 waves per CU) and let the SIMDs interleave the
 // steps' dependent LDS -> VALU -> MFMA chains.
-template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
+// XF (split_step): instantiated for NWV = 4 only; the planner sizes a launch
+// with max_bias / logit_softcap live for 4 waves (size_split).
+template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false>
 __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256) ? 2 : 4) void fattn_split_kernel(
     const SplitArgs a) {
     using C = SplitCfg<KT, VT, D>;
@@ -1546,6 +1569,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     const int iq2 = ik2 * a.rk2 + mh;
     const bool row_ok = (m < a.QPT * a.R) && (iq1 < a.NQ) && (mh < a.rk2);
     const int mrow = a.m_hp ? m : (mq < a.QPT ? mq : 0);  // this column's staged mask row (split_step)
+    const float slope = XF ? xf_slope(a.xf, iq2) : 1.0f;  // this column's q head's ALiBi slope
 
     // ---- this wave's KV slice
     const int wl = a.chunk_len / NWV;
@@ -1695,7 +1719,7 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;  // hides "first step" from loop peeling (a second copy of the body)
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM>(a, wbuf + cur * C::stepBytes, qop, mrow, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
+        split_step<KT, VT, D, HM, XF>(a, wbuf + cur * C::stepBytes, qop, mrow, slope, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
                                   m_run, l_run, o, corr, [&] { wait_steps<NI>(ahead); });
         if (nsteps <= 4 && s < 2) FATTN_SSTAMP(6 + 2 * s);  // (stamps build: step s computed)
 
@@ -1884,7 +1908,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM>(a, wbuf + s * C::stepBytes, qop, mrow, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
+        split_step<KT, VT, D, HM, false>(a, wbuf + s * C::stepBytes, qop, mrow, 1.0f, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
                                   m_run, l_run, o, corr, [&] {
                                       if (s == 0) wait_vmcnt_c<0>();
                                       else wait_lds_flag(f + 1);

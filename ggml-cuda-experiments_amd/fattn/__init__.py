@@ -82,7 +82,10 @@ class FattnTensor(C.Structure):
 class FattnParams(C.Structure):
     _fields_ = [("q", FattnTensor), ("k", FattnTensor), ("v", FattnTensor), ("mask", FattnTensor),
                 ("dst", C.c_void_p), ("scale", C.c_float), ("kv_chunk", C.c_int32),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                # ggml's op_params[1], [2] and the global head numbering of the ALiBi slopes (zeros: off)
+                ("max_bias", C.c_float), ("logit_softcap", C.c_float),
+                ("n_head_total", C.c_int32), ("head_first", C.c_int32)]
 
 
 _lib = None
@@ -211,7 +214,12 @@ def _stream(stream) -> Optional[int]:
 
 
 def ext_params(q: View, k: View, v: View, mask: Optional[View], dst_ptr: int, scale: float,
-               workspace_ptr: int = 0, workspace_bytes: int = 0, kv_chunk: int = 0) -> FattnParams:
+               workspace_ptr: int = 0, workspace_bytes: int = 0, kv_chunk: int = 0, *, max_bias: float = 0.0,
+               logit_softcap: float = 0.0, n_head_total: int = 0, head_first: int = 0) -> FattnParams:
+    """max_bias / logit_softcap: ggml's op_params[1] / [2] (ALiBi slopes on the
+    mask, cap * tanh(score / cap)); n_head_total / head_first: the unsharded
+    head count and the global index of q head 0, for the slopes of a
+    head-sharded launch (shard.HeadShard.slope_args()).  Zeros: off."""
     p = FattnParams()
     p.q, p.k, p.v = q.c(), k.c(), v.c()
     if mask is not None:
@@ -221,6 +229,10 @@ def ext_params(q: View, k: View, v: View, mask: Optional[View], dst_ptr: int, sc
     p.kv_chunk = int(kv_chunk)
     p.workspace = workspace_ptr or None
     p.workspace_bytes = int(workspace_bytes)
+    p.max_bias = float(max_bias)
+    p.logit_softcap = float(logit_softcap)
+    p.n_head_total = int(n_head_total)
+    p.head_first = int(head_first)
     return p
 
 
@@ -293,9 +305,11 @@ def mask_view(mask) -> View:
 class Attention:
     """Reusable FLASH_ATTN_EXT call: builds the params once, owns its workspace."""
 
-    def __init__(self, q: View, k: View, v: View, mask: Optional[View], dst, scale: float, kv_chunk: int = 0):
+    def __init__(self, q: View, k: View, v: View, mask: Optional[View], dst, scale: float, kv_chunk: int = 0, *,
+                 max_bias: float = 0.0, logit_softcap: float = 0.0, n_head_total: int = 0, head_first: int = 0):
         import torch
-        self.p = ext_params(q, k, v, mask, _tptr(dst), scale, 0, 0, kv_chunk)
+        self.p = ext_params(q, k, v, mask, _tptr(dst), scale, 0, 0, kv_chunk, max_bias=max_bias,
+                            logit_softcap=logit_softcap, n_head_total=n_head_total, head_first=head_first)
         ws = workspace_size(self.p)
         # (zeroing is optional: each launch epoch-stamps the arrival words at its front)
         self.workspace = torch.zeros(max(ws, 16), dtype=torch.uint8, device=dst.device)

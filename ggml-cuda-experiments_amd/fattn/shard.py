@@ -23,6 +23,7 @@ class HeadShard:
     kv1: int   # one past the last kv-head owned
     h0: int    # first q-head owned (= kv0 * r)
     h1: int
+    H: int = 0  # q heads of the unsharded problem (0: unknown, a hand-built shard)
 
     @property
     def n_kv(self) -> int:
@@ -31,6 +32,16 @@ class HeadShard:
     @property
     def n_heads(self) -> int:
         return self.h1 - self.h0
+
+    def slope_args(self) -> dict:
+        """What the rank's launch needs for the GLOBAL ALiBi slopes (max_bias):
+        its slice's q head 0 is head h0 of H, so
+        `fattn.ext_params(..., max_bias=b, **sh.slope_args())`.  Launched with
+        the defaults instead, a slice would take the slopes of heads
+        0 .. n_heads-1 of an n_heads-head model -- silently wrong."""
+        if self.H <= 0:
+            raise ValueError("HeadShard.H (the unsharded head count) is not set")
+        return {"n_head_total": self.H, "head_first": self.h0}
 
 
 def shard_heads(H: int, Hkv: int, world: int, rank: int) -> HeadShard:
@@ -45,7 +56,7 @@ def shard_heads(H: int, Hkv: int, world: int, rank: int) -> HeadShard:
     r = H // Hkv
     per = Hkv // world
     kv0 = rank * per
-    return HeadShard(rank, world, kv0, kv0 + per, kv0 * r, (kv0 + per) * r)
+    return HeadShard(rank, world, kv0, kv0 + per, kv0 * r, (kv0 + per) * r, H)
 
 
 def narrow(view, dim: int, start: int, count: int):
@@ -64,7 +75,8 @@ def head_views(q, k, v, sh: HeadShard):
     """The rank's FLASH_ATTN_EXT sub-problem, zero-copy: q heads [h0, h1) and
     kv heads [kv0, kv1) (ggml dim 2 of q / k / v).  The mask is shared by all
     heads (a row per query) and the rank's dst is its own contiguous
-    [S][n_q][h1-h0][D]; the GQA map ik2 = iq2 / r (src/flash-llama.h:128-140)
+    [S][n_q][h1-h0][D] (with max_bias the slopes are per GLOBAL head: pass
+    sh.slope_args() to ext_params / Attention); the GQA map ik2 = iq2 / r (src/flash-llama.h:128-140)
     holds inside the slice because h0 = kv0 * r."""
     return narrow(q, 2, sh.h0, sh.n_heads), narrow(k, 2, sh.kv0, sh.n_kv), narrow(v, 2, sh.kv0, sh.n_kv)
 

@@ -34,6 +34,10 @@
 //                        32 heads, N 4096), 4 (Q4_0, 32 q / 8 kv heads, N 8192), 5 (Q8_0,
 //                        n_q 64, N 4096); "prefill" (Q8_0, n_q = N = 4096, 32 heads,
 //                        zero mask: SURVEY 8(d)'s MFMA shape); later flags override
+//   --max-bias F         ggml's max_bias (ALiBi): head h adds slope(h) * mask to its scores
+//   --softcap F          ggml's logit_softcap: cap * tanh(score / cap) before the mask
+//                        (both default 0 = off; either takes the fattn_params call, with
+//                        n_head_total / head_first set per device under --ngpu)
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -117,10 +121,17 @@ void random_fill(std::vector<float>& a) {
 // q [NQ][H][D], k / v [Hkv][N][D], mask [NQ][N], out [NQ][H][D]; only the rows
 // listed (all of them for the reference's n_q = 1), heads over threads (the
 // per-head arithmetic and its order are the reference's, so the bits are too)
+// max_bias / softcap: ggml's FLASH_ATTN_EXT scalars (include/fattn.h), by its
+// host formulas -- score = cap * tanhf(acc * (scale / cap)) (softcap > 0) plus
+// slope(h) * mask; with both 0 the statements below are the reference's
 void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, const std::vector<float>& v,
                    const std::vector<float>& mask, std::vector<float>& out, int N, int D, int H, int Hkv, float scale,
-                   const std::vector<int>& rows, int threads = 1) {
+                   const std::vector<int>& rows, int threads = 1, float max_bias = 0.0f, float softcap = 0.0f) {
     const int r = H / Hkv;
+    int n2 = 1;
+    while (n2 * 2 <= H) n2 *= 2;
+    const float m0 = powf(2.0f, -max_bias / (float)n2), m1 = powf(2.0f, -(max_bias / 2.0f) / (float)n2);
+    const bool xf = max_bias > 0.0f || softcap > 0.0f;
     std::vector<float> qh(q.size()), kh(k.size()), vh(v.size());
     for (size_t i = 0; i < q.size(); i++) qh[i] = rh(q[i]);
     for (size_t i = 0; i < k.size(); i++) kh[i] = rh(k[i]);
@@ -139,6 +150,11 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
                     acc = acc + p;
                 }
                 s[c] = acc * scale + mrow[c];
+                if (xf) {
+                    const float slope = max_bias > 0.0f ? (h < n2 ? powf(m0, (float)(h + 1)) : powf(m1, (float)(2 * (h - n2) + 1))) : 1.0f;
+                    const float x = softcap > 0.0f ? softcap * tanhf(acc * (scale / softcap)) : acc * scale;
+                    s[c] = x + slope * mrow[c];
+                }
             }
             float M = -INFINITY, S = 0.0f;
             for (int i = 0; i < N; i++) {
@@ -201,7 +217,7 @@ int main(int argc, const char* argv[]) {
     bool parallel_kv = true, cpu_only = false;
     std::string mask_kind = "random";
     const char* dump = nullptr;
-    float tol = 1e-3f;
+    float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -225,6 +241,8 @@ int main(int argc, const char* argv[]) {
         else if (a == "--n-q") n_q = atoi(next());
         else if (a == "--check-rows") check_rows = std::max(1, atoi(next()));
         else if (a == "--ngpu") ngpu = atoi(next());
+        else if (a == "--max-bias") max_bias = (float)atof(next());
+        else if (a == "--softcap") softcap = (float)atof(next());
         else if (a == "--mask") {
             mask_kind = next();
             if (mask_kind != "random" && mask_kind != "zero" && mask_kind != "none") {
@@ -261,6 +279,8 @@ int main(int argc, const char* argv[]) {
         printf("invalid num_warps, should be 2, 4, 8\n");  // kernel_test.h:176-178 (informational)
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
+    const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
+    if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)
 
     const int D = head_dim, H = num_heads, Hkv = num_kv_heads, N = kv_size, NQ = n_q;
     const float scale = 1.0f / sqrtf((float)D);
@@ -294,7 +314,7 @@ int main(int argc, const char* argv[]) {
 
     if (cpu_only) {  // BASELINE config 1: kernel_test.h:50-66 on the host, nothing else
         std::vector<float> out((size_t)D * H * NQ);
-        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads);
+        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads, max_bias, softcap);
         print_array("Reference", out.data(), std::min(16, D * H));
         if (dump) {
             FILE* f = fopen(dump, "wb");
@@ -374,7 +394,7 @@ int main(int argc, const char* argv[]) {
 
     // CPU reference (kernel_test.h:50-66) on the checked rows
     std::vector<float> qkv((size_t)D * H * NQ, 0.0f), qkv_gpu((size_t)D * H * NQ);
-    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads);
+    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads, max_bias, softcap);
     print_array("Reference", qkv.data(), 16);
 
     // ---- per device: its head shard (kv heads [g Hkv/G, (g+1) Hkv/G) and their
@@ -430,6 +450,10 @@ int main(int argc, const char* argv[]) {
                         {2, (int64_t)Np * 2, (int64_t)Np * 2 * mask_rows, (int64_t)Np * 2 * mask_rows}};
         d.p.dst = d.out;
         d.p.scale = scale;
+        d.p.max_bias = max_bias;
+        d.p.logit_softcap = softcap;
+        d.p.n_head_total = H;     // the slopes are the unsharded model's: this device's q head 0 is head g * Hl
+        d.p.head_first = g * Hl;
         d.ws_bytes = parallel_kv ? fattn_row_workspace_size(D, N, H) : fattn_workspace_size(&d.p);
         d.ws_bytes = std::max<size_t>(d.ws_bytes, 16);
         HIP_CHECK(hipMalloc(&d.ws, d.ws_bytes));
@@ -462,7 +486,7 @@ int main(int argc, const char* argv[]) {
             int rc;
             if (parallel_kv)
                 rc = fattn_row(d.q, d.k, d.v, d.mask, d.ws, d.ws_bytes, d.out, D, N, H, scale, D * N, r_kv_heads, d.st);
-            else if (NQ == 1 && G == 1 && has_mask)
+            else if (NQ == 1 && G == 1 && has_mask && !op_xf)
                 rc = fattn_ext_f16_launch(d.q, d.k, d.v, d.mask, d.out, scale,
                                           D, 1, H, 1,
                                           D, N, Hkv, 1,

@@ -111,7 +111,30 @@ typedef struct fattn_tensor {
  *   H % Hkv == 0 (GQA broadcast), S % Skv == 0.
  *   softmax(scale * q.k^T + mask) . v per (seq, head, query row).  A row whose
  *   mask is -inf everywhere yields NaN, as the reference's softmax does
- *   (src/utils.h:30-49). */
+ *   (src/utils.h:30-49).
+ *   max_bias, logit_softcap: the other two floats of ggml's op_params
+ *        (op_params[1], op_params[2]), with ggml's meaning.  For q head h
+ *        (global index, below), s = q.k and mask value m (0 without a mask):
+ *            x = s * scale                        logit_softcap == 0
+ *            x = cap * tanh(s * (scale / cap))    logit_softcap  > 0 (cap = logit_softcap)
+ *            score = x + slope(h) * m
+ *        slope(h) = 1 when max_bias == 0; else, with n = n_head_total and
+ *        n2 = 2^floor(log2 n), 2^(-(max_bias / n2) * (h + 1)) for h < n2 and
+ *        2^(-(max_bias / 2 / n2) * (2 * (h - n2) + 1)) past it -- ALiBi from
+ *        one shared distance mask, without H pre-multiplied head planes (a head
+ *        plane, ne[2] > 1, is still scaled by the slope of the query's head).
+ *        max_bias without a mask changes nothing: same plan, same output bits.
+ *        The slope is > 0, so -inf stays -inf.  h = head_first + iq2:
+ *        a head-sharded launch passes the global index of its q head 0 and the
+ *        unsharded head count n_head_total (0 = q.ne[2]); head_first >= 0 and
+ *        head_first + H <= n_head_total.  A negative, NaN or infinite max_bias
+ *        or logit_softcap is FATTN_ERR_INVALID_ARG.  tanh is built from
+ *        v_exp_f32 / v_rcp_f32 (1 - 2 / (1 + 2^(2 log2e t))): exact saturation,
+ *        absolute error about 1e-7, so about cap * 1e-7 in a logit.  With either
+ *        live, prefill shapes run fattn_pf_kernel rather than the one-wave-
+ *        per-SIMD bodies; the multi-query kernel applies the slope per lane
+ *        (GQA tiles keep their plan).  The struct grew by these four fields:
+ *        zero-initialise it (memset / = {0}); zeros are the earlier behaviour. */
 typedef struct fattn_params {
     fattn_tensor q, k, v, mask;
     float* dst;
@@ -128,6 +151,11 @@ typedef struct fattn_params {
                               between launches.  Launches that share one workspace must be
                               ordered on one stream */
     size_t workspace_bytes;
+    /* ggml's other two op_params floats (see above); all four zero = softmax(scale * q.k^T + mask) */
+    float max_bias;        /* ALiBi; 0 = off */
+    float logit_softcap;   /* 0 = off */
+    int32_t n_head_total;  /* heads of the unsharded model, for the slopes; 0 = q.ne[2] */
+    int32_t head_first;    /* global index of q head 0 (head-sharded launches); 0 otherwise */
 } fattn_params;
 
 size_t fattn_workspace_size(const fattn_params* p);

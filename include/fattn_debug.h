@@ -53,7 +53,8 @@ enum {
                                        An explicit value (64 included) also lifts the default's rule that every
                                        KV chunk hold two 128-key tiles */
     FATTN_OPT_SPLIT_WAVES = 19,     /* split kernel waves per workgroup: 0 = auto, 4, 8 or 16 (16-B row path;
-                                       16 needs the Q8_0/Q4_0 register budget, else clamped to 8) */
+                                       16 needs the Q8_0/Q4_0 register budget, else clamped to 8; a launch with
+                                       max_bias / logit_softcap live takes 4 whatever this says) */
     FATTN_OPT_SPLIT_SKIP = 20       /* split kernel, masked: 0 = steps whose mask is -inf for every key and row
                                        of the tile are neither loaded nor computed (default; the mask words are
                                        read beside Q), 1 = every step loaded and computed */,
@@ -117,7 +118,10 @@ enum {
 int fattn_set_option(int option, int value);
 
 /* Diagnostic: the kernel(s) fattn_ext would launch for `p` and the plan's
- * grid / LDS / chunk / workspace, as text (NUL-terminated, at most cap bytes).
+ * grid / LDS / chunk / workspace, as text (NUL-terminated, at most cap bytes);
+ * then " mask planes (ne2,ne3)" when a plane count exceeds 1, " softcap <cap>"
+ * when logit_softcap is live and " alibi <max_bias>" when max_bias is (it is
+ * not without a mask) -- nothing when they are off.
  * Returns FATTN_OK or the error fattn_ext would return. */
 int fattn_describe(const fattn_params* p, char* out, size_t cap);
 
