@@ -225,7 +225,7 @@ __device__ __forceinline__ void reg_fence(T& v) {
 //     x = cap * tanh(s * (scale / cap))    (cap > 0)
 //     u = x + slope(h) * mask
 // `live` is a kernel argument (wave-uniform): with both off the kernels keep
-// their one fma and branch around this code.  The host (make_plan) fills the
+// their one fma and branch around this code.  The host (fill_args) fills the
 // struct; live bit 1 is set only with a mask (max_bias without one changes
 // nothing, as in ggml).
 struct ScoreXf {

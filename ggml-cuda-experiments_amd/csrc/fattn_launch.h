@@ -1,5 +1,5 @@
 // fattn_launch.h -- the launch plan and the kernel launchers, shared by the
-// planner / C ABI (fattn_api.hip) and the per-head-dim translation units
+// planner (fattn_plan.h), the C ABI (fattn_api.hip) and the per-head-dim translation units
 // (fattn_launch_d*.hip: each instantiates launch_types<D>, so the kernels of
 // the head dims compile in parallel).
 #pragma once
@@ -22,35 +22,40 @@ namespace fattn {
 
 constexpr int kMaxDevices = 64;
 
+// the kernel a plan launches (one of them: the planner's choose_kernel and sizing)
+enum class Kernel {
+    Split,    // split-KV kernel (fattn_split.h): every wave issues its own steps
+    SplitLd,  // ... with kSplitLoaders loader waves beside the compute waves (fattn_split_ld_kernel)
+    Mq,       // multi-query kernel (fattn_mq.h)
+    Pf,       // prefill kernel, the 8-wave body (fattn_pf.h)
+    Pf4,      // ... its one-wave-per-SIMD body (fattn_pf4.h; f16 rows, D = 128)
+    Bd,       // batched-decode kernel, all waves alike (fattn_bd.h)
+    Bdp,      // ... in its compute / build-role form (fattn_bdp.h; Q8_0 / Q4_0)
+};
+
 struct Plan {
-    SplitArgs a;
-    int kt, vt;  // vt may be VT_F16T
-    int D;
-    int gran;
+    SplitArgs a = {};
+    Kernel kernel = Kernel::Split;
+    int kt = 0, vt = 0;  // vt may be VT_F16T
+    int D = 0;
+    int gran = 0;
     dim3 grid;
-    int lds;
-    size_t ws_bytes, cnt_bytes, ml_bytes;
-    int cus;  // compute units of the device the plan is for
-    int nwv;  // split kernel: waves per workgroup (4, 8, 16)
-    // split kernel: loader waves beside the nwv compute waves (fattn_split_ld_kernel), 0 = none
-    int nld = 0;
+    int lds = 0;
+    size_t ws_bytes = 0, cnt_bytes = 0, ml_bytes = 0;
+    int cus = 0;  // compute units of the device the plan is for
+    int nwv = 0;  // split kernel: waves per workgroup (4, 8, 16)
+    int nw = 0;   // mq kernel: waves per workgroup: 4 (16 rows each) or 8 (32 rows each)
     bool merge_plain = false;  // second-launch merges (split, batched decode): plain loads (FATTN_OPT_MERGE_PLAIN)
-    bool mq;  // multi-query kernel (fattn_mq.h)
-    bool pf;  // prefill kernel (fattn_pf.h)
-    bool bd;  // batched-decode kernel (fattn_bd.h)
-    bool bdp; // ... in its compute / build-role form (fattn_bdp.h; Q8_0 / Q4_0)
     bool pf_flags = false;  // masked prefill: live-block flags pre-pass (tile-range skipping)
+    int pf4_sched = 0;      // Kernel::Pf4: its schedule (fattn_pf4_kernel's SCHED)
     // prefill over Q8_0 / Q4_0: the rows staged to f16 in the workspace first
     // (kv_stage_f16_kernel), then the f16 prefill kernel (kt = vt = F16 then)
-    bool pf4 = false;       // the prefill's one-wave-per-SIMD body (fattn_pf4.h; f16 rows, D = 128)
-    int pf4_sched = 0;      // ... its schedule (fattn_pf4_kernel's SCHED)
     bool pf_stage = false;
     int stage_kt = 0;                                  // the cache's type
     const uint8_t *stage_k = nullptr, *stage_v = nullptr;  // the cache's K / V
     int64_t stage_k_nb2 = 0, stage_k_nb3 = 0, stage_v_nb2 = 0, stage_v_nb3 = 0;
     int stage_hkv = 0, stage_skv = 0;
     size_t stage_off = 0, stage_bytes = 0;             // per K (or V): Skv * Hkv * N * D * 2
-    int nw;   // mq kernel: waves per workgroup: 4 (16 rows each) or 8 (32 rows each)
 };
 
 struct Events {
@@ -92,17 +97,59 @@ int launch_kernel(const void* kern, const Plan& pl, hipStream_t st, const Events
     return FATTN_OK;
 }
 
+// The second-launch merge kernels of the three split-KV kernels, as template
+// arguments of launch_chunk_merge.  The multi-query merge has no plain-load form.
+struct SplitMerge {
+    static constexpr bool has_plain = true;
+    template <int D, int KIT, bool PLAIN, bool F16>
+    static constexpr auto kernel() { return fattn_merge_kernel<D, KIT, PLAIN, F16>; }
+};
+struct BdMerge {
+    static constexpr bool has_plain = true;
+    template <int D, int KIT, bool PLAIN, bool F16>
+    static constexpr auto kernel() { return fattn_bd_merge_kernel<D, KIT, PLAIN, F16>; }
+};
+template <int SUBS>  // 16-row subtiles per tile
+struct MqMerge {
+    static constexpr bool has_plain = false;
+    template <int D, int KIT, bool PLAIN, bool F16>
+    static constexpr auto kernel() { return fattn_mq_merge_kernel<D, KIT, SUBS, F16>; }
+};
+
+// Merge the chunk partials in a second launch, one wave per packed row, with
+// as few load slots per lane (KIT) as the chunk count allows (the slots past
+// it still cost issue cycles); f16 partials (16-B loads of 8 dims, merge_ppr_h
+// parts per lane row; not at D = 64), else sc1 or plain loads of f32 ones.
+template <typename Family, int D>
+void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
+    auto pick = [&](int parts_per_row, auto plain, auto f16) {
+        constexpr bool PLAIN = decltype(plain)::value, F16 = decltype(f16)::value;
+        const int need = (pl.a.n_chunks + parts_per_row - 1) / parts_per_row;
+        if (need <= 2) hipLaunchKernelGGL((Family::template kernel<D, 2, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
+        else if (need <= 4) hipLaunchKernelGGL((Family::template kernel<D, 4, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
+        else if (need <= 8) hipLaunchKernelGGL((Family::template kernel<D, 8, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
+        else hipLaunchKernelGGL((Family::template kernel<D, 16, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
+    };
+    if constexpr (D != 64) {
+        if (pl.a.part_f16) return pick(merge_ppr_h<D>(), std::false_type(), std::true_type());
+    }
+    if constexpr (Family::has_plain) {
+        if (pl.merge_plain) return pick(merge_ppr<D>(), std::true_type(), std::false_type());
+    }
+    pick(merge_ppr<D>(), std::false_type(), std::false_type());
+}
+
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
 int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
-    if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && (D == 64 || D == 128)) {
-        if (pl.nld == kSplitLoaders) {
+    if (pl.kernel == Kernel::SplitLd) {
+        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && (D == 64 || D == 128)) {
             auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders>;
             return launch_kernel((const void*)lk, pl, st, ev, [&] {
                 hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, pl.a);
             });
         }
+        return FATTN_ERR_INVALID_ARG;
     }
-    if (pl.nld) return FATTN_ERR_INVALID_ARG;
     void (*kern)(SplitArgs) = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI>;
     // max_bias / logit_softcap live: the bodies with the score transform, which
     // exist for 4 waves (the planner sizes such a launch so: size_split)
@@ -113,35 +160,15 @@ int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(NWV * kWave), pl.lds, st, pl.a);
         if constexpr (EPI == 0) {
-            // multi-row tiles: the chunk partials merge in a second launch, with
-            // as few load slots per lane as the chunk count allows (the slots
-            // past it still cost issue cycles) -- unless they merge in-kernel (2)
+            // multi-row tiles: the chunk partials merge in a second launch --
+            // unless they merge in-kernel (2)
             if (pl.a.merge_launch == 1) {
                 // one wave per packed row a tile can hold: R heads x the query
                 // rows it really has (config 4's 4-row GQA tiles, QPT 4 but one
                 // query row: one workgroup per tile, not four)
                 const int qrows = pl.a.QPT < pl.a.NQ ? pl.a.QPT : pl.a.NQ;
                 const int rows = qrows * pl.a.R < kRows ? qrows * pl.a.R : kRows;
-                const dim3 g((unsigned)((rows + 3) / 4), pl.grid.y, pl.grid.z);
-                const int need = (pl.a.n_chunks + merge_ppr<D>() - 1) / merge_ppr<D>();
-                auto go = [&](auto kit, auto plain, auto f16) {
-                    hipLaunchKernelGGL((fattn_merge_kernel<D, decltype(kit)::value, decltype(plain)::value, decltype(f16)::value>),
-                                       g, dim3(256), 0, st, pl.a);
-                };
-                auto pick = [&](int nd, auto plain, auto f16) {
-                    if (nd <= 2) go(std::integral_constant<int, 2>(), plain, f16);
-                    else if (nd <= 4) go(std::integral_constant<int, 4>(), plain, f16);
-                    else if (nd <= 8) go(std::integral_constant<int, 8>(), plain, f16);
-                    else go(std::integral_constant<int, 16>(), plain, f16);
-                };
-                if constexpr (D != 64) {
-                    if (pl.a.part_f16) {  // (f16 partials: 16-B loads of 8 dims, merge_ppr_h parts per lane row)
-                        pick((pl.a.n_chunks + merge_ppr_h<D>() - 1) / merge_ppr_h<D>(), std::false_type(), std::true_type());
-                        return;
-                    }
-                }
-                if (pl.merge_plain) pick(need, std::true_type(), std::false_type());
-                else pick(need, std::false_type(), std::false_type());
+                launch_chunk_merge<SplitMerge, D>(dim3((unsigned)((rows + 3) / 4), pl.grid.y, pl.grid.z), pl, st);
             }
         }
     });
@@ -196,25 +223,7 @@ int launch_mq_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             // the chunk partials of every 16-row subtile (4 per 64-row tile,
             // 16 per 256-row tile) merge in a second launch
             constexpr int SUBS = NW == 8 ? 16 : 4;
-            const dim3 g(kRows / 4, pl.grid.y * SUBS, pl.grid.z);
-            const int need = (pl.a.n_chunks + merge_ppr<D>() - 1) / merge_ppr<D>();
-            auto go = [&](auto kit, auto f16) {
-                hipLaunchKernelGGL((fattn_mq_merge_kernel<D, decltype(kit)::value, SUBS, decltype(f16)::value>), g,
-                                   dim3(256), 0, st, pl.a);
-            };
-            auto pick = [&](int nd, auto f16) {
-                if (nd <= 2) go(std::integral_constant<int, 2>(), f16);
-                else if (nd <= 4) go(std::integral_constant<int, 4>(), f16);
-                else if (nd <= 8) go(std::integral_constant<int, 8>(), f16);
-                else go(std::integral_constant<int, 16>(), f16);
-            };
-            if constexpr (D != 64) {
-                if (pl.a.part_f16) {
-                    pick((pl.a.n_chunks + merge_ppr_h<D>() - 1) / merge_ppr_h<D>(), std::true_type());
-                    return;
-                }
-            }
-            pick(need, std::false_type());
+            launch_chunk_merge<MqMerge<SUBS>, D>(dim3(kRows / 4, pl.grid.y * SUBS, pl.grid.z), pl, st);
         }
     });
 }
@@ -233,14 +242,16 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     // (max_bias / logit_softcap live: the body with the score transform; the
     // planner keeps such launches off the one-wave-per-SIMD bodies)
     void (*kern)(SplitArgs) = pl.a.xf.live ? fattn_pf_kernel<KT, D, HM, true> : fattn_pf_kernel<KT, D, HM, false>;
-    const void* main_kern = (const void*)kern;
+    int waves = kPfWaves;
     if constexpr (KT == FATTN_TYPE_F16 && D == 128) {
-        if (pl.pf4)
-            main_kern = pl.pf4_sched == 4   ? (const void*)fattn_pf4_kernel<D, HM, 4>
-                        : pl.pf4_sched == 3 ? (const void*)fattn_pf4_kernel<D, HM, 3>
-                                            : (const void*)fattn_pf4_kernel<D, HM, 2>;
+        if (pl.kernel == Kernel::Pf4) {
+            if (pl.pf4_sched == 4) kern = fattn_pf4_kernel<D, HM, 4>;
+            else if (pl.pf4_sched == 3) kern = fattn_pf4_kernel<D, HM, 3>;
+            else kern = fattn_pf4_kernel<D, HM, 2>;
+            waves = kPf4Waves;
+        }
     }
-    return launch_kernel(main_kern, pl, st, ev, [&] {
+    return launch_kernel((const void*)kern, pl, st, ev, [&] {
         // the pre-pass, one launch: the quantised cache's rows -> f16 rows in the
         // workspace (K and V), and the mask's live / +-0 block flags
         bool staged = false;
@@ -265,56 +276,26 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             else if (pl.stage_kt == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q8_0>, g, dim3(256), 0, st, pa);
             else hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q4_0>, g, dim3(256), 0, st, pa);
         }
-        if constexpr (KT == FATTN_TYPE_F16 && D == 128) {
-            if (pl.pf4) {
-                if (pl.pf4_sched == 4)
-                    hipLaunchKernelGGL((fattn_pf4_kernel<D, HM, 4>), pl.grid, dim3(kPf4Waves * kWave), pl.lds, st, pl.a);
-                else if (pl.pf4_sched == 3)
-                    hipLaunchKernelGGL((fattn_pf4_kernel<D, HM, 3>), pl.grid, dim3(kPf4Waves * kWave), pl.lds, st, pl.a);
-                else
-                    hipLaunchKernelGGL((fattn_pf4_kernel<D, HM, 2>), pl.grid, dim3(kPf4Waves * kWave), pl.lds, st, pl.a);
-                return;
-            }
-        }
-        hipLaunchKernelGGL(kern, pl.grid, dim3(kPfWaves * kWave), pl.lds, st, pl.a);
+        hipLaunchKernelGGL(kern, pl.grid, dim3(waves * kWave), pl.lds, st, pl.a);
     });
 }
 
-// D = 128: the all-waves form, or the role form for quantised K/V (pl.bdp);
-// D = 64 / 96: the role form for quantised K/V (the planner sets pl.bdp), the
-// all-waves form's f16 image ring for f16
+// D = 128: the all-waves form, or the role form for quantised K/V (Kernel::Bdp);
+// D = 64 / 96: the role form only for quantised K/V, the all-waves form's f16
+// image ring for f16
 template <int KT, int D, bool HM>
 int launch_bd_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     void (*kern)(SplitArgs) = nullptr;
-    if constexpr (D == 128 || KT == FATTN_TYPE_F16) kern = fattn_bd_kernel<KT, D, HM>;
-    if constexpr (KT != FATTN_TYPE_F16) {
-        if (pl.bdp) kern = fattn_bdp_kernel<KT, D, HM>;
+    if constexpr (D == 128 || KT == FATTN_TYPE_F16) {
+        if (pl.kernel == Kernel::Bd) kern = fattn_bd_kernel<KT, D, HM>;
     }
-    if (kern == nullptr || (D != 128 && KT != FATTN_TYPE_F16 && !pl.bdp)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if constexpr (KT != FATTN_TYPE_F16) {
+        if (pl.kernel == Kernel::Bdp) kern = fattn_bdp_kernel<KT, D, HM>;
+    }
+    if (kern == nullptr) return FATTN_ERR_UNSUPPORTED_TYPE;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(kBdWaves * kWave), pl.lds, st, pl.a);
-        if (pl.a.merge_launch == 1) {
-            const dim3 g(kBdRows / 4, pl.grid.y, pl.grid.z);
-            const int need = (pl.a.n_chunks + merge_ppr<D>() - 1) / merge_ppr<D>();
-            auto go = [&](auto kit, auto plain, auto f16) {
-                hipLaunchKernelGGL((fattn_bd_merge_kernel<D, decltype(kit)::value, decltype(plain)::value, decltype(f16)::value>),
-                                   g, dim3(256), 0, st, pl.a);
-            };
-            auto pick = [&](int nd, auto plain, auto f16) {
-                if (nd <= 2) go(std::integral_constant<int, 2>(), plain, f16);
-                else if (nd <= 4) go(std::integral_constant<int, 4>(), plain, f16);
-                else if (nd <= 8) go(std::integral_constant<int, 8>(), plain, f16);
-                else go(std::integral_constant<int, 16>(), plain, f16);
-            };
-            if constexpr (D != 64) {
-                if (pl.a.part_f16) {  // (f16 partials: 16-B loads of 8 dims, merge_ppr_h parts per lane row)
-                    pick((pl.a.n_chunks + merge_ppr_h<D>() - 1) / merge_ppr_h<D>(), std::false_type(), std::true_type());
-                    return;
-                }
-            }
-            if (pl.merge_plain) pick(need, std::true_type(), std::false_type());
-            else pick(need, std::false_type(), std::false_type());
-        }
+        if (pl.a.merge_launch == 1) launch_chunk_merge<BdMerge, D>(dim3(kBdRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
 }
 
@@ -349,43 +330,47 @@ extern template int launch_mixed<256>(const Plan&, hipStream_t, const Events&);
 // fattn_launch_d<D>.hip)
 template <int D>
 int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
-    if constexpr (D == 64 || D == 128 || D == 256) {
-        if (pl.kt != pl.vt && pl.vt != VT_F16T) return launch_mixed<D>(pl, st, ev);
-    }
-    if constexpr (D == 64 || D == 80 || D == 96 || D == 128) {
-        if (pl.pf) {
-            if (pl.kt == FATTN_TYPE_F16 && pl.vt == FATTN_TYPE_F16) return launch_pf<FATTN_TYPE_F16, D>(pl, st, ev);
-            if constexpr (D != 80) {  // (80 is not a whole number of ggml blocks)
-                if (pl.kt == FATTN_TYPE_Q8_0 && pl.vt == FATTN_TYPE_Q8_0) return launch_pf<FATTN_TYPE_Q8_0, D>(pl, st, ev);
-                if (pl.kt == FATTN_TYPE_Q4_0 && pl.vt == FATTN_TYPE_Q4_0) return launch_pf<FATTN_TYPE_Q4_0, D>(pl, st, ev);
+    constexpr int F16 = FATTN_TYPE_F16, Q8 = FATTN_TYPE_Q8_0, Q4 = FATTN_TYPE_Q4_0;
+    const bool f16 = pl.kt == F16 && pl.vt == F16, q8 = pl.kt == Q8 && pl.vt == Q8, q4 = pl.kt == Q4 && pl.vt == Q4;
+    // a (kernel, type, D) the library has no instantiation of falls through to the error below
+    switch (pl.kernel) {
+        case Kernel::Pf:
+        case Kernel::Pf4:
+            if constexpr (D == 64 || D == 80 || D == 96 || D == 128) {
+                if (f16) return launch_pf<F16, D>(pl, st, ev);
+                if constexpr (D != 80) {  // (80 is not a whole number of ggml blocks)
+                    if (q8) return launch_pf<Q8, D>(pl, st, ev);
+                    if (q4) return launch_pf<Q4, D>(pl, st, ev);
+                }
             }
-            return FATTN_ERR_UNSUPPORTED_TYPE;
-        }
+            break;
+        case Kernel::Bd:
+        case Kernel::Bdp:
+            if constexpr (D == 64 || D == 96 || D == 128) {
+                if (q8) return launch_bd<Q8, D>(pl, st, ev);
+                if (q4) return launch_bd<Q4, D>(pl, st, ev);
+                if (f16) return launch_bd<F16, D>(pl, st, ev);
+            }
+            break;
+        case Kernel::Mq:
+            if constexpr (D == 64 || D == 128 || D == 256) {
+                if (q8) return launch_mq<Q8, D>(pl, st, ev);
+                if (q4) return launch_mq<Q4, D>(pl, st, ev);
+            }
+            break;
+        case Kernel::Split:
+        case Kernel::SplitLd:
+            if constexpr (D == 64 || D == 128 || D == 256) {
+                if (pl.kt != pl.vt && pl.vt != VT_F16T) return launch_mixed<D>(pl, st, ev);
+            }
+            if constexpr (D % QK == 0) {
+                if (q8) return launch_gran<Q8, Q8, D>(pl, st, ev);
+                if (q4) return launch_gran<Q4, Q4, D>(pl, st, ev);
+            }
+            if (f16) return launch_gran<F16, F16, D>(pl, st, ev);
+            if (pl.kt == F16 && pl.vt == VT_F16T) return launch_gran<F16, VT_F16T, D>(pl, st, ev);
+            break;
     }
-    if constexpr (D == 64 || D == 96 || D == 128) {
-        if (pl.bd) {
-            if (pl.kt == FATTN_TYPE_Q8_0 && pl.vt == FATTN_TYPE_Q8_0) return launch_bd<FATTN_TYPE_Q8_0, D>(pl, st, ev);
-            if (pl.kt == FATTN_TYPE_Q4_0 && pl.vt == FATTN_TYPE_Q4_0) return launch_bd<FATTN_TYPE_Q4_0, D>(pl, st, ev);
-            if (pl.kt == FATTN_TYPE_F16 && pl.vt == FATTN_TYPE_F16) return launch_bd<FATTN_TYPE_F16, D>(pl, st, ev);
-            return FATTN_ERR_UNSUPPORTED_TYPE;
-        }
-    }
-    if constexpr (D == 64 || D == 128 || D == 256) {
-        if (pl.mq) {
-            if (pl.kt == FATTN_TYPE_Q8_0 && pl.vt == FATTN_TYPE_Q8_0) return launch_mq<FATTN_TYPE_Q8_0, D>(pl, st, ev);
-            if (pl.kt == FATTN_TYPE_Q4_0 && pl.vt == FATTN_TYPE_Q4_0) return launch_mq<FATTN_TYPE_Q4_0, D>(pl, st, ev);
-            return FATTN_ERR_UNSUPPORTED_TYPE;
-        }
-    }
-    if (pl.pf || pl.mq || pl.bd) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
-    if constexpr (D % QK == 0) {
-        if (pl.kt == FATTN_TYPE_Q8_0 && pl.vt == FATTN_TYPE_Q8_0)
-            return launch_gran<FATTN_TYPE_Q8_0, FATTN_TYPE_Q8_0, D>(pl, st, ev);
-        if (pl.kt == FATTN_TYPE_Q4_0 && pl.vt == FATTN_TYPE_Q4_0)
-            return launch_gran<FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_0, D>(pl, st, ev);
-    }
-    if (pl.kt == FATTN_TYPE_F16 && pl.vt == FATTN_TYPE_F16) return launch_gran<FATTN_TYPE_F16, FATTN_TYPE_F16, D>(pl, st, ev);
-    if (pl.kt == FATTN_TYPE_F16 && pl.vt == VT_F16T) return launch_gran<FATTN_TYPE_F16, VT_F16T, D>(pl, st, ev);
     return FATTN_ERR_UNSUPPORTED_TYPE;
 }
 

@@ -145,9 +145,9 @@ def _check(rc: int, what: str):
 
 
 def set_option(option: int, value: int):
-    """Planner override (include/fattn_debug.h fattn_set_option): OPT_MQ_ROWS_PER_WAVE
-    (0 auto, 16, 32), OPT_MQ_DISABLE (1 = split-KV kernel only), OPT_SPLIT_STEPS
-    (32-position steps per wave, 0 auto) or OPT_SPLIT_INFLIGHT (steps in flight, 0 auto)."""
+    """Planner override (fattn_set_option): the OPT_* constants above mirror the
+    FATTN_OPT_* enum of include/fattn_debug.h, which documents every option's
+    values and effect.  Raises FattnError for an unknown option or an illegal value."""
     _check(lib().fattn_set_option(option, value), "fattn_set_option")
 
 

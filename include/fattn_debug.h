@@ -25,10 +25,12 @@ int fattn_ext_events(const fattn_params* p, void* stream, void* ev_begin, void* 
 
 /* Planner overrides (tests, benchmarks).  They are PROCESS-WIDE: one call changes
  * the plans of every later fattn_ext / fattn_describe / fattn_workspace_size on
- * every host thread (stored in atomics, so never torn, but a thread that sets an
- * option while another plans races with it).  Set them before launching, or from
- * one thread.  Option ids of removed experiments are not reused.  Returns
- * FATTN_OK or FATTN_ERR_INVALID_ARG. */
+ * every host thread.  Each of those calls copies all options once and plans from
+ * the copy, so one plan never mixes two values of an option; a thread that sets
+ * options while another plans still decides which values that plan sees.  Set
+ * them before launching, or from one thread.  Option ids of removed experiments
+ * are not reused.  Returns FATTN_OK or FATTN_ERR_INVALID_ARG.  (Each option's
+ * default and legal values: one row of kOptionTable, csrc/fattn_plan.h.) */
 enum {
     FATTN_OPT_MQ_ROWS_PER_WAVE = 1, /* multi-query kernel: 0 = auto, 16 (4 waves x 16 rows), 32 (8 waves x 32 rows) */
     FATTN_OPT_MQ_DISABLE = 2,       /* 1 = never pick the multi-query kernel (split-KV kernel only) */
