@@ -199,12 +199,19 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
     return n < 0 || (size_t)n >= cap ? FATTN_ERR_INVALID_ARG : FATTN_OK;
 }
 
-int fattn_ext(const fattn_params* p, void* stream) { return fattn_ext_events(p, stream, nullptr, nullptr); }
+}  // extern "C"
 
-int fattn_ext_events(const fattn_params* p, void* stream, void* ev_begin, void* ev_end) {
+namespace {
+
+// The one launch path of fattn_ext / fattn_ext_events / fattn_ext_sinks.  The
+// plan is a function of `p` alone: `sinks` (null: off) only rides along as a
+// kernel argument of the plan's kernels (SplitArgs::sinks)
+int launch_ext(const fattn_params* p, const float* sinks, void* stream, void* ev_begin, void* ev_end) {
     Plan pl;
     const int rc = plan_now(p, pl);
     if (rc != FATTN_OK) return rc;
+    if ((uintptr_t)sinks % 4) return FATTN_ERR_ALIGNMENT;
+    pl.a.sinks = sinks;
     if (pl.ws_bytes) {
         if (!p->workspace || p->workspace_bytes < pl.ws_bytes || (uintptr_t)p->workspace % 16) return FATTN_ERR_WORKSPACE;
         uint8_t* w = (uint8_t*)p->workspace;
@@ -231,6 +238,20 @@ int fattn_ext_events(const fattn_params* p, void* stream, void* ev_begin, void* 
         case 128: return launch_types<128>(pl, st, ev);
         default: return launch_types<256>(pl, st, ev);
     }
+}
+
+}  // namespace
+
+extern "C" {
+
+int fattn_ext(const fattn_params* p, void* stream) { return launch_ext(p, nullptr, stream, nullptr, nullptr); }
+
+int fattn_ext_events(const fattn_params* p, void* stream, void* ev_begin, void* ev_end) {
+    return launch_ext(p, nullptr, stream, ev_begin, ev_end);
+}
+
+int fattn_ext_sinks(const fattn_params* p, const float* sinks, void* stream) {
+    return launch_ext(p, sinks, stream, nullptr, nullptr);
 }
 
 int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void* mask, float* dst, float scale,

@@ -245,9 +245,14 @@ __device__ __forceinline__ void bd_tile_merge(const SplitArgs& a, uint8_t* smem,
     for (int r = chunk * kBdWaves + wave; r < qt_rows; r += kBdWaves * n) {  // wave-uniform
         const int64_t s0 = tile * n * kBdRows + r;  // chunk 0's row r
         const int rq = div_R(a, r);
-        float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + ik2 * a.rk2 + (r - rq * a.R)) * D;
+        const int riq2 = ik2 * a.rk2 + (r - rq * a.R);
+        float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
         if (ok) {
-            merge_row_parts<D, 8>(a.ws_o + s0 * D, a.ws_ml + 2 * s0, n, out, lane, kBdRows * D, 2 * kBdRows);
+            merge_row_parts<D, 8>(a.ws_o + s0 * D, a.ws_ml + 2 * s0, n, out, lane, kBdRows * D, 2 * kBdRows,
+                                  [&]() -> const float* {
+                                      const float* sinks = a.sinks;
+                                      return sinks ? sinks + riq2 : nullptr;
+                                  });
         } else if (lane < D / 4) {
             *(f32x4*)(out + 4 * lane) = f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
         }
@@ -330,6 +335,14 @@ __device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, con
     if (a.n_chunks == 1) {
         const int q2 = ik2 * a.rk2 + (pr - rq * a.R);
         float* out = a.dst + (((int64_t)iq3 * a.NQ + q1) * a.H + q2) * D + c0;
+        if (const float* sinks = a.sinks) {  // (wave-uniform; rows differ per thread: one load each)
+            bool dead;
+            const float inv = sink_inv(M, L, sinks[q2], dead);
+#pragma unroll
+            for (int e = 0; e < kDpt; e += 4)
+                *(f32x4*)(out + e) = sink_row(f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]}, inv, dead);
+            return;
+        }
         const float inv = 1.0f / L;  // fully masked row -> NaN like the reference
 #pragma unroll
         for (int e = 0; e < kDpt; e += 4) {
@@ -695,13 +708,15 @@ __global__ __launch_bounds__(256) void fattn_bd_merge_kernel(const SplitArgs a) 
     if (p >= min(a.QPT, a.NQ - qt * a.QPT) * a.R) return;
     const int64_t slot0 = ((int64_t)iq3 * gridDim.y + y) * a.n_chunks * kBdRows + p;  // chunk 0's row
     const int rq = div_R(a, p);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + ik2 * a.rk2 + (p - rq * a.R)) * D;
+    const int riq2 = ik2 * a.rk2 + (p - rq * a.R);
+    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
+    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
     if constexpr (F16) {
         merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  kBdRows * D, 2 * kBdRows);
+                                  kBdRows * D, 2 * kBdRows, sink);
     } else {
         merge_row_parts<D, KIT, PLAIN ? 0 : kAuxSc1>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                                    kBdRows * D, 2 * kBdRows);
+                                                    kBdRows * D, 2 * kBdRows, sink);
     }
 }
 

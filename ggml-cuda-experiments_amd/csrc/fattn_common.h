@@ -265,6 +265,35 @@ __device__ __forceinline__ float xf_score(const ScoreXf& x, float scale, float s
     return __builtin_fmaf(slope, m, v);
 }
 
+// ---------------------------------------------------------------- attention sinks
+// ggml's FLASH_ATTN_EXT src[4]: one extra logit per q head that joins the
+// softmax denominator and has no value row (include/fattn.h).  Every kernel
+// ends a row with a state (M, L, acc): M the reference max in log2 units, L =
+// sum 2^(score - M), acc = sum 2^(score - M) v.  With the raw sink s
+// (natural units: not scaled, capped or sloped) the row is
+//     acc / (L + 2^(s log2e - M)),
+// so sink_inv() returns the factor that stands where 1 / L stood, once per
+// output row, at the sites that normalise into dst (never where a chunk
+// partial is published).  Overflow-safe form: with mm = max(M, s'),
+// e = 2^(M - mm), the factor is e / (L e + 2^(s' - mm)) -- both exponents
+// <= 0 and one of them 0, so the denominator lies in [min(L, 1), L + 1] and no
+// finite sink gives inf or NaN; a sink far above M gives e = 0 and a zero
+// row, one far below (or -inf: no sink) gives 1 / L.
+// `dead`: the row's mask was -inf everywhere (M = -inf, L = 0; the factor is
+// NaN then, and acc may be too).  ggml's row is S = 1, VKQ = 0: the caller
+// writes zeros by selection, sink_row().
+__device__ __forceinline__ float sink_inv(float M, float L, float sink, bool& dead) {
+    const float s = sink * 1.4426950408889634f;
+    dead = !(L > 0.0f) || M == -__builtin_inff();
+    const float mm = fmaxf(M, s);
+    const float e = __builtin_amdgcn_exp2f(M - mm);
+    return e / __builtin_fmaf(L, e, __builtin_amdgcn_exp2f(s - mm));
+}
+__device__ __forceinline__ float sink_row(float acc, float inv, bool dead) { return dead ? 0.0f : acc * inv; }
+__device__ __forceinline__ f32x4 sink_row(f32x4 acc, float inv, bool dead) {
+    return dead ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc * inv;
+}
+
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }

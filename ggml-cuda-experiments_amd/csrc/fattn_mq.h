@@ -428,10 +428,18 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
     for (int gi = 0; gi < NG; gi++) l_tot[gi] = grp4_sum(l_run[gi]);
 
     if (a.n_chunks == 1) {
+        const float* sinks = a.sinks;
 #pragma unroll
         for (int gi = 0; gi < NG; gi++) {
             if (!row_ok[gi]) continue;
             float* out = a.dst + (((int64_t)iq3 * a.NQ + iq1[gi]) * a.H + iq2[gi]) * D + 4 * g;
+            if (sinks) {  // (wave-uniform; m_run is the row's reference max in log2 units)
+                bool dead;
+                const float inv = sink_inv(m_run[gi], l_tot[gi], sinks[iq2[gi]], dead);
+#pragma unroll
+                for (int c = 0; c < NC; c++) *(f32x4*)(out + 16 * c) = sink_row(o[gi][c], inv, dead);
+                continue;
+            }
             const float inv = 1.0f / l_tot[gi];  // fully masked row -> NaN like the reference
 #pragma unroll
             for (int c = 0; c < NC; c++) {
@@ -526,12 +534,15 @@ __global__ __launch_bounds__(256) void fattn_mq_merge_kernel(const SplitArgs a) 
     if (p >= min(a.QPT, a.NQ - qt * a.QPT) * a.R) return;
     const int64_t slot0 = ((int64_t)iq3 * gridDim.y + ys) * a.n_chunks * kRows + tm;  // chunk 0's row
     const int rq = div_R(a, p);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + ik2 * a.rk2 + (p - rq * a.R)) * D;
+    const int riq2 = ik2 * a.rk2 + (p - rq * a.R);
+    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
+    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
     if constexpr (F16) {
         merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  kRows * D, 2 * kRows);
+                                  kRows * D, 2 * kRows, sink);
     } else {
-        merge_row_parts<D, KIT>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane, kRows * D, 2 * kRows);
+        merge_row_parts<D, KIT>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane, kRows * D, 2 * kRows,
+                                sink);
     }
 }
 

@@ -748,18 +748,29 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     // rows, 64 lanes x 16 B = 1 KiB of contiguous row bytes per instruction
     // (cdna_hip_programming.md T21).
     const float l_tot = xor32_pair(l2.x + l2.y, false);
+    // attention sinks (SplitArgs::sinks; wave-uniform branch): this lane's row's
+    // head's sink joins the denominator, sink_inv() -- m_run is the row's
+    // reference max in log2 units, (m_run, l_tot) = (-inf, 0) a fully masked row
+    // (inv, none, fill) once, ahead of the store loops: 1 / l_tot and NaN for a
+    // fully masked row like the reference, or the sink's factor and zeros
+    float inv = 1.0f / l_tot;
+    bool none = l_tot == 0.0f;
+    float fill = __builtin_nanf("");
+    if (const float* sinks = a.sinks) {
+        inv = sink_inv(m_run, l_tot, row_ok ? sinks[iq2] : 0.0f, none);
+        fill = 0.0f;
+    }
 #ifdef FATTN_PF_DIRECT_STORE
     // diagnostic build only (A/B): the row-per-lane stores from the accumulator layout
     if (row_ok) {
         float* out = a.dst + (((int64_t)iq3 * a.NQ + iq1) * a.H + iq2) * D + 4 * h;
-        const float inv = 1.0f / l_tot;
 #pragma unroll
         for (int db = 0; db < NDB; db++) {
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = l_tot == 0.0f ? __builtin_nanf("") : o[db][4 * u + r] * inv;
+                for (int r = 0; r < 4; r++) v[r] = none ? fill : o[db][4 * u + r] * inv;
                 if (32 * db + 8 * u + 4 * h < D) *(f32x4*)(out + 32 * db + 8 * u) = v;
             }
         }
@@ -771,7 +782,6 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     __syncthreads();  // every wave is done with the images, raw tiles and mask slots
     float* park = (float*)smem + wave * (kPfRowsW * kStride);
     {
-        const float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
         float* pk = park + c32 * kStride + 4 * h;
 #pragma unroll
         for (int db = 0; db < NDB; db++) {
@@ -779,7 +789,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
             for (int u = 0; u < 4; u++) {
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = l_tot == 0.0f ? __builtin_nanf("") : o[db][4 * u + r] * inv;
+                for (int r = 0; r < 4; r++) v[r] = none ? fill : o[db][4 * u + r] * inv;
                 *(f32x4*)(pk + 32 * db + 8 * u) = v;
             }
         }

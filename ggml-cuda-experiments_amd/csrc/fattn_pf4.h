@@ -1198,10 +1198,22 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
     constexpr int kStride = D + 4;
     __syncthreads();  // every wave is done with the rings
     float* park = (float*)smem + wave * (kPf4RowsW * kStride);
+    const float* sinks = a.sinks;
 #pragma unroll
     for (int rb = 0; rb < 2; rb++) {
         const float l_tot = PF4_XOR32(l2[rb].x + l2[rb].y, false);
-        const float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
+        float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
+        bool none = l_tot == 0.0f;
+        float fill = __builtin_nanf("");
+        // attention sinks (SplitArgs::sinks; wave-uniform branch, plain C++ behind the
+        // asm chains): the row's head's sink joins the denominator, sink_inv() --
+        // m_run[rb] is the row's reference max in log2 units
+        if (sinks) {
+            int q1, q2;
+            const bool ok = row_of(kPf4RowsW * wave + 32 * rb + c32, q1, q2);
+            inv = sink_inv(m_run[rb], l_tot, ok ? sinks[q2] : 0.0f, none);
+            fill = 0.0f;
+        }
         float* pk = park + (32 * rb + c32) * kStride + 4 * h;
 #pragma unroll
         for (int db = 0; db < NDB; db++) {
@@ -1209,7 +1221,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
             for (int u = 0; u < 4; u++) {
                 f32x4 v;
 #pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = l_tot == 0.0f ? __builtin_nanf("") : o[rb][db][4 * u + r] * inv;
+                for (int r = 0; r < 4; r++) v[r] = none ? fill : o[rb][db][4 * u + r] * inv;
                 *(f32x4*)(pk + 32 * db + 8 * u) = v;
             }
         }

@@ -110,6 +110,10 @@ struct SplitArgs {
                         // (half the partial bytes; store_part_f16, merge_row_parts_h)
     ScoreXf xf;         // max_bias / logit_softcap (xf_score, fattn_common.h); xf.live == 0: off.  Last: the
                         // fields above keep their kernarg offsets
+    const float* sinks; // attention sinks, one raw f32 logit per q head of this launch (fattn_ext_sinks;
+                        // sink_inv, fattn_common.h), or null: off.  Appended behind xf, which keeps its
+                        // offset as every field above it does.  Read only in the epilogues that
+                        // normalise into dst, under a wave-uniform branch outside every tile loop
 };
 
 // XOR mask of the 16-B chunk swizzle of an LDS row of `cpr` chunks: the largest
@@ -846,8 +850,14 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
     const int riq1 = qt * a.QPT + rq;
     const int riq2 = ik2 * a.rk2 + hs * a.R;
     float* out = a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D + d4;
-    const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
-    *(f32x4*)out = acc * inv;
+    if (const float* sinks = a.sinks) {  // (wave-uniform) the head's sink joins the merged row's denominator
+        bool dead;
+        const float inv = sink_inv(M, L, sinks[riq2], dead);
+        *(f32x4*)out = sink_row(acc, inv, dead);
+    } else {
+        const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
+        *(f32x4*)out = acc * inv;
+    }
     FATTN_SSTAMP(13);
 }
 
@@ -862,9 +872,15 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
 template <int D>
 constexpr int merge_ppr() { return 64 % (D / 4) == 0 ? 64 / (D / 4) : 1; }  // parts per lane row (4, 2, 1)
 
-template <int D, int kIt = 16, int AUX = kAuxSc1>  // kIt: loads per lane per round trip; AUX: the loads' cache bits
+// `sink_of()`: the address of the row's q head's sink (SplitArgs::sinks), or
+// null: no sinks.  A callable, so that it is evaluated where the row is
+// normalised and the pointer is not held across the loads above it.
+struct NoSink {
+    __device__ __forceinline__ const float* operator()() const { return nullptr; }
+};
+template <int D, int kIt = 16, int AUX = kAuxSc1, typename SinkOf = NoSink>  // kIt: loads per lane per round trip; AUX: the loads' cache bits
 __device__ __forceinline__ void merge_row_parts(const float* parts_o, const float* parts_ml, int NP, float* out,
-                                                int lane, int ostride = D, int mstride = 2) {
+                                                int lane, int ostride = D, int mstride = 2, SinkOf sink_of = SinkOf()) {
     constexpr float kNegInf = -__builtin_inff();
     constexpr int LPP = D / 4;              // lanes per part
     constexpr int PPR = merge_ppr<D>();     // D = 80 / 96: 1
@@ -915,6 +931,12 @@ __device__ __forceinline__ void merge_row_parts(const float* parts_o, const floa
         acc.w = xor32_pair(acc.w, false);
     }
     if (h) return;
+    if (const float* sink = sink_of()) {  // (wave-uniform)
+        bool dead;
+        const float inv = sink_inv(M, L, *sink, dead);
+        *(f32x4*)(out + d4) = sink_row(acc, inv, dead);
+        return;
+    }
     const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
     *(f32x4*)(out + d4) = acc * inv;
 }
@@ -954,9 +976,9 @@ __device__ __forceinline__ void store_part_f16(uint16_t* dst, const float (&acc)
 // third lane-swap level).
 template <int D>
 constexpr int merge_ppr_h() { return 64 % (D / 8) == 0 ? 64 / (D / 8) : 1; }  // (4, 2, 1)
-template <int D, int kIt>
+template <int D, int kIt, typename SinkOf = NoSink>
 __device__ __forceinline__ void merge_row_parts_h(const uint16_t* parts_o, const float* parts_ml, int NP, float* out,
-                                                  int lane, int ostride, int mstride) {
+                                                  int lane, int ostride, int mstride, SinkOf sink_of = SinkOf()) {
     constexpr float kNegInf = -__builtin_inff();
     constexpr int LPP = D / 8;
     constexpr int PPR = merge_ppr_h<D>();
@@ -1004,6 +1026,13 @@ __device__ __forceinline__ void merge_row_parts_h(const uint16_t* parts_o, const
         if constexpr (PPR >= 2) acc[e] = xor32_pair(acc[e], false);
     }
     if (h) return;
+    if (const float* sink = sink_of()) {  // (wave-uniform; L = sum_p w_p l_p is the row's whole sum at reference M)
+        bool dead;
+        const float inv = sink_inv(M, L, *sink, dead);
+        *(f32x4*)(out + d8) = sink_row(f32x4{acc[0], acc[1], acc[2], acc[3]}, inv, dead);
+        *(f32x4*)(out + d8 + 4) = sink_row(f32x4{acc[4], acc[5], acc[6], acc[7]}, inv, dead);
+        return;
+    }
     const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
     *(f32x4*)(out + d8) = f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
     *(f32x4*)(out + d8 + 4) = f32x4{acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv};
@@ -1087,8 +1116,14 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
     float* out = a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D;
     if (a.n_chunks == 1) {
         if (h == 0) {
-            const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;
-            *(f32x4*)(out + d4) = acc * inv;
+            if (const float* sinks = a.sinks) {  // (wave-uniform)
+                bool dead;
+                const float inv = sink_inv(M, L, sinks[riq2], dead);
+                *(f32x4*)(out + d4) = sink_row(acc, inv, dead);
+            } else {
+                const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;
+                *(f32x4*)(out + d4) = acc * inv;
+            }
         }
         return;
     }
@@ -1116,9 +1151,13 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
     const float* po_all = a.ws_o + tile * a.n_chunks * D;
     const float* pml_all = a.ws_ml + 2 * tile * a.n_chunks;
     const int need = (a.n_chunks + merge_ppr<D>() - 1) / merge_ppr<D>();
-    if (need <= 4) merge_row_parts<D, 4>(po_all, pml_all, a.n_chunks, out, lane);
-    else if (need <= 8) merge_row_parts<D, 8>(po_all, pml_all, a.n_chunks, out, lane);
-    else merge_row_parts<D>(po_all, pml_all, a.n_chunks, out, lane);
+    auto sink = [&]() -> const float* {
+        const float* sinks = a.sinks;
+        return sinks ? sinks + riq2 : nullptr;
+    };
+    if (need <= 4) merge_row_parts<D, 4>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
+    else if (need <= 8) merge_row_parts<D, 8>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
+    else merge_row_parts<D>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
     FATTN_SSTAMP(13);
 }
 
@@ -1208,7 +1247,19 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
         lw[w] = tm < rv ? ml[2 * tm + 1] : 0.0f;
         M = fmaxf(M, mw[w]);
     }
-    float L = 0.0f;
+    // Attention sinks, single chunk (the row is normalised below): the sink is one
+    // more part of the merge -- max s log2e, sum 1, no O row -- so it joins M and
+    // L here and 1 / L stays the factor: sink_inv()'s value in the merge's own
+    // overflow-safe form, with no second normalising statement in a body that
+    // sits at its SGPR limit.  Mk: the max over the keys alone; a fully masked
+    // row (Mk = -inf) keeps L = 0, so the select on L == 0 below still finds it.
+    // Without sinks ms = -inf leaves M and L as they were, bit for bit
+    const float Mk = M;
+    float ms = kNegInf;
+    if (a.n_chunks == 1 && a.sinks != nullptr && tm < rv)  // (wave-uniform but for the row bound)
+        ms = a.sinks[ik2 * a.rk2 + hs * a.R + (tm - div_R(a, tm) * a.R)] * 1.4426950408889634f;
+    M = fmaxf(M, ms);
+    float L = (ms == kNegInf || Mk == kNegInf) ? 0.0f : __builtin_amdgcn_exp2f(ms - M);
     float acc[EPT];
 #pragma unroll
     for (int e = 0; e < EPT; e++) acc[e] = 0.0f;
@@ -1222,6 +1273,7 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
             for (int e = 0; e < EPT; e++) acc[e] += wt * ow[e];
         }
     }
+    auto head_of = [&](int r) { return ik2 * a.rk2 + hs * a.R + (r - div_R(a, r) * a.R); };  // q head of packed row r (in-kernel merge)
     auto dst_row = [&](int r) -> float* {
         const int rq = div_R(a, r);
         const int riq1 = qt * a.QPT + rq;
@@ -1231,14 +1283,18 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     if (a.n_chunks == 1) {
         if (tm < rv && dok) {
             float* out = dst_row(tm) + d0;
-            const float inv = 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
+            // L == 0: the row has no live key -- NaN like the reference, zeros with
+            // sinks; by selection either way
+            const float inv = 1.0f / L;
+            const bool none = L == 0.0f;
+            const float fill = a.sinks != nullptr ? 0.0f : __builtin_nanf("");  // (wave-uniform)
 #pragma unroll
             for (int e = 0; e < EPT; e += 4) {
                 f32x4 v;
-                v.x = L == 0.0f ? __builtin_nanf("") : acc[e] * inv;
-                v.y = L == 0.0f ? __builtin_nanf("") : acc[e + 1] * inv;
-                v.z = L == 0.0f ? __builtin_nanf("") : acc[e + 2] * inv;
-                v.w = L == 0.0f ? __builtin_nanf("") : acc[e + 3] * inv;
+                v.x = none ? fill : acc[e] * inv;
+                v.y = none ? fill : acc[e + 1] * inv;
+                v.z = none ? fill : acc[e + 2] * inv;
+                v.w = none ? fill : acc[e + 3] * inv;
                 *(f32x4*)(out + e) = v;
             }
         }
@@ -1298,7 +1354,11 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
             const int64_t s0 = tile * a.n_chunks * kRows + r;  // chunk 0's row r
             float* out = dst_row(r);
             if (ok) {
-                merge_row_parts<D, 8>(a.ws_o + s0 * D, a.ws_ml + 2 * s0, a.n_chunks, out, lane, kRows * D, 2 * kRows);
+                merge_row_parts<D, 8>(a.ws_o + s0 * D, a.ws_ml + 2 * s0, a.n_chunks, out, lane, kRows * D, 2 * kRows,
+                                      [&]() -> const float* {
+                                          const float* sinks = a.sinks;
+                                          return sinks ? sinks + head_of(r) : nullptr;
+                                      });
             } else if (lane < D / 4) {
                 *(f32x4*)(out + 4 * lane) = f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""),
                                                   __builtin_nanf("")};
@@ -1950,12 +2010,13 @@ __global__ __launch_bounds__(256) void fattn_merge_kernel(const SplitArgs a) {
     const int riq1 = qt * a.QPT + rq;
     const int riq2 = ik2 * a.rk2 + hs * a.R + (tm - rq * a.R);
     float* out = a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D;
+    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
     if constexpr (F16) {
         merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  kRows * D, 2 * kRows);
+                                  kRows * D, 2 * kRows, sink);
     } else {
         merge_row_parts<D, KIT, PLAIN ? 0 : kAuxSc1>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                                    kRows * D, 2 * kRows);
+                                                    kRows * D, 2 * kRows, sink);
     }
 }
 
@@ -2023,7 +2084,18 @@ __device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, i
     const float Lr = seg_reduce<false>(has_ml ? wt * fl(mlb.y) : 0.0f, NCP);
     if (mr < rv) {
         wts[mr][mc] = wt;
-        if (mc == 0) rowL[mr] = Lr;
+        // with sinks rowL holds the row's whole factor instead (sink_inv: M is known
+        // here and nowhere below), -1 for a fully masked row -- a factor is >= 0
+        if (mc == 0) {
+            float lr = Lr;
+            if (const float* sinks = a.sinks) {  // (wave-uniform)
+                const int pr = row_base + mr;
+                bool dead;
+                const float inv = sink_inv(Mr, Lr, sinks[ik2 * a.rk2 + hs * a.R + (pr - div_R(a, pr) * a.R)], dead);
+                lr = dead ? -1.0f : inv;
+            }
+            rowL[mr] = lr;
+        }
     }
     __syncthreads();
 
@@ -2063,15 +2135,19 @@ __device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, i
         f32x4 x = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
         for (int k = 0; k < kRows; k++) x += (k < G) ? part[k] : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        // (with sinks rowL holds the factor, -1 for a fully masked row: above)
         const float Lrow = rowL[rr];
-        const float inv = 1.0f / Lrow;
+        const bool with_sinks = a.sinks != nullptr;  // (wave-uniform)
+        const float inv = with_sinks ? Lrow : 1.0f / Lrow;
+        const bool none = with_sinks ? Lrow < 0.0f : Lrow == 0.0f;
+        const float fill = with_sinks ? 0.0f : __builtin_nanf("");
         const int pr = row_base + rr;  // packed row within the tile
         const int rq = div_R(a, pr);
         const int riq1 = qt * a.QPT + rq;
         const int riq2 = ik2 * a.rk2 + hs * a.R + (pr - rq * a.R);
         f32x4 o4;
 #pragma unroll
-        for (int j = 0; j < 4; j++) o4[j] = (Lrow == 0.0f) ? __builtin_nanf("") : x[j] * inv;
+        for (int j = 0; j < 4; j++) o4[j] = none ? fill : x[j] * inv;
         *(f32x4*)(a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D + dq) = o4;
     }
 }

@@ -34,7 +34,7 @@ ERRORS = {
 EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
-    "fattn_describe", "fattn_cpy",
+    "fattn_describe", "fattn_cpy", "fattn_ext_sinks",
 )
 OPT_MQ_ROWS_PER_WAVE = 1
 OPT_MQ_DISABLE = 2
@@ -112,6 +112,8 @@ def lib() -> C.CDLL:
         L.fattn_workspace_init.argtypes = [vp, sz, vp]
         L.fattn_ext.restype = C.c_int
         L.fattn_ext.argtypes = [C.POINTER(FattnParams), vp]
+        L.fattn_ext_sinks.restype = C.c_int
+        L.fattn_ext_sinks.argtypes = [C.POINTER(FattnParams), vp, vp]
         L.fattn_ext_events.restype = C.c_int
         L.fattn_ext_events.argtypes = [C.POINTER(FattnParams), vp, vp, vp]
         L.fattn_ext_f16_launch.restype = C.c_int
@@ -247,10 +249,40 @@ def describe(p: FattnParams) -> str:
     return buf.value.decode()
 
 
-def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None):
+NO_SINKS = object()   # Attention.retarget(sinks=NO_SINKS): back to a launch without sinks
+
+
+def _sinks_ptr(sinks, n_head: int) -> Optional[int]:
+    """sinks: None, a raw device pointer (taken on trust), or a torch tensor:
+    contiguous float32 on the GPU with exactly n_head = q.ne[2] values -- a host
+    tensor or a short slice would be an illegal or out-of-bounds device read."""
+    if sinks is None or isinstance(sinks, int):
+        return sinks
+    import torch
+    if sinks.dtype != torch.float32 or not sinks.is_contiguous():
+        raise ValueError("sinks: a contiguous float32 tensor, one value per q head of the launch")
+    if not sinks.is_cuda:
+        raise ValueError("sinks: a device tensor (this one is on the host)")
+    if sinks.numel() != n_head:
+        raise ValueError(f"sinks: {sinks.numel()} values for the launch's {n_head} q heads (q.ne[2])")
+    return _tptr(sinks)
+
+
+def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sinks=None):
     """GGML_OP_FLASH_ATTN_EXT on the GPU (replaces flash_attn_ext_f16, src/flash-llama.h:5-32).
-    ev_begin/ev_end: optional raw hipEvent_t handles recorded around the main kernel."""
-    if ev_begin is None and ev_end is None:
+    ev_begin/ev_end: optional raw hipEvent_t handles recorded around the main kernel.
+    sinks: ggml's src[4], one raw f32 logit per q head of THIS launch that joins
+    the softmax denominator (include/fattn.h, fattn_ext_sinks) -- a device pointer
+    or a torch f32 tensor of p.q.ne[2] values (a head shard passes
+    shard.HeadShard.sink_slice(sinks)); None is fattn_ext.  The plan, the
+    workspace and describe(p) do not depend on it.  There is no events variant:
+    sinks with ev_begin / ev_end raises ValueError."""
+    if sinks is not None:
+        if ev_begin is not None or ev_end is not None:
+            raise ValueError("flash_attn_ext: sinks cannot be combined with ev_begin / ev_end")
+        ptr = _sinks_ptr(sinks, int(p.q.ne[2]))
+        _check(lib().fattn_ext_sinks(C.byref(p), ptr, _stream(stream)), "fattn_ext_sinks")
+    elif ev_begin is None and ev_end is None:
         _check(lib().fattn_ext(C.byref(p), _stream(stream)), "fattn_ext")
     else:
         _check(lib().fattn_ext_events(C.byref(p), _stream(stream), ev_begin, ev_end), "fattn_ext_events")
@@ -306,8 +338,10 @@ class Attention:
     """Reusable FLASH_ATTN_EXT call: builds the params once, owns its workspace."""
 
     def __init__(self, q: View, k: View, v: View, mask: Optional[View], dst, scale: float, kv_chunk: int = 0, *,
-                 max_bias: float = 0.0, logit_softcap: float = 0.0, n_head_total: int = 0, head_first: int = 0):
+                 max_bias: float = 0.0, logit_softcap: float = 0.0, n_head_total: int = 0, head_first: int = 0,
+                 sinks=None):
         import torch
+        self.sinks = sinks   # ggml's src[4] (flash_attn_ext): a pointer, a torch f32 tensor (kept alive here) or None
         self.p = ext_params(q, k, v, mask, _tptr(dst), scale, 0, 0, kv_chunk, max_bias=max_bias,
                             logit_softcap=logit_softcap, n_head_total=n_head_total, head_first=head_first)
         ws = workspace_size(self.p)
@@ -317,8 +351,14 @@ class Attention:
         self.p.workspace_bytes = self.workspace.numel()
         self.dst = dst
 
-    def retarget(self, q=None, k=None, v=None, dst=None, mask=None):
-        """Point the same call at other buffers with identical shapes/strides."""
+    def retarget(self, q=None, k=None, v=None, dst=None, mask=None, sinks=None):
+        """Point the same call at other buffers with identical shapes/strides.
+        None keeps what the call has.  sinks: another pointer or tensor of
+        q.ne[2] f32 values, or fattn.NO_SINKS to launch without sinks again."""
+        if sinks is NO_SINKS:
+            self.sinks = None
+        elif sinks is not None:
+            self.sinks = sinks
         if mask is not None:
             self.p.mask.data = mask
         if q is not None:
@@ -334,7 +374,7 @@ class Attention:
         return describe(self.p)
 
     def __call__(self, stream=None, ev_begin=None, ev_end=None):
-        flash_attn_ext(self.p, stream, ev_begin, ev_end)
+        flash_attn_ext(self.p, stream, ev_begin, ev_end, sinks=self.sinks)
         return self.dst
 
 

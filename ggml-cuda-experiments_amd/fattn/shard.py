@@ -43,6 +43,17 @@ class HeadShard:
             raise ValueError("HeadShard.H (the unsharded head count) is not set")
         return {"n_head_total": self.H, "head_first": self.h0}
 
+    def sink_slice(self, sinks):
+        """The rank's attention sinks: sinks[h0:h1] of the unsharded model's H
+        values (a torch tensor or numpy array: a view).  fattn_ext_sinks indexes
+        its array by the launch's LOCAL q head, so -- unlike the slopes, which
+        come from a formula over the global head index -- a slice takes its own
+        slice.  Passing the unsliced array would give every rank heads
+        0 .. n_heads-1's sinks: silently wrong."""
+        if self.H > 0 and len(sinks) != self.H:
+            raise ValueError(f"sink_slice: {len(sinks)} sinks for {self.H} heads")
+        return sinks[self.h0:self.h1]
+
 
 def shard_heads(H: int, Hkv: int, world: int, rank: int) -> HeadShard:
     """Contiguous kv-head groups; every rank gets the same count (the gather

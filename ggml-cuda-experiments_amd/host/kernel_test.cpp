@@ -38,6 +38,10 @@
 //   --softcap F          ggml's logit_softcap: cap * tanh(score / cap) before the mask
 //                        (both default 0 = off; either takes the fattn_params call, with
 //                        n_head_total / head_first set per device under --ngpu)
+//   --sinks BASE         ggml's attention sinks (src[4], fattn_ext_sinks): head h of the model
+//                        gets the raw extra logit BASE + 0.25 * (h % 8) in its softmax
+//                        denominator (the global head index under --ngpu: device g passes
+//                        its own slice); the CPU reference applies the same
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -123,10 +127,14 @@ void random_fill(std::vector<float>& a) {
 // per-head arithmetic and its order are the reference's, so the bits are too)
 // max_bias / softcap: ggml's FLASH_ATTN_EXT scalars (include/fattn.h), by its
 // host formulas -- score = cap * tanhf(acc * (scale / cap)) (softcap > 0) plus
-// slope(h) * mask; with both 0 the statements below are the reference's
+// slope(h) * mask; with both 0 the statements below are the reference's.
+// sinks (null: none): ggml's src[4], one raw logit per head joining (M, S) after
+// the row's last key by ggml's statement; the row is then the plain row times
+// g = vs * S_plain / S -- the factor form, so P keeps the plain row's f16 rounding
 void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, const std::vector<float>& v,
                    const std::vector<float>& mask, std::vector<float>& out, int N, int D, int H, int Hkv, float scale,
-                   const std::vector<int>& rows, int threads = 1, float max_bias = 0.0f, float softcap = 0.0f) {
+                   const std::vector<int>& rows, int threads = 1, float max_bias = 0.0f, float softcap = 0.0f,
+                   const std::vector<float>* sinks = nullptr) {
     const int r = H / Hkv;
     int n2 = 1;
     while (n2 * 2 <= H) n2 *= 2;
@@ -166,6 +174,22 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
                 }
             }
             for (int i = 0; i < N; i++) s[i] = expf(s[i] - M) / S;
+            float gsink = 1.0f;
+            if (sinks) {
+                const float sk = (*sinks)[h];
+                float vs = 1.0f, Ss = S;
+                if (sk > M) {
+                    vs = expf(M - sk);
+                    Ss = Ss * vs + 1.0f;
+                } else {
+                    Ss += expf(sk - M);
+                }
+                gsink = vs * S / Ss;
+                if (M == -INFINITY) {  // mask -inf everywhere: S = 1, VKQ = 0
+                    gsink = 0.0f;
+                    for (int i = 0; i < N; i++) s[i] = 0.0f;
+                }
+            }
             float* o = out.data() + ((size_t)row * H + h) * D;
             for (int c = 0; c < D; c++) {
                 float acc = 0.0f;
@@ -173,7 +197,7 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
                     const float p = rh(s[i]) * vv[(size_t)i * D + c];
                     acc = acc + p;
                 }
-                o[c] = acc;
+                o[c] = sinks ? acc * gsink : acc;
             }
         }
     };
@@ -217,7 +241,8 @@ int main(int argc, const char* argv[]) {
     bool parallel_kv = true, cpu_only = false;
     std::string mask_kind = "random";
     const char* dump = nullptr;
-    float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f;
+    float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
+    bool use_sinks = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -243,6 +268,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--ngpu") ngpu = atoi(next());
         else if (a == "--max-bias") max_bias = (float)atof(next());
         else if (a == "--softcap") softcap = (float)atof(next());
+        else if (a == "--sinks") sink_base = (float)atof(next()), use_sinks = true;
         else if (a == "--mask") {
             mask_kind = next();
             if (mask_kind != "random" && mask_kind != "zero" && mask_kind != "none") {
@@ -281,6 +307,7 @@ int main(int argc, const char* argv[]) {
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)
+    if (use_sinks) parallel_kv = false;                  // (nor the sinks: fattn_ext_sinks takes fattn_params)
 
     const int D = head_dim, H = num_heads, Hkv = num_kv_heads, N = kv_size, NQ = n_q;
     const float scale = 1.0f / sqrtf((float)D);
@@ -311,10 +338,13 @@ int main(int argc, const char* argv[]) {
             for (int i = 0; i < check_rows; i++) rows.push_back(b + i);
     }
     const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::vector<float> sinks(H);
+    for (int h = 0; h < H; h++) sinks[h] = sink_base + 0.25f * (float)(h % 8);
+    const std::vector<float>* sinks_ref = use_sinks ? &sinks : nullptr;
 
     if (cpu_only) {  // BASELINE config 1: kernel_test.h:50-66 on the host, nothing else
         std::vector<float> out((size_t)D * H * NQ);
-        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads, max_bias, softcap);
+        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref);
         print_array("Reference", out.data(), std::min(16, D * H));
         if (dump) {
             FILE* f = fopen(dump, "wb");
@@ -394,7 +424,7 @@ int main(int argc, const char* argv[]) {
 
     // CPU reference (kernel_test.h:50-66) on the checked rows
     std::vector<float> qkv((size_t)D * H * NQ, 0.0f), qkv_gpu((size_t)D * H * NQ);
-    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads, max_bias, softcap);
+    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref);
     print_array("Reference", qkv.data(), 16);
 
     // ---- per device: its head shard (kv heads [g Hkv/G, (g+1) Hkv/G) and their
@@ -413,6 +443,7 @@ int main(int argc, const char* argv[]) {
     struct Dev {
         hipStream_t st;
         float *q, *out, *gather;
+        float* sinks;  // this device's heads' sinks (--sinks), or null
         void *k, *v, *mask, *ws;
         size_t ws_bytes;
         fattn_params p;
@@ -438,6 +469,11 @@ int main(int argc, const char* argv[]) {
         HIP_CHECK(hipMemcpyAsync(d.k, kbytes.data() + kvb * g, kvb, hipMemcpyHostToDevice, d.st));
         HIP_CHECK(hipMemcpyAsync(d.v, vbytes.data() + kvb * g, kvb, hipMemcpyHostToDevice, d.st));
         HIP_CHECK(hipMemcpyAsync(d.mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, d.st));
+        d.sinks = nullptr;
+        if (use_sinks) {  // the slice of the model's sinks that belongs to this device's q heads
+            HIP_CHECK(hipMalloc(&d.sinks, sizeof(float) * Hl));
+            HIP_CHECK(hipMemcpyAsync(d.sinks, sinks.data() + (size_t)g * Hl, sizeof(float) * Hl, hipMemcpyHostToDevice, d.st));
+        }
         // the ext plan: the flash_attn_ext argument list of kernel_test.h:191-198
         // (n_q = 1) or its ne01 = n_q form, as a fattn_params view
         std::memset(&d.p, 0, sizeof(d.p));
@@ -486,7 +522,7 @@ int main(int argc, const char* argv[]) {
             int rc;
             if (parallel_kv)
                 rc = fattn_row(d.q, d.k, d.v, d.mask, d.ws, d.ws_bytes, d.out, D, N, H, scale, D * N, r_kv_heads, d.st);
-            else if (NQ == 1 && G == 1 && has_mask && !op_xf)
+            else if (NQ == 1 && G == 1 && has_mask && !op_xf && !use_sinks)
                 rc = fattn_ext_f16_launch(d.q, d.k, d.v, d.mask, d.out, scale,
                                           D, 1, H, 1,
                                           D, N, Hkv, 1,
@@ -496,7 +532,7 @@ int main(int argc, const char* argv[]) {
                                           D, H, 1, 1,
                                           kv_type, kv_type, d.ws, d.ws_bytes, d.st);
             else
-                rc = fattn_ext(&d.p, d.st);
+                rc = use_sinks ? fattn_ext_sinks(&d.p, d.sinks, d.st) : fattn_ext(&d.p, d.st);
             if (rc) return rc;
         }
         if (G > 1) {

@@ -13,6 +13,8 @@
  *                           (q/k/v/mask as ggml ne/nb views, f32 dst in the
  *                           permuted [seq][n_q][H][D] layout of flash-llama.h:434),
  *                           extended with K/V element types F16 / Q8_0 / Q4_0.
+ *   fattn_ext_sinks()    fattn_ext() with upstream ggml's src[4], the per-head attention
+ *                           sinks (absent from the reference; see its comment below).
  *   fattn_ext_f16_launch()  the positional argument list of flash-llama.h:7-32,
  *                           verbatim (ne00..ne03, ne10..ne13, ne31, nb31,
  *                           nb01..nb03, nb11..nb13, ne0..ne3), for call sites
@@ -169,6 +171,36 @@ size_t fattn_workspace_size(const fattn_params* p);
  * generation + 1), so a replayed graph finds it clean. */
 int fattn_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 int fattn_ext(const fattn_params* p, void* stream);
+
+/* fattn_ext with attention sinks: src[4] of ggml's GGML_OP_FLASH_ATTN_EXT (the
+ * gpt-oss family).  A sink is one extra logit per q head: it joins the softmax
+ * denominator and has no value row.  ggml passes it as a tensor of its own, and
+ * so does this entry point -- fattn_params does not grow.
+ *   sinks  device pointer to q.ne[2] contiguous f32 values, indexed by the
+ *          launch's LOCAL q head iq2: a head-sharded launch passes
+ *          sinks + head_first (no formula, so no global numbering as for the
+ *          slopes).  4-byte aligned, else FATTN_ERR_ALIGNMENT -- checked, like
+ *          every other validation, before anything launches; invalid params
+ *          return what fattn_ext returns for them, whatever sinks is.
+ *          NULL: exactly fattn_ext(p, stream) -- same code path, same bits.
+ * After the whole KV range a row with running max M and sum S in natural-log
+ * units (scale, the soft cap and slope * mask already in them) takes the sink
+ * s = sinks[iq2] as ggml does:
+ *     if (s > M) { ms = expf(M - s); VKQ *= ms; S = S * ms + 1; } else S += expf(s - M);
+ *     out = VKQ / S
+ * in closed form out = O / (L + exp(s - M)): the plain output times
+ * g = 1 / (1 + exp(s - lse)), lse the row's log-sum-exp.
+ *   - the sink is RAW: not multiplied by scale, not capped, no ALiBi slope.
+ *   - a row whose mask is -inf everywhere has S = 1, VKQ = 0: with sinks such a
+ *     row is zeros, not the NaN of fattn_ext.
+ *   - sinks[h] = -inf: no sink for that head.  NaN or +inf in the array is
+ *     undefined (the library cannot read device memory to check it).
+ * Sinks never change the plan, the grid, the workspace size or the describe
+ * string: fattn_workspace_size(p) and fattn_describe(p) are functions of p
+ * alone, so fattn_describe(p) is also the plan of the sinks launch.  The sink
+ * enters once per output row, in the epilogue that normalises into dst (after
+ * the chunk merge of a split-KV plan); the tile loops are untouched. */
+int fattn_ext_sinks(const fattn_params* p, const float* sinks, void* stream);
 
 /* flash-llama.h:7-32 argument list (K and V share nb11..nb13, flash-llama.h:123-125;
  * mask rows padded to ne31, nb31 bytes per row; one mask plane -- the list has
