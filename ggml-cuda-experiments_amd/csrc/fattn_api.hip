@@ -111,7 +111,7 @@ const char* fattn_strerror(int s) {
         case FATTN_OK: return "ok";
         case FATTN_ERR_INVALID_ARG: return "invalid argument";
         case FATTN_ERR_UNSUPPORTED_TYPE: return "unsupported tensor type";
-        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96, 128, 256)";
+        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256)";
         case FATTN_ERR_BAD_STRIDE: return "unsupported strides / layout";
         case FATTN_ERR_WORKSPACE: return "workspace too small";
         case FATTN_ERR_LAUNCH: return "HIP launch failed";
@@ -140,7 +140,8 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
     const int rc = plan_now(p, pl);
     if (rc != FATTN_OK) return rc;
     auto tn = [](int t) {
-        return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == VT_F16T ? "f16T" : "f16";
+        return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
+               : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == VT_F16T ? "f16T" : "f16";
     };
     const char* hm = pl.a.has_mask ? "mask" : "nomask";
     // the second-launch merge `name` of the plan, or its in-kernel merge (split, batched decode)
@@ -161,8 +162,9 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
                                : pl.pf4_sched == 4     ? "fattn_pf4_kernel(lean)"
                                : pl.pf4_sched == 3     ? "fattn_pf4_kernel(balanced)"
                                                        : "fattn_pf4_kernel(pipelined)";
-            std::snprintf(kern, sizeof kern, "%s%s%s%s%s%s<%s,D%d,%s>", pre ? "pf_prepass[" : "",
-                          pl.pf_stage ? (pl.stage_kt == FATTN_TYPE_Q8_0 ? "kv_stage_f16<q8_0>" : "kv_stage_f16<q4_0>") : "",
+            char stage[32] = "";
+            if (pl.pf_stage) std::snprintf(stage, sizeof stage, "kv_stage_f16<%s>", tn(pl.stage_kt));
+            std::snprintf(kern, sizeof kern, "%s%s%s%s%s%s<%s,D%d,%s>", pre ? "pf_prepass[" : "", stage,
                           pl.pf_stage && pl.pf_flags ? " + " : "", pl.pf_flags ? "pf_mask_flags" : "", pre ? "] + " : "",
                           body, tn(pl.kt), pl.D, hm);
             break;
@@ -339,10 +341,17 @@ int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n
     if (type == FATTN_TYPE_F16) {
         hipLaunchKernelGGL(dequant_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                            (const uint16_t*)src, dst, n);
-    } else if (type == FATTN_TYPE_Q8_0 || type == FATTN_TYPE_Q4_0) {
+    } else if (is_quant(type)) {
         if (k % QK) return FATTN_ERR_INVALID_ARG;
         const int64_t nb = n / QK;
-        if (type == FATTN_TYPE_Q8_0)
+        const dim3 grid((unsigned)((nb + 255) / 256));
+        if (type == FATTN_TYPE_Q4_1)
+            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
+        else if (type == FATTN_TYPE_Q5_0)
+            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
+        else if (type == FATTN_TYPE_Q5_1)
+            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q5_1>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
+        else if (type == FATTN_TYPE_Q8_0)
             hipLaunchKernelGGL(dequant_q8_0_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st,
                                (const uint8_t*)src, dst, nb);
         else
@@ -366,6 +375,15 @@ int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_r
     else if (type == FATTN_TYPE_Q4_0)
         hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q4_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
                            (uint8_t*)dst, nb);
+    else if (type == FATTN_TYPE_Q4_1)
+        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q4_1>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
+                           (uint8_t*)dst, nb);
+    else if (type == FATTN_TYPE_Q5_0)
+        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q5_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
+                           (uint8_t*)dst, nb);
+    else if (type == FATTN_TYPE_Q5_1)
+        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q5_1>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
+                           (uint8_t*)dst, nb);
     else
         return FATTN_ERR_UNSUPPORTED_TYPE;
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
@@ -375,7 +393,7 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     if (!src || !dst || !src->data || !dst->data) return FATTN_ERR_INVALID_ARG;
     if (src->type != FATTN_TYPE_F32 || src->nb[0] != 4) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int t = dst->type;
-    if (t != FATTN_TYPE_F16 && t != FATTN_TYPE_Q8_0 && t != FATTN_TYPE_Q4_0) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (t != FATTN_TYPE_F16 && !is_quant(t)) return FATTN_ERR_UNSUPPORTED_TYPE;
     for (int i = 0; i < 4; i++)
         if (src->ne[i] != dst->ne[i] || src->ne[i] <= 0) return FATTN_ERR_INVALID_ARG;
     const int64_t ue = t == FATTN_TYPE_F16 ? 1 : QK;
@@ -395,6 +413,9 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     (void)hipGetLastError();
     if (t == FATTN_TYPE_F16) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_F16>, grid, dim3(256), 0, st, a, units);
     else if (t == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q8_0>, grid, dim3(256), 0, st, a, units);
+    else if (t == FATTN_TYPE_Q4_1) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, a, units);
+    else if (t == FATTN_TYPE_Q5_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, a, units);
+    else if (t == FATTN_TYPE_Q5_1) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q5_1>, grid, dim3(256), 0, st, a, units);
     else hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q4_0>, grid, dim3(256), 0, st, a, units);
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
 }

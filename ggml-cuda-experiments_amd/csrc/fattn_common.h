@@ -48,6 +48,43 @@ struct TypeInfo<FATTN_TYPE_Q4_0> {
     static constexpr int block_bytes = kQ4Bytes;
 };
 
+// Q4_1 {f16 d; f16 m; u8 qs[16]}, Q5_0 {f16 d; u8 qh[4]; u8 qs[16]}, Q5_1 {f16 d;
+// f16 m; u8 qh[4]; u8 qs[16]}: element j in the low nibble of qs[j], j + 16 in
+// the high one, bit j of the little-endian u32 qh its fifth bit.
+// x = q d + m (Q4_1, Q5_1) or (q - 16) d (Q5_0)
+constexpr int kQ41Bytes = 20;
+constexpr int kQ50Bytes = 22;
+constexpr int kQ51Bytes = 24;
+template <>
+struct TypeInfo<FATTN_TYPE_Q4_1> {
+    static constexpr int block_elems = QK;
+    static constexpr int block_bytes = kQ41Bytes;
+};
+template <>
+struct TypeInfo<FATTN_TYPE_Q5_0> {
+    static constexpr int block_elems = QK;
+    static constexpr int block_bytes = kQ50Bytes;
+};
+template <>
+struct TypeInfo<FATTN_TYPE_Q5_1> {
+    static constexpr int block_elems = QK;
+    static constexpr int block_bytes = kQ51Bytes;
+};
+
+// The three block types with a fifth bit and / or an affine term: whether T is
+// one of them, whether its blocks hold m / qh, the byte offsets of qh and qs in
+// a block, and the code's zero point (Q5_0: 16)
+__host__ __device__ constexpr bool is_kv_ext(int t) {
+    return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1;
+}
+__host__ __device__ constexpr bool has_min(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_1; }
+__host__ __device__ constexpr bool has_qh(int t) { return t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1; }
+__host__ __device__ constexpr int qh_off(int t) { return t == FATTN_TYPE_Q5_0 ? 2 : 4; }
+__host__ __device__ constexpr int qs_off(int t) {
+    return t == FATTN_TYPE_Q4_1 ? 4 : t == FATTN_TYPE_Q5_0 ? 6 : t == FATTN_TYPE_Q5_1 ? 8 : 2;
+}
+__host__ __device__ constexpr int code_zero(int t) { return t == FATTN_TYPE_Q5_0 ? 16 : 0; }
+
 template <int T, int D>
 constexpr int row_bytes() {
     return D / TypeInfo<T>::block_elems * TypeInfo<T>::block_bytes;
@@ -118,6 +155,41 @@ __device__ __forceinline__ u32x2 read8_at(const uint8_t* smem, uint32_t off) {
     }
     return r;
 }
+
+// 4 / 8 bytes at an LDS offset with off % 4 == MOD4 (0 or 2) known at compile
+// time, by dword reads only (Q5_0's qh and qs sit 2 bytes off a dword in every
+// other block)
+template <int MOD4>
+__device__ __forceinline__ uint32_t read4_mod4(const uint8_t* smem, uint32_t off) {
+    static_assert(MOD4 == 0 || MOD4 == 2, "");
+    if constexpr (MOD4 == 0) {
+        return *(const uint32_t*)(smem + off);
+    } else {
+        const uint32_t w0 = *(const uint32_t*)(smem + off - 2);
+        const uint32_t w1 = *(const uint32_t*)(smem + off + 2);
+        return alignbyte(w1, w0, 2);
+    }
+}
+template <int MOD4>
+__device__ __forceinline__ u32x2 read8_mod4(const uint8_t* smem, uint32_t off) {
+    static_assert(MOD4 == 0 || MOD4 == 2, "");
+    u32x2 r;
+    if constexpr (MOD4 == 0) {
+        r.x = *(const uint32_t*)(smem + off);
+        r.y = *(const uint32_t*)(smem + off + 4);
+    } else {
+        const uint32_t w0 = *(const uint32_t*)(smem + off - 2);
+        const uint32_t w1 = *(const uint32_t*)(smem + off + 2);
+        const uint32_t w2 = *(const uint32_t*)(smem + off + 6);
+        r.x = alignbyte(w1, w0, 2);
+        r.y = alignbyte(w2, w1, 2);
+    }
+    return r;
+}
+
+// Four bits (x < 16) -> bit 4 of the four bytes of a dword: bit k lands at
+// 7k + k = 8k by one multiply (the 16 partial products sit at distinct bits: no carry)
+__device__ __forceinline__ uint32_t bits4_to_bit4(uint32_t x) { return ((x * 0x00204081u) & 0x01010101u) << 4; }
 
 // ---------------------------------------------------------------- wave reductions
 // wave64 replacements for warp_reduce_max / warp_reduce_sum (cuda_info.h:46-85).

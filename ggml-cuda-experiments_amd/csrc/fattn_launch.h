@@ -142,7 +142,7 @@ void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
 int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
     if (pl.kernel == Kernel::SplitLd) {
-        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && (D == 64 || D == 128)) {
+        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && !is_kv_ext(KT) && (D == 64 || D == 128)) {
             auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders>;
             return launch_kernel((const void*)lk, pl, st, ev, [&] {
                 hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, pl.a);
@@ -237,6 +237,10 @@ int launch_mq(const Plan& pl, hipStream_t st, const Events& ev) {
     return pl.a.has_mask ? launch_mq_hm<KT, D, 4, true>(pl, st, ev) : launch_mq_hm<KT, D, 4, false>(pl, st, ev);
 }
 
+// the prefill pre-pass staging a Q4_1 / Q5_0 / Q5_1 cache (pf_prepass_kernel<stage_kt>;
+// instantiated in fattn_launch_kv_ext.hip)
+void launch_prepass_kv_ext(int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa);
+
 template <int KT, int D, bool HM>
 int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     // (max_bias / logit_softcap live: the body with the score transform; the
@@ -273,6 +277,7 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             const int64_t nst = staged ? 2 * (int64_t)pa.per_head * pa.hkv * pa.skv : 0;
             const dim3 g((unsigned)(nst + nfl));
             if (!staged) hipLaunchKernelGGL(pf_prepass_kernel<0>, g, dim3(256), 0, st, pa);
+            else if (is_kv_ext(pl.stage_kt)) launch_prepass_kv_ext(pl.stage_kt, g, st, pa);
             else if (pl.stage_kt == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q8_0>, g, dim3(256), 0, st, pa);
             else hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q4_0>, g, dim3(256), 0, st, pa);
         }
@@ -326,6 +331,22 @@ extern template int launch_mixed<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_mixed<128>(const Plan&, hipStream_t, const Events&);
 extern template int launch_mixed<256>(const Plan&, hipStream_t, const Events&);
 
+// split kernel over a Q4_1 / Q5_0 / Q5_1 cache (K and V of type T; instantiated
+// once per (T, D) in fattn_launch_<type>_d<D>.hip; D = 64, 128, 256)
+template <int T, int D>
+int launch_kv_ext(const Plan& pl, hipStream_t st, const Events& ev) {
+    static_assert(is_kv_ext(T), "");
+    return launch_gran<T, T, D>(pl, st, ev);
+}
+#define FATTN_KV_EXT_EXTERN(T)                                                        \
+    extern template int launch_kv_ext<T, 64>(const Plan&, hipStream_t, const Events&);  \
+    extern template int launch_kv_ext<T, 128>(const Plan&, hipStream_t, const Events&); \
+    extern template int launch_kv_ext<T, 256>(const Plan&, hipStream_t, const Events&);
+FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q4_1)
+FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_0)
+FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_1)
+#undef FATTN_KV_EXT_EXTERN
+
 // every kernel of head dim D (defined here, instantiated once per D in
 // fattn_launch_d<D>.hip)
 template <int D>
@@ -361,6 +382,9 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
         case Kernel::Split:
         case Kernel::SplitLd:
             if constexpr (D == 64 || D == 128 || D == 256) {
+                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q4_1) return launch_kv_ext<FATTN_TYPE_Q4_1, D>(pl, st, ev);
+                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_0) return launch_kv_ext<FATTN_TYPE_Q5_0, D>(pl, st, ev);
+                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_1) return launch_kv_ext<FATTN_TYPE_Q5_1, D>(pl, st, ev);
                 if (pl.kt != pl.vt && pl.vt != VT_F16T) return launch_mixed<D>(pl, st, ev);
             }
             if constexpr (D % QK == 0) {

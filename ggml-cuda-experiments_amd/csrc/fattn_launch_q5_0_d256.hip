@@ -1,0 +1,8 @@
+// fattn_launch_q5_0_d256.hip -- the head-dim-256 split kernels over a Q5_0 K / V
+// cache (fattn_launch.h launch_kv_ext), in their own translation unit so they
+// build in parallel with the others.
+#include "fattn_launch.h"
+
+namespace fattn {
+template int launch_kv_ext<FATTN_TYPE_Q5_0, 256>(const Plan&, hipStream_t, const Events&);
+}  // namespace fattn

@@ -96,7 +96,7 @@ constexpr int kLdsPerCU = 163840;
 template <int KT, int VT, int D>
 int lds_bytes_of(Kernel kern, int waves, int nbuf) {
     constexpr int F16 = FATTN_TYPE_F16;
-    constexpr bool quant = KT != F16 && KT == VT;
+    constexpr bool quant = KT != F16 && KT == VT && !is_kv_ext(KT);  // (Q8_0 / Q4_0: the kernels below the split kernel)
     switch (kern) {
         case Kernel::Split:
         case Kernel::SplitLd: {
@@ -111,7 +111,7 @@ int lds_bytes_of(Kernel kern, int waves, int nbuf) {
                 return waves == 8 ? MQCfg<KT, D, 8, 32>::ldsBytes : MQCfg<KT, D, 4, 16>::ldsBytes;
             break;
         case Kernel::Pf:
-            if constexpr (KT == VT && D != 256) return PfCfg<KT, D>::ldsBytes;
+            if constexpr (KT == VT && D != 256 && !is_kv_ext(KT)) return PfCfg<KT, D>::ldsBytes;
             break;
         case Kernel::Pf4:
             if constexpr (KT == F16 && VT == F16 && D == 128) return Pf4Cfg<D>::ldsBytes;
@@ -151,7 +151,12 @@ inline int lds_bytes(Kernel kern, int kt, int vt, int D, int waves, int nbuf = 0
             default: return with_d(k, std::integral_constant<int, FATTN_TYPE_F16>());
         }
     };
+    // Q4_1 / Q5_0 / Q5_1: K and V of one type, head dims 64 / 128 / 256 (check_views)
+    auto same = [&](auto k) { return D == 80 || D == 96 ? 0 : with_d(k, k); };
     switch (kt) {
+        case FATTN_TYPE_Q4_1: return same(std::integral_constant<int, FATTN_TYPE_Q4_1>());
+        case FATTN_TYPE_Q5_0: return same(std::integral_constant<int, FATTN_TYPE_Q5_0>());
+        case FATTN_TYPE_Q5_1: return same(std::integral_constant<int, FATTN_TYPE_Q5_1>());
         case FATTN_TYPE_Q8_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q8_0>());
         case FATTN_TYPE_Q4_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q4_0>());
         default: return with_v(std::integral_constant<int, FATTN_TYPE_F16>());
@@ -159,7 +164,9 @@ inline int lds_bytes(Kernel kern, int kt, int vt, int D, int waves, int nbuf = 0
 }
 
 // ---------------------------------------------------------------- helpers
-inline bool is_quant(int t) { return t == FATTN_TYPE_Q8_0 || t == FATTN_TYPE_Q4_0; }
+// the ggml block types a cache may hold; is_kv_ext (fattn_common.h) names the
+// three of them only the split kernel and the prefill staging take
+inline bool is_quant(int t) { return t == FATTN_TYPE_Q8_0 || t == FATTN_TYPE_Q4_0 || is_kv_ext(t); }
 
 // bytes of one row of k elements (fattn_row_size)
 inline size_t row_size(int type, int64_t k) {
@@ -168,6 +175,9 @@ inline size_t row_size(int type, int64_t k) {
         case FATTN_TYPE_F16: return (size_t)k * 2;
         case FATTN_TYPE_Q8_0: return k % QK ? 0 : (size_t)(k / QK) * kQ8Bytes;
         case FATTN_TYPE_Q4_0: return k % QK ? 0 : (size_t)(k / QK) * kQ4Bytes;
+        case FATTN_TYPE_Q4_1: return k % QK ? 0 : (size_t)(k / QK) * kQ41Bytes;
+        case FATTN_TYPE_Q5_0: return k % QK ? 0 : (size_t)(k / QK) * kQ50Bytes;
+        case FATTN_TYPE_Q5_1: return k % QK ? 0 : (size_t)(k / QK) * kQ51Bytes;
         default: return 0;
     }
 }
@@ -238,6 +248,12 @@ inline int check_views(const fattn_params* p, Views& w) {
     // the split kernel, head dims 64 / 128 / 256
     w.mixed = k.type != v.type;
     if (w.mixed && D != 64 && D != 128 && D != 256) return FATTN_ERR_UNSUPPORTED_TYPE;
+    // Q4_1 / Q5_0 / Q5_1: K and V of one type, not at D = 96 (Q5_0 rows of 66 B
+    // are no whole number of dwords; the three share one rule)
+    if (is_kv_ext(k.type) || is_kv_ext(v.type)) {
+        if (w.mixed) return FATTN_ERR_UNSUPPORTED_TYPE;
+        if (D == 96) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
+    }
     if ((uintptr_t)q.data % 16 || q.nb[1] % 16 || q.nb[2] % 16 || q.nb[3] % 16) return FATTN_ERR_ALIGNMENT;
     // ggml's op_params[1], [2] and the global head numbering of the slopes
     if (!std::isfinite(p->max_bias) || p->max_bias < 0.0f) return FATTN_ERR_INVALID_ARG;
@@ -377,7 +393,10 @@ inline void choose_kernel(const fattn_params* p, const Views& w, const Options& 
     const int64_t rows = NQ * a.rk2;  // packed rows per kv head
     const bool heads_ok = rows >= 32 && a.rk2 <= 64;
     const bool packed_ok = !o[FATTN_OPT_MQ_DISABLE] && !w.mixed && w.g16 && heads_ok;
-    const bool quant_ok = packed_ok && is_quant(kt);
+    // (Q4_1 / Q5_0 / Q5_1: none of the multi-query and batched-decode kernels -- their
+    // shapes fall to the split kernel -- and prefill only through the f16 staging)
+    const bool quant_ok = packed_ok && is_quant(kt) && !is_kv_ext(kt);
+    const bool stage_ok = packed_ok && is_kv_ext(kt) && o[FATTN_OPT_PF_STAGE] != 1 && N * D * 2 <= kSpanMax;
     const bool mq_ok = quant_ok && (D == 64 || D == 128 || D == 256);
     // the same packing for f16 K/V rows (not transposed V): the prefill and
     // batched-decode kernels fill their f16 images by LDS-DMA straight from the rows
@@ -402,7 +421,7 @@ inline void choose_kernel(const fattn_params* p, const Views& w, const Options& 
     // (D = 80's padding dims are DMA'd from 0x80000000 past the row offset,
     // outside the descriptor only while the spans stay within 2 GiB: fattn_pf.h)
     const bool d80_ok = f16_ok && w.k_span <= (int64_t)0x80000000 && w.v_span <= (int64_t)0x80000000;
-    const bool pf = (quant_ok || f16_ok) && opt_pf != 1 && (D == 64 || D == 96 || D == 128 || (D == 80 && d80_ok)) &&
+    const bool pf = (quant_ok || f16_ok || stage_ok) && opt_pf != 1 && (D == 64 || D == 96 || D == 128 || (D == 80 && d80_ok)) &&
                     p->kv_chunk <= 0 && N % kPfKeys == 0 && p->scale > 0.0f &&
                     (opt_pf == 2 || Hkv * S * ((rows + kPfRows - 1) / kPfRows) >= pl.cus);
     // batched decode (config 5: 64 query rows per kv head): 64-row workgroups
@@ -457,7 +476,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     SplitArgs& a = pl.a;
     auto lds = [&](int nbuf, int nwv) { return lds_bytes(Kernel::Split, pl.kt, pl.vt, pl.D, nwv, nbuf); };
     const int64_t steps = (N + kStep - 1) / kStep;
-    const int wps = (pl.kt == FATTN_TYPE_F16 || pl.gran == 4 || pl.D == 256) ? 2 : 4;  // __launch_bounds__ waves/SIMD
+    const int wps = (pl.kt == FATTN_TYPE_F16 || pl.gran == 4 || pl.D == 256 || is_kv_ext(pl.kt)) ? 2 : 4;  // __launch_bounds__ waves/SIMD
     const int rv_max = std::min<int64_t>(kRows, (int64_t)a.R * std::min<int64_t>(a.QPT, NQ));
     const int64_t total = steps * Y * S;
     const bool fused_merge = o[FATTN_OPT_SPLIT_MERGE] != 0;
@@ -529,7 +548,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     // whole chunk fits the LDS (every step resident), 16-B rows, D = 64 / 128,
     // one K / V type; 4 loader waves issue it all up front
     if (o[FATTN_OPT_SPLIT_LOADERS] == 2 && pl.gran == 16 && a.wave_merge == 2 && nwv == 8 && spw >= 2 && spw <= 3 &&
-        (pl.D == 64 || pl.D == 128) && pl.kt == pl.vt && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
+        (pl.D == 64 || pl.D == 128) && pl.kt == pl.vt && !is_kv_ext(pl.kt) && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
         lds(spw, nwv) + kSplitLdFlagBytes <= kLdsPerCU) {
         pl.kernel = Kernel::SplitLd;
         nbuf = spw;

@@ -11,7 +11,7 @@
 //    (GQA broadcast ik2 = iq2 / (ne02/ne12), flash-llama.h:128-140), so a
 //    32q/8kv decode packs 4 heads into one tile instead of re-reading K/V 4x.
 //  * Each wave owns a contiguous slice of the chunk and streams it in steps of
-//    32 positions.  The raw ggml rows (f16 / Q8_0 / Q4_0 blocks, exactly as in
+//    32 positions.  The raw ggml rows (f16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 blocks, exactly as in
 //    HBM) plus the step's mask rows are copied HBM -> LDS with
 //    global_load_lds_dwordx4 (fully coalesced 1 KiB per wave instruction; a
 //    dword-granular variant serves arbitrary ggml row strides), NBUF steps in
@@ -517,6 +517,28 @@ __device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs
 }
 
 // ---------------------------------------------------------------- block scales
+// Quantised V: the A operand of P.V is the exact integer code plus the f16
+// magic number 1024 (0x6400 | code), the block scale folded into P; v_code_off
+// is what the epilogue takes off per unit of corr[b] = sum P d_b: 1024 plus the
+// code's zero point (Q8_0: 128 by the sign flip, Q4_0: 8, Q5_0: 16) or, for the
+// unsigned codes of Q4_1 / Q5_1, their centre v_code_centre (8 / 16).  The
+// centre is not in the format: P d is rounded to f16, so the product sum carries
+// sum eps_r P_r d_r (q_r - c) -- half the error with c at the middle of the code
+// range than with c = 0 -- and c sum P d comes back exactly through the second
+// accumulator (q d + m = (q - c) d + (m + c d))
+template <int VT>
+constexpr int v_code_centre() { return VT == FATTN_TYPE_Q4_1 ? 8 : VT == FATTN_TYPE_Q5_1 ? 16 : 0; }
+template <int VT>
+constexpr float v_code_off() {
+    return VT == FATTN_TYPE_Q8_0 ? 1152.0f : VT == FATTN_TYPE_Q4_0 ? 1032.0f : VT == FATTN_TYPE_Q5_0 ? 1040.0f
+           : 1024.0f + (float)v_code_centre<VT>();
+}
+// per-block f32 accumulators a wave carries beside O: corr[b], and for Q4_1 /
+// Q5_1 behind them sum P (m_b + c d_b) (plain P, not the rounded P d: exact f16
+// products summed in f32), which the epilogue adds to the block's 32 columns
+template <int VT, int D>
+constexpr int corr_len() { return (D + QK - 1) / QK * (has_min(VT) ? 2 : 1); }
+
 // The f16 scale of block b of a raw ggml row sits at byte BB*b.  row_scales()
 // fetches the dwords holding all of a row's scales (2 x ds_read2_b32 for 4
 // blocks); scale_bits() extracts block b's 16 bits.
@@ -627,6 +649,49 @@ __device__ __forceinline__ f16x8 k_operand(const uint8_t* kb, int row, int g, in
         r.s01 = h0; r.s23 = h1; r.s45 = h2; r.s67 = h3;
         return r;
     }
+}
+
+// ... for Q4_1 / Q5_0 / Q5_1 rows: the 5-bit (4-bit) code from the nibble and
+// the qh bit as the exact f16 1024 + code, minus 1024 + zero point (exact);
+// Q5_0: times d, one f16 rounding of the exact product; Q4_1 / Q5_1: one packed
+// f16 fma q d + m, one rounding of the exact sum.  Rows are whole dwords, so
+// within a row d (and m) share the dword at BB b (Q5_0: BB b & ~3, d in either
+// half), qh and qs sit at a compile-time offset modulo 4 (b is unrolled)
+template <int KT, int D>
+__device__ __forceinline__ f16x8 k_operand_ext(const uint8_t* kb, int row, int g, int b) {
+    constexpr int BB = TypeInfo<KT>::block_bytes;
+    constexpr int RB = row_bytes<KT, D>();
+    static_assert(RB % 4 == 0, "rows of whole dwords");
+    const uint32_t base = row * RB;
+    const uint32_t dm = *(const uint32_t*)(kb + base + ((BB * b) & ~3));
+    const uint32_t qo = BB * b + qs_off(KT);
+    const u32x2 raw = (qo & 2) ? read8_mod4<2>(kb, base + qo + 8 * (g & 1)) : read8_mod4<0>(kb, base + qo + 8 * (g & 1));
+    const uint32_t sh = (g >> 1) * 4;
+    uint32_t cx = (raw.x >> sh) & 0x0F0F0F0Fu, cy = (raw.y >> sh) & 0x0F0F0F0Fu;
+    if constexpr (has_qh(KT)) {
+        const uint32_t ho = BB * b + qh_off(KT);
+        const uint32_t qh = (ho & 2) ? read4_mod4<2>(kb, base + ho) : read4_mod4<0>(kb, base + ho);
+        const uint32_t q8 = (qh >> (8 * g)) & 0xFFu;  // the fifth bits of elements 8g .. 8g + 7
+        cx |= bits4_to_bit4(q8 & 0xFu);
+        cy |= bits4_to_bit4(q8 >> 4);
+    }
+    constexpr f16 zo = (f16)(-1024.0f - (float)code_zero(KT));
+    const f16x2 off = {zo, zo};
+    f16x2 h0 = as_h2(perm_b32(0x64646464u, cx, 0x04010400u)) + off, h1 = as_h2(perm_b32(0x64646464u, cx, 0x04030402u)) + off;
+    f16x2 h2 = as_h2(perm_b32(0x64646464u, cy, 0x04010400u)) + off, h3 = as_h2(perm_b32(0x64646464u, cy, 0x04030402u)) + off;
+    if constexpr (has_min(KT)) {
+        const f16x2 d = as_h2(perm_b32(dm, dm, 0x01000100u)), m = as_h2(perm_b32(dm, dm, 0x03020302u));
+        h0 = __builtin_elementwise_fma(h0, d, m);
+        h1 = __builtin_elementwise_fma(h1, d, m);
+        h2 = __builtin_elementwise_fma(h2, d, m);
+        h3 = __builtin_elementwise_fma(h3, d, m);
+    } else {
+        const f16x2 d = as_h2(perm_b32(dm, dm, ((BB * b) & 2) ? 0x03020302u : 0x01000100u));
+        h0 *= d; h1 *= d; h2 *= d; h3 *= d;
+    }
+    f16x8 r;
+    r.s01 = h0; r.s23 = h1; r.s45 = h2; r.s67 = h3;
+    return r;
 }
 
 // V operand (A of O^T = V^T.P^T) for column group c (16 columns):
@@ -1173,7 +1238,7 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
 // alias step buffers, so wait for every wave before writing them.
 template <int KT, int VT, int D, int NW, int EPI>
 __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D / 16], float m_run, float l_run,
-                                               float (&corr)[(D + QK - 1) / QK], int wave, int lane, int qt, int hs, int ik2,
+                                               float (&corr)[corr_len<VT, D>()], int wave, int lane, int qt, int hs, int ik2,
                                                int iq3, int y, int chunk, uint8_t* smem, int region, bool active,
                                                bool sync_first) {
     using C = SplitCfg<KT, VT, D>;
@@ -1182,7 +1247,7 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     constexpr float kNegInf = -__builtin_inff();
     constexpr bool kVQ8 = C::VTT == FATTN_TYPE_Q8_0;
     constexpr bool kVQ = C::VTT != FATTN_TYPE_F16;
-    constexpr float kVOff = kVQ8 ? 1152.0f : 1032.0f;
+    constexpr float kVOff = v_code_off<C::VTT>();
     const int g = lane >> 4;
     const int m = lane & 15;
     // split_step keeps the reference max in natural units; the merges work in log2
@@ -1195,6 +1260,11 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
             const float cb = kVOff * grp4_sum(corr[b]);
             o[2 * b] -= cb;
             o[2 * b + 1] -= cb;
+            if constexpr (has_min(C::VTT)) {  // + sum P (m_b + c d_b), the affine term of the block's 32 columns
+                const float mb = grp4_sum(corr[NB + b]);
+                o[2 * b] += mb;
+                o[2 * b + 1] += mb;
+            }
         }
     }
     if constexpr (EPI == 1) {
@@ -1397,7 +1467,7 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
 template <int KT, int VT, int D, bool HM, bool XF, typename WaitV>
 __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mrow,
                                            float slope, int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
-                                           f32x4 (&o)[D / 16], float (&corr)[(D + QK - 1) / QK], WaitV&& wait_v) {
+                                           f32x4 (&o)[D / 16], float (&corr)[corr_len<VT, D>()], WaitV&& wait_v) {
     using C = SplitCfg<KT, VT, D>;
     constexpr int NB = (D + QK - 1) / QK;  // k-steps of S^T (D = 80: the last one half zero)
     constexpr int NC = D / 16;
@@ -1417,6 +1487,9 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
         if constexpr (KT == FATTN_TYPE_F16) {
 #pragma unroll
             for (int b = 0; b < NB; b++) st[t] = mfma16(k_operand<KT, D>(kb, 16 * t + i16, g, b, 0), qop[b], st[t]);
+        } else if constexpr (is_kv_ext(KT)) {
+#pragma unroll
+            for (int b = 0; b < NB; b++) st[t] = mfma16(k_operand_ext<KT, D>(kb, 16 * t + i16, g, b), qop[b], st[t]);
         } else {
             const RowScales<KT, D> ks = row_scales<KT, D>(kb + (16 * t + i16) * C::rowK);
 #pragma unroll
@@ -1480,7 +1553,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
             for (int c = 0; c < NC; c++) o[c] *= alpha;
             if constexpr (kVQ) {
 #pragma unroll
-                for (int b = 0; b < NB; b++) corr[b] *= alpha;
+                for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] *= alpha;
             }
         }
         m_run = m_new;
@@ -1551,6 +1624,58 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
                 }
                 o[2 * b] = mfma16(__builtin_bit_cast(f16x8, ae), pbd, o[2 * b]);
                 o[2 * b + 1] = mfma16(__builtin_bit_cast(f16x8, ao), pbd, o[2 * b + 1]);
+            } else if constexpr (is_kv_ext(C::VTT)) {
+                // Q4_1 / Q5_0 / Q5_1: byte i of qs carries column i (low nibble) and 16 + i
+                // (high nibble), bits i and 16 + i of the row's qh their fifth bits
+                constexpr int VTT = C::VTT;
+                if constexpr (has_min(VTT)) {
+                    // the second accumulator sum P (m_b + c d_b): m in the high halves of the
+                    // d | m dwords; c d is exact in f16 (c a power of two)
+                    const f16x2 m01 = as_h2(perm_b32(sw[1], sw[0], 0x07060302u)), m23 = as_h2(perm_b32(sw[3], sw[2], 0x07060302u));
+                    const f16x2 m45 = as_h2(perm_b32(sw[5], sw[4], 0x07060302u)), m67 = as_h2(perm_b32(sw[7], sw[6], 0x07060302u));
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s01, m01, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s23, m23, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s45, m45, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s67, m67, corr[NB + b], false);
+                    constexpr f16 cc = (f16)(float)v_code_centre<VTT>();
+                    const f16x2 c2 = {cc, cc};
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s01, d01 * c2, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s23, d23 * c2, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s45, d45 * c2, corr[NB + b], false);
+                    corr[NB + b] = __builtin_amdgcn_fdot2(pb.s67, d67 * c2, corr[NB + b], false);
+                }
+                const uint8_t* cp = vb + b * BB + qs_off(VTT) + i16;
+                uint32_t w[8], hb[8];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    w[r] = cp[(rA + r) * C::rowV];
+                    w[4 + r] = cp[(rB + r) * C::rowV];
+                }
+                if constexpr (has_qh(VTT)) {
+                    // {bit i16 at bit 0, bit 16 + i16 at bit 16} of each row's qh
+                    const int HO = BB * b + qh_off(VTT);  // (b is unrolled: a constant)
+#pragma unroll
+                    for (int r = 0; r < 8; r++) {
+                        const uint8_t* hp = vb + ((r < 4 ? rA : rB - 4) + r) * C::rowV + HO;
+                        uint32_t qh;
+                        if (HO % 4 == 0) qh = *(const uint32_t*)hp;
+                        else qh = (uint32_t)*(const uint16_t*)hp | ((uint32_t)*(const uint16_t*)(hp + 2) << 16);
+                        hb[r] = (qh >> i16) & 0x00010001u;
+                    }
+                }
+                u32x4 al, ah;  // f16 pairs 1024 + code (exact)
+#pragma unroll
+                for (int pr = 0; pr < 4; pr++) {
+                    const uint32_t x = w[2 * pr] | (w[2 * pr + 1] << 16);
+                    al[pr] = (x & 0x000F000Fu) | 0x64006400u;
+                    ah[pr] = ((x >> 4) & 0x000F000Fu) | 0x64006400u;
+                    if constexpr (has_qh(VTT)) {
+                        al[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c040c00u) << 4;
+                        ah[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c060c02u) << 4;
+                    }
+                }
+                o[2 * b] = mfma16(__builtin_bit_cast(f16x8, al), pbd, o[2 * b]);
+                o[2 * b + 1] = mfma16(__builtin_bit_cast(f16x8, ah), pbd, o[2 * b + 1]);
             } else {  // Q4_0: byte i carries column i (low nibble) and 16+i (high nibble)
                 const uint8_t* cp = vb + b * BB + 2 + i16;
                 uint32_t w[8];
@@ -1575,9 +1700,10 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
 }
 
 // waves per SIMD the split kernel's register budget allows (__launch_bounds__)
+// (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4)
 template <int KT, int D, int GRAN>
 constexpr int split_waves_per_simd() {
-    return (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256) ? 2 : 4;
+    return (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4;
 }
 
 // NWV waves per workgroup (4, 8 or 16), each streaming its own slice of the
@@ -1588,7 +1714,7 @@ constexpr int split_waves_per_simd() {
 // XF (split_step): instantiated for NWV = 4 only; the planner sizes a launch
 // with max_bias / logit_softcap live for 4 waves (size_split).
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false>
-__global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256) ? 2 : 4) void fattn_split_kernel(
+__global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4) void fattn_split_kernel(
     const SplitArgs a) {
     using C = SplitCfg<KT, VT, D>;
     using P = StepPlan<KT, VT, D, GRAN>;
@@ -1598,8 +1724,9 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     constexpr int NC = D / 16;   // 16-wide output column groups (MFMA tiles of O^T)
     constexpr float kNegInf = -__builtin_inff();
     // quantised V: the A operand is the exact integer code plus the magic-number
-    // offset (1152 for Q8_0, 1032 for Q4_0) with the block scale folded into P;
-    // corr[b] accumulates sum(P * d_b) so the offset comes off once in the epilogue
+    // offset (v_code_off: 1152 for Q8_0, 1032 for Q4_0, ...) with the block scale folded
+    // into P; corr[b] accumulates sum(P * d_b) so the offset comes off once in the
+    // epilogue (Q4_1 / Q5_1: corr[NB + b] accumulates sum(P * (m_b + c d_b)), added there)
 
     const int lane = threadIdx.x & 63;
     // wave-uniform by construction; readfirstlane lets the compiler see it, so the
@@ -1757,9 +1884,9 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     f32x4 o[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) o[c] = f32x4{0, 0, 0, 0};
-    float corr[NB];
+    float corr[corr_len<VT, D>()];
 #pragma unroll
-    for (int b = 0; b < NB; b++) corr[b] = 0.0f;
+    for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] = 0.0f;
 
     int cur = 0;  // buffer of step s
     for (int s = 0; s < nsteps; s++) {
@@ -1957,9 +2084,9 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
     f32x4 o[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) o[c] = f32x4{0, 0, 0, 0};
-    float corr[NB];
+    float corr[corr_len<VT, D>()];
 #pragma unroll
-    for (int b = 0; b < NB; b++) corr[b] = 0.0f;
+    for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] = 0.0f;
     for (int s = 0; s < nsteps; s++) {
         const uint32_t* f = flags + (wave * spw + s) * 2;
         if (s == 0) wait_steps_plus<NI, P::NIV>(0);  // own DMA: K + mask landed

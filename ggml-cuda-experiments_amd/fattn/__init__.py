@@ -21,8 +21,10 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", os.environ.get("
 
 # ggml_type numbering (include/fattn.h)
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0 = 0, 1, 2, 8
-TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0}
-BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18}
+TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
+TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
+              "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1}
+BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18, TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
 
 FATTN_OK = 0
 ERRORS = {
@@ -295,7 +297,8 @@ def _tptr(t) -> int:
 
 
 def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "head") -> View:
-    """View of a KV cache held in a byte (or f16) torch tensor.
+    """View of a KV cache held in a byte (or f16) torch tensor; typ: TYPE_F16 or a
+    block type (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1).
 
     layout "head": [S][Hkv][N][row]   (per-head contiguous; reference decode layout,
                    src/flash_row_float.h:19,58)
@@ -390,7 +393,7 @@ def quantize(x, typ: int, stream=None):
 
 
 def cpy(src: View, dst: View, stream=None):
-    """GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 into a strided view (the KV-cache
+    """GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view (the KV-cache
     write, include/fattn.h fattn_cpy); src/dst are ggml views of device memory."""
     s, d = src.c(), dst.c()
     _check(lib().fattn_cpy(C.byref(s), C.byref(d), _stream(stream)), "fattn_cpy")

@@ -19,7 +19,7 @@
 //   --n-warps N          accepted for compatibility (kernel_test.h:9-13); the gfx950
 //                        kernels pick their own wave counts
 //   --kv-size N          KV length, min 256 on the GPU path (kernel_test.h:14-18)
-//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0
+//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0 | q4_1 | q5_0 | q5_1
 //   --cpu-only           the CPU reference alone (BASELINE config 1: no GPU is touched,
 //                        any kv_size); with --dump FILE its f32 output is written raw
 //   --head-dim D --heads H --kv-heads Hkv --iters I --tol T
@@ -210,6 +210,42 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
     for (auto& th : pool) th.join();
 }
 
+const char* type_name(int t) {
+    return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
+           : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : "f16";
+}
+
+bool is_kv_ext(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1; }
+
+// ggml's dequantize_row_q4_1 / _q5_0 / _q5_1 in plain C++ (this file builds with
+// -ffp-contract=off: every operation rounded on its own): `rows` rows of D values
+// from blocks {f16 d; [f16 m;] [u8 qh[4];] u8 qs[16]}
+void dequant_host(int type, const uint8_t* src, float* dst, int D, int64_t rows) {
+    const bool has_m = type != FATTN_TYPE_Q5_0, has_qh = type != FATTN_TYPE_Q4_1;
+    const int bb = 2 + (has_m ? 2 : 0) + (has_qh ? 4 : 0) + 16;
+    const int64_t nblk = rows * (D / 32);
+    for (int64_t i = 0; i < nblk; i++) {
+        const uint8_t* b = src + i * bb;
+        const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
+        const float m = has_m ? h2f((uint16_t)(b[2] | (b[3] << 8))) : 0.0f;
+        const uint8_t* hp = b + (has_m ? 4 : 2);
+        const uint32_t qh = has_qh ? (uint32_t)hp[0] | ((uint32_t)hp[1] << 8) | ((uint32_t)hp[2] << 16) | ((uint32_t)hp[3] << 24) : 0u;
+        const uint8_t* qs = b + bb - 16;
+        float* y = dst + i * 32;
+        for (int j = 0; j < 16; j++) {
+            const int q0 = (qs[j] & 0x0F) | (int)(((qh >> j) & 1u) << 4);
+            const int q1 = (qs[j] >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4);
+            if (has_m) {
+                y[j] = (float)q0 * d + m;
+                y[j + 16] = (float)q1 * d + m;
+            } else {
+                y[j] = (float)(q0 - 16) * d;
+                y[j + 16] = (float)(q1 - 16) * d;
+            }
+        }
+    }
+}
+
 void print_array(const char* name, const float* a, int count) {  // utils.h:63-71
     printf("---------------- %s ------------------\n", name);
     for (int i = 0; i < count; i++) printf("%0.4ff, ", a[i]);
@@ -220,6 +256,9 @@ int parse_type(const std::string& s) {
     if (s == "f16") return FATTN_TYPE_F16;
     if (s == "q8_0") return FATTN_TYPE_Q8_0;
     if (s == "q4_0") return FATTN_TYPE_Q4_0;
+    if (s == "q4_1") return FATTN_TYPE_Q4_1;
+    if (s == "q5_0") return FATTN_TYPE_Q5_0;
+    if (s == "q5_1") return FATTN_TYPE_Q5_1;
     fprintf(stderr, "unknown --kv-type %s\n", s.c_str());
     exit(2);
 }
@@ -369,9 +408,9 @@ int main(int argc, const char* argv[]) {
            prop.multiProcessorCount, prop.sharedMemPerBlock / 1024, prop.totalGlobalMem >> 20,
            ngpu > 1 ? " (x --ngpu)" : "");
 
-    // K/V values as the kernels see them: f16 rounding on the host, or Q8_0 /
-    // Q4_0 quantised on device 0 (fattn_quantize) and dequantised back for the
-    // CPU reference (fattn_dequantize)
+    // K/V values as the kernels see them: f16 rounding on the host, or
+    // quantised on device 0 (fattn_quantize) and dequantised back for the CPU
+    // reference (fattn_dequantize; Q4_1 / Q5_0 / Q5_1: dequant_host)
     const size_t rb = fattn_row_size(kv_type, D);
     std::vector<float> kref = key, vref = value;
     std::vector<uint8_t> kbytes(rb * N * Hkv), vbytes(rb * N * Hkv);
@@ -413,6 +452,10 @@ int main(int argc, const char* argv[]) {
             HIP_CHECK(hipMemcpyAsync(kbytes.data(), d_kq, kbytes.size(), hipMemcpyDeviceToHost, st0));
             HIP_CHECK(hipMemcpyAsync(vbytes.data(), d_vq, vbytes.size(), hipMemcpyDeviceToHost, st0));
             HIP_CHECK(hipStreamSynchronize(st0));
+            if (is_kv_ext(kv_type)) {  // (the reference's values from the blocks, on the host)
+                dequant_host(kv_type, kbytes.data(), kref.data(), D, (int64_t)N * Hkv);
+                dequant_host(kv_type, vbytes.data(), vref.data(), D, (int64_t)N * Hkv);
+            }
             HIP_CHECK(hipFree(d_kf));
             HIP_CHECK(hipFree(d_vf));
             HIP_CHECK(hipFree(d_kq));
@@ -502,7 +545,7 @@ int main(int argc, const char* argv[]) {
     }
     if (parallel_kv && kv_type != FATTN_TYPE_F16) {
         fprintf(stderr, "the flash_attn_row branch takes f16 K/V (use --no-kv-parallel for %s)\n",
-                kv_type == FATTN_TYPE_Q8_0 ? "q8_0" : "q4_0");
+                type_name(kv_type));
         return 2;
     }
     std::vector<ncclComm_t> comms(G);

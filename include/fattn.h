@@ -12,7 +12,8 @@
  *                           src/flash-matrix.cu:198-206).  Same argument meaning
  *                           (q/k/v/mask as ggml ne/nb views, f32 dst in the
  *                           permuted [seq][n_q][H][D] layout of flash-llama.h:434),
- *                           extended with K/V element types F16 / Q8_0 / Q4_0.
+ *                           extended with K/V element types F16 / Q8_0 / Q4_0 /
+ *                           Q4_1 / Q5_0 / Q5_1.
  *   fattn_ext_sinks()    fattn_ext() with upstream ggml's src[4], the per-head attention
  *                           sinks (absent from the reference; see its comment below).
  *   fattn_ext_f16_launch()  the positional argument list of flash-llama.h:7-32,
@@ -28,7 +29,7 @@
  *                           scratch exactly like d_temporal (kernel_test.h:155).
  *   fattn_workspace_size()  the size of that scratch (kernel_test.h:155 computes
  *                           it inline).
- *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 row conversion on the
+ *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 row conversion on the
  *                           GPU (bit-exact with upstream ggml; absent from the
  *                           reference) -- the KV-cache write side.
  *
@@ -60,6 +61,9 @@ enum fattn_type {
     FATTN_TYPE_F32 = 0,
     FATTN_TYPE_F16 = 1,
     FATTN_TYPE_Q4_0 = 2,
+    FATTN_TYPE_Q4_1 = 3,
+    FATTN_TYPE_Q5_0 = 6,
+    FATTN_TYPE_Q5_1 = 7,
     FATTN_TYPE_Q8_0 = 8,
 };
 
@@ -67,7 +71,7 @@ enum fattn_status {
     FATTN_OK = 0,
     FATTN_ERR_INVALID_ARG = -1,     /* NULL pointer, bad shape, ne not divisible */
     FATTN_ERR_UNSUPPORTED_TYPE = -2,
-    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96, 128 or 256 */
+    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 */
     FATTN_ERR_BAD_STRIDE = -4,       /* layout the kernels cannot address */
     FATTN_ERR_WORKSPACE = -5,        /* workspace too small */
     FATTN_ERR_LAUNCH = -6,           /* HIP launch failure */
@@ -85,11 +89,20 @@ typedef struct fattn_tensor {
 
 /* GGML_OP_FLASH_ATTN_EXT:
  *   q    f32  ne = [D, n_q, H, S]        (any nb with nb[0] == 4)
- *   k    F16/Q8_0/Q4_0  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
- *   v    F16/Q8_0/Q4_0  ne = [D, N, Hkv, Skv]; rows contiguous, or for F16 only
+ *   k    F16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
+ *   v    the same types  ne = [D, N, Hkv, Skv]; rows contiguous, or for F16 only
  *        transposed (nb[1] == 2, nb[0] == N*2 style strides).  v's type may
  *        differ from k's (llama.cpp's separate K / V cache types) at D = 64,
- *        128 and 256: the split-KV kernel takes every such pair
+ *        128 and 256: the split-KV kernel takes every such pair of F16 / Q8_0 /
+ *        Q4_0.  Q4_1 / Q5_0 / Q5_1 (the other classic 32-element blocks of
+ *        llama.cpp's --cache-type-k/-v: 20 / 22 / 24 bytes, {d, [m], [qh], qs}):
+ *        K and V of one such type, at D = 64, 128 and 256.  Every decode shape
+ *        runs the split-KV kernel over the raw blocks; prefill shapes at D = 64 /
+ *        128 stage the rows to f16 first (as Q8_0 / Q4_0 do), at D = 256 they run
+ *        the split-KV kernel.  Not supported: D = 96 with one of the three
+ *        (FATTN_ERR_UNSUPPORTED_HEAD_DIM: Q5_0 rows would be 66 bytes, no whole
+ *        number of dwords) and a pair that mixes one of them with any other
+ *        type (FATTN_ERR_UNSUPPORTED_TYPE)
  *   mask F16 ne = [N', rows >= n_q] with N' >= N rounded up to even (ggml pads
  *        mask rows to GGML_KQ_MASK_PAD), 4-byte aligned rows; row = query
  *        index; or data == NULL for no mask.  ne[2] and ne[3] are plane counts,
@@ -221,17 +234,17 @@ int fattn_row(const float* query, const void* key, const void* value, const void
               int head_stride, int r_kv_heads, void* stream);
 
 /* ggml row conversions on the GPU (n_rows rows of k elements each, contiguous).
- * dequantize: Q8_0/Q4_0/F16 -> f32 (bit-exact with ggml dequantize_row_*).
- * quantize:   f32 -> Q8_0/Q4_0 (bit-exact with ggml quantize_row_*_ref). */
+ * dequantize: Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/F16 -> f32 (bit-exact with ggml dequantize_row_*).
+ * quantize:   f32 -> Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 (bit-exact with ggml quantize_row_*_ref). */
 int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n_rows, void* stream);
 int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_rows, void* stream);
 
-/* GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 into a strided view: the KV-cache write
+/* GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view: the KV-cache write
  * (quantize-on-write; upstream ggml cpy_f32_q /
  * cpy_f32_f16, absent from the reference).  src: f32, nb[0] = 4; dst: same ne,
  * nb[0] = element / block bytes, any nb[1..3] -- e.g. one token's Hkv rows
  * written into a [Hkv][N][row] cache (nb1 = N * row bytes) or a [N][Hkv][row]
- * cache (nb1 = row bytes).  ne[0] a multiple of 32 for Q8_0 / Q4_0.  Values
+ * cache (nb1 = row bytes).  ne[0] a multiple of 32 for the block types.  Values
  * bit-exact with ggml quantize_row_*_ref / f16 round-to-nearest-even. */
 int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
 
