@@ -22,6 +22,7 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", os.environ.get("
 # ggml_type numbering (include/fattn.h)
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0 = 0, 1, 2, 8
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
+TYPE_I32, TYPE_I64 = 26, 27   # index tensors of set_rows only
 TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
               "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1}
 BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18, TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
@@ -36,7 +37,7 @@ ERRORS = {
 EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
-    "fattn_describe", "fattn_cpy", "fattn_ext_sinks",
+    "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows",
 )
 OPT_MQ_ROWS_PER_WAVE = 1
 OPT_MQ_DISABLE = 2
@@ -137,6 +138,8 @@ def lib() -> C.CDLL:
         L.fattn_version.restype = C.c_char_p
         L.fattn_cpy.restype = C.c_int
         L.fattn_cpy.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp]
+        L.fattn_set_rows.restype = C.c_int
+        L.fattn_set_rows.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp]
         L.fattn_describe.restype = C.c_int
         L.fattn_describe.argtypes = [C.POINTER(FattnParams), C.c_char_p, sz]
         _lib = L
@@ -397,6 +400,18 @@ def cpy(src: View, dst: View, stream=None):
     write, include/fattn.h fattn_cpy); src/dst are ggml views of device memory."""
     s, d = src.c(), dst.c()
     _check(lib().fattn_cpy(C.byref(s), C.byref(d), _stream(stream)), "fattn_cpy")
+
+
+def set_rows(src: View, idx: View, dst: View, stream=None):
+    """GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: the KV-cache write by slot
+    index (include/fattn.h fattn_set_rows).  src: f32 ne = [ne0, nr, ne2, ne3];
+    idx: TYPE_I64 or TYPE_I32 ne = [nr, ne11, ne12, 1] in device memory; dst: the
+    cache, ne = [ne0, n_slots, ne2, ne3].  Row i of plane (i2, i3) is converted
+    into slot idx[i, i2 % ne11, i3 % ne12]; a slot outside [0, n_slots) writes
+    nothing.  The slots are read on the device, so a captured graph replays with
+    whatever the index tensor then holds."""
+    s, i, d = src.c(), idx.c(), dst.c()
+    _check(lib().fattn_set_rows(C.byref(s), C.byref(i), C.byref(d), _stream(stream)), "fattn_set_rows")
 
 
 def dequantize(blocks, typ: int, k: int, stream=None):

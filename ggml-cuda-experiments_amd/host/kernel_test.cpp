@@ -42,6 +42,11 @@
 //                        gets the raw extra logit BASE + 0.25 * (h % 8) in its softmax
 //                        denominator (the global head index under --ngpu: device g passes
 //                        its own slice); the CPU reference applies the same
+//   --set-rows           build the K / V caches with fattn_set_rows (GGML_OP_SET_ROWS) from the
+//                        f32 K / V instead of fattn_quantize / the host's f16 rounding: row n
+//                        goes to slot perm[n] of a seeded permutation, and the CPU reference
+//                        sees K, V and the mask columns in slot order (Q has no KV axis); implies
+//                        --no-kv-parallel (flash_attn_row's transposed V is no row write)
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -281,7 +286,7 @@ int main(int argc, const char* argv[]) {
     std::string mask_kind = "random";
     const char* dump = nullptr;
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
-    bool use_sinks = false;
+    bool use_sinks = false, set_rows = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -295,6 +300,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--n-warps") num_warps = atoi(next());
         else if (a == "--kv-size") kv_size = atoi(next());
         else if (a == "--cpu-only") cpu_only = true;
+        else if (a == "--set-rows") set_rows = true;
         else if (a == "--dump") dump = next();
         else if (a == "--kv-type") kv_type = parse_type(next());
         else if (a == "--head-dim") head_dim = atoi(next());
@@ -347,6 +353,7 @@ int main(int argc, const char* argv[]) {
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)
     if (use_sinks) parallel_kv = false;                  // (nor the sinks: fattn_ext_sinks takes fattn_params)
+    if (set_rows) parallel_kv = false;                   // (SET_ROWS writes rows: no transposed V)
 
     const int D = head_dim, H = num_heads, Hkv = num_kv_heads, N = kv_size, NQ = n_q;
     const float scale = 1.0f / sqrtf((float)D);
@@ -367,6 +374,29 @@ int main(int argc, const char* argv[]) {
     random_fill(value);
     random_fill(mask);
     if (mask_kind != "random") std::fill(mask.begin(), mask.end(), 0.0f);  // "none": zeros on the CPU, no mask on the GPU
+    // --set-rows: row n of K / V lands in slot perm[n] (Fisher-Yates over an LCG of
+    // its own: the rand() stream above stays the reference's); from here on key,
+    // value and the mask columns are in slot order, key_src / value_src as drawn
+    std::vector<int64_t> perm;
+    std::vector<float> key_src, value_src;
+    if (set_rows && !cpu_only) {
+        perm.resize(N);
+        for (int n = 0; n < N; n++) perm[n] = n;
+        uint64_t lcg = 0x9E3779B97F4A7C15ull;
+        for (int n = N - 1; n > 0; n--) {
+            lcg = lcg * 6364136223846793005ull + 1442695040888963407ull;
+            std::swap(perm[n], perm[(lcg >> 33) % (uint64_t)(n + 1)]);
+        }
+        key_src = key, value_src = value;
+        const std::vector<float> mask_src = mask;
+        for (int h = 0; h < Hkv; h++)
+            for (int n = 0; n < N; n++) {
+                std::memcpy(&key[((size_t)h * N + perm[n]) * D], &key_src[((size_t)h * N + n) * D], sizeof(float) * D);
+                std::memcpy(&value[((size_t)h * N + perm[n]) * D], &value_src[((size_t)h * N + n) * D], sizeof(float) * D);
+            }
+        for (int r = 0; r < NQ; r++)
+            for (int n = 0; n < N; n++) mask[(size_t)r * N + perm[n]] = mask_src[(size_t)r * N + n];
+    }
     // the query rows the CPU reference checks: all of them, or check_rows at
     // the start, middle and end of the sequence
     std::vector<int> rows;
@@ -419,7 +449,7 @@ int main(int argc, const char* argv[]) {
         HIP_CHECK(hipSetDevice(0));
         hipStream_t st0;
         HIP_CHECK(hipStreamCreate(&st0));
-        if (kv_type == FATTN_TYPE_F16) {
+        if (kv_type == FATTN_TYPE_F16 && !set_rows) {
             uint16_t* k16 = (uint16_t*)kbytes.data();
             uint16_t* v16 = (uint16_t*)vbytes.data();
             for (size_t i = 0; i < key.size(); i++) k16[i] = f2h(key[i]);
@@ -439,16 +469,38 @@ int main(int argc, const char* argv[]) {
             HIP_CHECK(hipMalloc(&d_vq, vbytes.size()));
             HIP_CHECK(hipMemcpyAsync(d_kf, key.data(), 4 * key.size(), hipMemcpyHostToDevice, st0));
             HIP_CHECK(hipMemcpyAsync(d_vf, value.data(), 4 * value.size(), hipMemcpyHostToDevice, st0));
-            int rc = fattn_quantize(kv_type, d_kf, d_kq, D, (int64_t)N * Hkv, st0);
-            rc = rc ? rc : fattn_quantize(kv_type, d_vf, d_vq, D, (int64_t)N * Hkv, st0);
-            rc = rc ? rc : fattn_dequantize(kv_type, d_kq, d_kf, D, (int64_t)N * Hkv, st0);
-            rc = rc ? rc : fattn_dequantize(kv_type, d_vq, d_vf, D, (int64_t)N * Hkv, st0);
+            int rc;
+            void* d_idx = nullptr;
+            if (set_rows) {
+                // ggml_set_rows(cache, cur, idxs) per tensor: f32 [D, N, Hkv] rows as drawn,
+                // one I64 index row for every head, the cache [Hkv][N][row]
+                HIP_CHECK(hipMemcpyAsync(d_kf, key_src.data(), 4 * key.size(), hipMemcpyHostToDevice, st0));
+                HIP_CHECK(hipMemcpyAsync(d_vf, value_src.data(), 4 * value.size(), hipMemcpyHostToDevice, st0));
+                HIP_CHECK(hipMalloc(&d_idx, sizeof(int64_t) * N));
+                HIP_CHECK(hipMemcpyAsync(d_idx, perm.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, st0));
+                const int64_t eb = kv_type == FATTN_TYPE_F16 ? 2 : (int64_t)fattn_row_size(kv_type, 32);
+                const fattn_tensor ti = {d_idx, FATTN_TYPE_I64, 0, {N, 1, 1, 1}, {8, 8 * (int64_t)N, 8 * (int64_t)N, 8 * (int64_t)N}};
+                fattn_tensor ts = {d_kf, FATTN_TYPE_F32, 0, {D, N, Hkv, 1}, {4, (int64_t)D * 4, (int64_t)D * 4 * N, (int64_t)D * 4 * N * Hkv}};
+                fattn_tensor td = {d_kq, kv_type, 0, {D, N, Hkv, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+                rc = fattn_set_rows(&ts, &ti, &td, st0);
+                ts.data = d_vf, td.data = d_vq;
+                rc = rc ? rc : fattn_set_rows(&ts, &ti, &td, st0);
+            } else {
+                rc = fattn_quantize(kv_type, d_kf, d_kq, D, (int64_t)N * Hkv, st0);
+                rc = rc ? rc : fattn_quantize(kv_type, d_vf, d_vq, D, (int64_t)N * Hkv, st0);
+            }
+            if (kv_type != FATTN_TYPE_F16) {
+                rc = rc ? rc : fattn_dequantize(kv_type, d_kq, d_kf, D, (int64_t)N * Hkv, st0);
+                rc = rc ? rc : fattn_dequantize(kv_type, d_vq, d_vf, D, (int64_t)N * Hkv, st0);
+            }
             if (rc) {
-                fprintf(stderr, "quantize failed: %s\n", fattn_strerror(rc));
+                fprintf(stderr, "%s failed: %s\n", set_rows ? "set_rows" : "quantize", fattn_strerror(rc));
                 return 2;
             }
-            HIP_CHECK(hipMemcpyAsync(kref.data(), d_kf, 4 * key.size(), hipMemcpyDeviceToHost, st0));
-            HIP_CHECK(hipMemcpyAsync(vref.data(), d_vf, 4 * value.size(), hipMemcpyDeviceToHost, st0));
+            if (kv_type != FATTN_TYPE_F16) {  // (f16: the reference rounds key / value itself)
+                HIP_CHECK(hipMemcpyAsync(kref.data(), d_kf, 4 * key.size(), hipMemcpyDeviceToHost, st0));
+                HIP_CHECK(hipMemcpyAsync(vref.data(), d_vf, 4 * value.size(), hipMemcpyDeviceToHost, st0));
+            }
             HIP_CHECK(hipMemcpyAsync(kbytes.data(), d_kq, kbytes.size(), hipMemcpyDeviceToHost, st0));
             HIP_CHECK(hipMemcpyAsync(vbytes.data(), d_vq, vbytes.size(), hipMemcpyDeviceToHost, st0));
             HIP_CHECK(hipStreamSynchronize(st0));
@@ -460,6 +512,7 @@ int main(int argc, const char* argv[]) {
             HIP_CHECK(hipFree(d_vf));
             HIP_CHECK(hipFree(d_kq));
             HIP_CHECK(hipFree(d_vq));
+            if (d_idx) HIP_CHECK(hipFree(d_idx));
         }
         HIP_CHECK(hipStreamSynchronize(st0));
         HIP_CHECK(hipStreamDestroy(st0));

@@ -32,6 +32,10 @@
  *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 row conversion on the
  *                           GPU (bit-exact with upstream ggml; absent from the
  *                           reference) -- the KV-cache write side.
+ *   fattn_cpy() / fattn_set_rows()   the cache write itself: GGML_OP_CPY into a
+ *                           contiguous view, and GGML_OP_SET_ROWS, rows scattered to
+ *                           the slots an index tensor in device memory names (what
+ *                           llama.cpp emits since mid-2025); both absent from the reference.
  *
  * Conventions:
  *   - every pointer is a device pointer the caller allocated; the library never
@@ -65,6 +69,8 @@ enum fattn_type {
     FATTN_TYPE_Q5_0 = 6,
     FATTN_TYPE_Q5_1 = 7,
     FATTN_TYPE_Q8_0 = 8,
+    FATTN_TYPE_I32 = 26,  /* index tensors of fattn_set_rows only: every other entry point rejects them */
+    FATTN_TYPE_I64 = 27,
 };
 
 enum fattn_status {
@@ -247,6 +253,41 @@ int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_r
  * cache (nb1 = row bytes).  ne[0] a multiple of 32 for the block types.  Values
  * bit-exact with ggml quantize_row_*_ref / f16 round-to-nearest-even. */
 int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
+
+/* GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: the KV-cache write by slot
+ * index (upstream ggml_set_rows(a, b, c) with dst = a, src = b, idx = c; absent
+ * from the reference).  The slots are data in device memory, not launch
+ * arguments: one captured graph serves every decode step.
+ *   src  F32  ne = [ne0, nr, ne2, ne3]; nb[0] == 4, nb[1..3] any multiples of 4,
+ *        4-byte aligned base (a 16-byte aligned base with nb[1..3] multiples of
+ *        16 reads 16 B per lane, anything else 4 B at a time: same bytes written)
+ *   idx  I64 or I32  ne = [nr, ne11, ne12, 1] with ne2 % ne11 == 0 and
+ *        ne3 % ne12 == 0 -- ggml's broadcast: one index row for all heads /
+ *        streams, or one per head / per stream.  Base and nb multiples of the
+ *        element size, nb[0] >= the element size; nb[1] / nb[2] any non-negative
+ *        multiples (0 repeats a row), looked at only where the count exceeds 1
+ *   dst  F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1  ne = [ne0, n_slots, ne2, ne3]; nb[0] = element /
+ *        block bytes, nb[1..3] and the base multiples of 2 as for fattn_cpy, so a
+ *        [N][Hkv][row] and a [Hkv][N][row] cache are both expressible.  ne0 a
+ *        multiple of 32 for the block types, any ne0 >= 1 for F16
+ * For every (i, i2, i3):
+ *     slot = idx.data[i*nb[0] + (i2 % ne11)*nb[1] + (i3 % ne12)*nb[2]]
+ * read at full width and compared with n_slots in 64 bits (an I64 value is never
+ * truncated); when 0 <= slot < n_slots the dst row at slot*nb[1] + i2*nb[2] +
+ * i3*nb[3] becomes the conversion of the src row at i*nb[1] + i2*nb[2] + i3*nb[3]:
+ * the bytes of ggml quantize_row_*_ref / the f16 round-to-nearest-even, exactly
+ * those fattn_cpy and fattn_quantize write.  No other byte of dst changes.
+ *   - AN OUT-OF-RANGE SLOT WRITES NOTHING: that row is skipped.  ggml asserts on
+ *     the host; the library cannot read device memory, and never stores out of
+ *     bounds.  This is the contract, not an error path: the call still returns 0.
+ *   - duplicate slots in one launch: some one of the rows wins, as in ggml.
+ * Validated before anything launches: NULL or a shape (any ne <= 0, ne that do
+ * not match, ne0 % 32 for a block type, more than 2^31 - 1 blocks in one
+ * [ne0, nr] plane) FATTN_ERR_INVALID_ARG; a type FATTN_ERR_UNSUPPORTED_TYPE; a
+ * wrong nb[0] or a negative idx stride FATTN_ERR_BAD_STRIDE; alignment
+ * FATTN_ERR_ALIGNMENT.  Stream-ordered; allocates nothing, does not
+ * synchronise, capturable. */
+int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, const fattn_tensor* dst, void* stream);
 
 const char* fattn_strerror(int status);
 /* bytes of one row of k elements (0 if unsupported) */
