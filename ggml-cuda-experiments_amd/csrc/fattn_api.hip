@@ -111,7 +111,7 @@ const char* fattn_strerror(int s) {
         case FATTN_OK: return "ok";
         case FATTN_ERR_INVALID_ARG: return "invalid argument";
         case FATTN_ERR_UNSUPPORTED_TYPE: return "unsupported tensor type";
-        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256)";
+        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256; K 576 with V 512, f16)";
         case FATTN_ERR_BAD_STRIDE: return "unsupported strides / layout";
         case FATTN_ERR_WORKSPACE: return "workspace too small";
         case FATTN_ERR_LAUNCH: return "HIP launch failed";
@@ -155,6 +155,13 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
     const char* xcd = pl.a.xcd_group ? " (xcd order)" : "";
     char kern[160];
     switch (pl.kernel) {
+        case Kernel::Mla: {  // (f32 partials, plain loads: no other merge form)
+            char vform[24] = "v=own";
+            if (pl.mla_v_off >= 0) std::snprintf(vform, sizeof vform, "v=k+%d", pl.mla_v_off);
+            std::snprintf(kern, sizeof kern, "fattn_mla_kernel<f16,DK%d,DV%d,%s,%s>%s%s", pl.D, pl.DV, hm, vform, xcd,
+                          pl.a.merge_launch ? " + fattn_mla_merge_kernel" : "");
+            break;
+        }
         case Kernel::Pf:
         case Kernel::Pf4: {
             const bool pre = pl.pf_stage || pl.pf_flags;  // (the pre-pass: one launch, pf_prepass_kernel)
@@ -233,6 +240,7 @@ int launch_ext(const fattn_params* p, const float* sinks, void* stream, void* ev
     Events ev;
     ev.begin = (hipEvent_t)ev_begin;
     ev.end = (hipEvent_t)ev_end;
+    if (pl.kernel == Kernel::Mla) return launch_mla(pl, st, ev);
     switch (pl.D) {
         case 64: return launch_types<64>(pl, st, ev);
         case 80: return launch_types<80>(pl, st, ev);
@@ -262,7 +270,10 @@ int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void
                          int ne2, int ne3, int k_type, int v_type, void* workspace, size_t workspace_bytes,
                          void* stream) {
     // flash-llama.h:120-125: V shares K's shape and strides -- so one row size:
-    // mixed K / V types need the struct form (fattn_ext) with V's own strides
+    // mixed K / V types need the struct form (fattn_ext) with V's own strides.
+    // The same one ne10 is K's and V's row length: the list cannot name the MLA
+    // shape (K dim 576, V dim 512), which only fattn_ext / fattn_ext_sinks take --
+    // ne00 = 576 here is FATTN_ERR_UNSUPPORTED_HEAD_DIM (V read as 576 wide)
     (void)ne0; (void)ne1; (void)ne2; (void)ne3;
     if (k_type != v_type) return FATTN_ERR_INVALID_ARG;
     fattn_params p;

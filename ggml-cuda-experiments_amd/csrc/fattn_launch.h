@@ -17,6 +17,7 @@
 #include "fattn_bd.h"
 #include "fattn_bdp.h"
 #include "fattn_split.h"
+#include "fattn_mla.h"
 
 namespace fattn {
 
@@ -31,13 +32,16 @@ enum class Kernel {
     Pf4,      // ... its one-wave-per-SIMD body (fattn_pf4.h; f16 rows, D = 128)
     Bd,       // batched-decode kernel, all waves alike (fattn_bd.h)
     Bdp,      // ... in its compute / build-role form (fattn_bdp.h; Q8_0 / Q4_0)
+    Mla,      // MLA kernel (fattn_mla.h): K dim 576, V dim 512, f16
 };
 
 struct Plan {
     SplitArgs a = {};
     Kernel kernel = Kernel::Split;
     int kt = 0, vt = 0;  // vt may be VT_F16T
-    int D = 0;
+    int D = 0;           // head dim (Kernel::Mla: K's, 576)
+    int DV = 0;          // Kernel::Mla: V's row length, 512 -- dst's last dim (0 on every other plan: D)
+    int mla_v_off = -1;  // Kernel::Mla: V is a view of K, this many bytes into each row; -1: V of its own
     int gran = 0;
     dim3 grid;
     int lds = 0;
@@ -394,9 +398,13 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
             if (f16) return launch_gran<F16, F16, D>(pl, st, ev);
             if (pl.kt == F16 && pl.vt == VT_F16T) return launch_gran<F16, VT_F16T, D>(pl, st, ev);
             break;
+        case Kernel::Mla: break;  // (launch_mla: no head dim of this table)
     }
     return FATTN_ERR_UNSUPPORTED_TYPE;
 }
+
+// the MLA kernels (instantiated in fattn_launch_mla.hip)
+int launch_mla(const Plan& pl, hipStream_t st, const Events& ev);
 
 extern template int launch_types<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_types<80>(const Plan&, hipStream_t, const Events&);

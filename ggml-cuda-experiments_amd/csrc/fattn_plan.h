@@ -123,6 +123,7 @@ int lds_bytes_of(Kernel kern, int waves, int nbuf) {
         case Kernel::Bdp:
             if constexpr (quant && (D == 64 || D == 96 || D == 128)) return BdpCfg<KT, D>::ldsBytes;
             break;
+        case Kernel::Mla: break;  // (size_mla: MlaCfg, no head dim of this table)
     }
     return 0;
 }
@@ -223,16 +224,88 @@ struct Views {
     int64_t D, NQ, H, S, N, Hkv, Skv;
     int64_t n_head_total;
     bool mixed, v_trans, g16, has_mask;
+    bool mla = false;      // K dim 576 / V dim 512 (check_views_mla); D is K's
+    int64_t mla_v_off = -1;  // ... V is a view of K, this many bytes into each row; -1: V of its own
     int64_t m_ne2 = 1, m_ne3 = 1, m_nb2 = 0, m_nb3 = 0;  // mask planes
     int64_t k_span, v_span, m_span, m_span_h, q_span;    // byte spans addressed through the 32-bit buffer descriptors
 };
 constexpr int64_t kSpanMax = (int64_t)0xFFFFFFF0;
+
+// ggml's op_params[1], [2] and the global head numbering of the slopes
+inline int check_scalars(const fattn_params* p, Views& w, int64_t H) {
+    if (!std::isfinite(p->max_bias) || p->max_bias < 0.0f) return FATTN_ERR_INVALID_ARG;
+    if (!std::isfinite(p->logit_softcap) || p->logit_softcap < 0.0f) return FATTN_ERR_INVALID_ARG;
+    w.n_head_total = p->n_head_total == 0 ? H : (int64_t)p->n_head_total;
+    if (p->head_first < 0 || (int64_t)p->head_first + H > w.n_head_total) return FATTN_ERR_INVALID_ARG;
+    return FATTN_OK;
+}
+
+// the mask view and its planes (w.has_mask, w.m_*)
+inline int check_mask(const fattn_tensor& mk, Views& w, int64_t N, int64_t NQ, int64_t H, int64_t S) {
+    w.has_mask = mk.data != nullptr;
+    if (!w.has_mask) return FATTN_OK;
+    // rows padded to an even length (ggml pads to GGML_KQ_MASK_PAD), dword aligned
+    if (mk.type != FATTN_TYPE_F16 || mk.ne[0] < N + (N & 1) || mk.ne[1] < NQ) return FATTN_ERR_INVALID_ARG;
+    if ((uintptr_t)mk.data % 4 || mk.nb[1] % 4) return FATTN_ERR_ALIGNMENT;
+    // mask planes: ne[2] per head, ne[3] per sequence, read by the query's
+    // indices as ggml does (iq2 % ne[2], iq3 % ne[3]); a count below 1 reads
+    // as 1 (zeroed structs), and a count of 1 has no stride to look at
+    w.m_ne2 = std::max<int64_t>(1, mk.ne[2]);
+    w.m_ne3 = std::max<int64_t>(1, mk.ne[3]);
+    if (H % w.m_ne2 || S % w.m_ne3) return FATTN_ERR_INVALID_ARG;
+    if (w.m_ne2 > 1) w.m_nb2 = mk.nb[2];
+    if (w.m_ne3 > 1) w.m_nb3 = mk.nb[3];
+    if (w.m_nb2 % 4 || w.m_nb3 % 4) return FATTN_ERR_ALIGNMENT;
+    if (w.m_nb2 < 0 || w.m_nb3 < 0) return FATTN_ERR_BAD_STRIDE;
+    // (mask_head_off takes iq2 % ne[2] through a float quotient)
+    if (w.m_ne2 > 1 && H >= (int64_t)1 << 24) return FATTN_ERR_INVALID_ARG;
+    return FATTN_OK;
+}
+
+// The one pair of unequal row lengths: q.ne[0] = k.ne[0] = 576, v.ne[0] = 512,
+// f16 rows, not transposed (multi-head latent attention, include/fattn.h).  16-B
+// pieces only: bases and nb[1..3] multiples of 16.  V is a VIEW of K when it
+// starts 0 .. 128 bytes (a multiple of 16) into K's first row with K's strides
+// (a stride of a dim of one element is not looked at): the kernel then loads
+// each cache row once and takes V out of the K tile.
+inline int check_views_mla(const fattn_params* p, Views& w) {
+    const fattn_tensor &q = p->q, &k = p->k, &v = p->v, &mk = p->mask;
+    if (k.ne[0] != kMlaDK || v.ne[0] != kMlaDV) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
+    if (k.type != FATTN_TYPE_F16 || v.type != FATTN_TYPE_F16 || k.nb[0] != 2 || v.nb[0] != 2) return FATTN_ERR_UNSUPPORTED_TYPE;
+    w.mla = true;
+    const int64_t NQ = w.NQ = q.ne[1], H = w.H = q.ne[2], S = w.S = q.ne[3];
+    const int64_t N = w.N = k.ne[1], Hkv = w.Hkv = k.ne[2], Skv = w.Skv = k.ne[3];
+    if (NQ <= 0 || H <= 0 || S <= 0 || N <= 0 || Hkv <= 0 || Skv <= 0) return FATTN_ERR_INVALID_ARG;
+    if (v.ne[1] != N || v.ne[2] != Hkv || v.ne[3] != Skv) return FATTN_ERR_INVALID_ARG;
+    if (H % Hkv || S % Skv) return FATTN_ERR_INVALID_ARG;
+    if (N > (int64_t)1 << 30 || NQ * H * S > (int64_t)1 << 31) return FATTN_ERR_INVALID_ARG;
+    w.mixed = w.v_trans = false;
+    if ((uintptr_t)q.data % 16 || q.nb[1] % 16 || q.nb[2] % 16 || q.nb[3] % 16) return FATTN_ERR_ALIGNMENT;
+    if (const int rc = check_scalars(p, w, H)) return rc;
+    for (const fattn_tensor* t : {&k, &v})
+        if ((uintptr_t)t->data % 16 || t->nb[1] % 16 || t->nb[2] % 16 || t->nb[3] % 16) return FATTN_ERR_ALIGNMENT;
+    // (rows may be padded, not overlapped: a row past N must lie past the span)
+    if (k.nb[1] < kMlaDK * 2 || v.nb[1] < kMlaDV * 2) return FATTN_ERR_BAD_STRIDE;
+    if (const int rc = check_mask(mk, w, N, NQ, H, S)) return rc;
+    w.g16 = true;
+    const int64_t off = (int64_t)((uintptr_t)v.data - (uintptr_t)k.data);
+    const bool same_nb = (N == 1 || v.nb[1] == k.nb[1]) && (Hkv == 1 || v.nb[2] == k.nb[2]) && (Skv == 1 || v.nb[3] == k.nb[3]);
+    if ((uintptr_t)v.data >= (uintptr_t)k.data && off <= kMlaVOffMax && same_nb) w.mla_v_off = off;
+    w.k_span = (N - 1) * k.nb[1] + kMlaDK * 2;
+    w.v_span = (N - 1) * v.nb[1] + kMlaDV * 2;
+    w.m_span = w.has_mask ? (NQ - 1) * mk.nb[1] + mk.ne[0] * 2 : 0;
+    w.m_span_h = w.m_span + (w.m_ne2 - 1) * w.m_nb2;
+    w.q_span = (NQ - 1) * q.nb[1] + (H - 1) * q.nb[2] + kMlaDK * 4;
+    if (w.k_span > kSpanMax || w.v_span > kSpanMax || w.m_span_h > kSpanMax || w.q_span > kSpanMax) return FATTN_ERR_BAD_STRIDE;
+    return FATTN_OK;
+}
 
 inline int check_views(const fattn_params* p, Views& w) {
     if (!p || !p->q.data || !p->k.data || !p->v.data || !p->dst) return FATTN_ERR_INVALID_ARG;
     const fattn_tensor &q = p->q, &k = p->k, &v = p->v, &mk = p->mask;
     if (q.type != FATTN_TYPE_F32 || q.nb[0] != 4) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int64_t D = w.D = q.ne[0];
+    if (D == kMlaDK) return check_views_mla(p, w);
     if (D != 64 && D != 80 && D != 96 && D != 128 && D != 256) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
     if (D % QK && (k.type != FATTN_TYPE_F16 || v.type != FATTN_TYPE_F16)) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
     if (k.ne[0] != D || v.ne[0] != D) return FATTN_ERR_INVALID_ARG;
@@ -255,11 +328,7 @@ inline int check_views(const fattn_params* p, Views& w) {
         if (D == 96) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
     }
     if ((uintptr_t)q.data % 16 || q.nb[1] % 16 || q.nb[2] % 16 || q.nb[3] % 16) return FATTN_ERR_ALIGNMENT;
-    // ggml's op_params[1], [2] and the global head numbering of the slopes
-    if (!std::isfinite(p->max_bias) || p->max_bias < 0.0f) return FATTN_ERR_INVALID_ARG;
-    if (!std::isfinite(p->logit_softcap) || p->logit_softcap < 0.0f) return FATTN_ERR_INVALID_ARG;
-    w.n_head_total = p->n_head_total == 0 ? H : (int64_t)p->n_head_total;
-    if (p->head_first < 0 || (int64_t)p->head_first + H > w.n_head_total) return FATTN_ERR_INVALID_ARG;
+    if (const int rc = check_scalars(p, w, H)) return rc;
 
     const size_t rowK = row_size(k.type, D), rowV = row_size(v.type, D);
     // K rows must be contiguous (nb[0] = element size / block granular)
@@ -277,24 +346,7 @@ inline int check_views(const fattn_params* p, Views& w) {
     if (k.nb[1] % 2 || k.nb[2] % 4 || k.nb[3] % 4 || (uintptr_t)k.data % 4) return FATTN_ERR_ALIGNMENT;
     if (v.nb[1] % 2 || v.nb[2] % 4 || v.nb[3] % 4 || (uintptr_t)v.data % 4) return FATTN_ERR_ALIGNMENT;
 
-    w.has_mask = mk.data != nullptr;
-    if (w.has_mask) {
-        // rows padded to an even length (ggml pads to GGML_KQ_MASK_PAD), dword aligned
-        if (mk.type != FATTN_TYPE_F16 || mk.ne[0] < N + (N & 1) || mk.ne[1] < NQ) return FATTN_ERR_INVALID_ARG;
-        if ((uintptr_t)mk.data % 4 || mk.nb[1] % 4) return FATTN_ERR_ALIGNMENT;
-        // mask planes: ne[2] per head, ne[3] per sequence, read by the query's
-        // indices as ggml does (iq2 % ne[2], iq3 % ne[3]); a count below 1 reads
-        // as 1 (zeroed structs), and a count of 1 has no stride to look at
-        w.m_ne2 = std::max<int64_t>(1, mk.ne[2]);
-        w.m_ne3 = std::max<int64_t>(1, mk.ne[3]);
-        if (H % w.m_ne2 || S % w.m_ne3) return FATTN_ERR_INVALID_ARG;
-        if (w.m_ne2 > 1) w.m_nb2 = mk.nb[2];
-        if (w.m_ne3 > 1) w.m_nb3 = mk.nb[3];
-        if (w.m_nb2 % 4 || w.m_nb3 % 4) return FATTN_ERR_ALIGNMENT;
-        if (w.m_nb2 < 0 || w.m_nb3 < 0) return FATTN_ERR_BAD_STRIDE;
-        // (mask_head_off takes iq2 % ne[2] through a float quotient)
-        if (w.m_ne2 > 1 && H >= (int64_t)1 << 24) return FATTN_ERR_INVALID_ARG;
-    }
+    if (const int rc = check_mask(mk, w, N, NQ, H, S)) return rc;
 
     // fast path: 16-B pieces.  Quantised rows: contiguous per head (a step of
     // 32 rows is one run of bytes); f16 rows: 16-B aligned
@@ -734,6 +786,51 @@ inline int size_pf(Plan& pl, const Options& o, const fattn_params* p, const View
     return FATTN_OK;
 }
 
+// MLA sizing: one 4-wave workgroup (64 packed rows; 120 KiB of LDS with V a
+// view of K, 144 KiB with V of its own) per CU; the KV sequence of each (kv
+// head x 64-row tile x seq) splits into chunks of whole 32-key tiles until the
+// workgroups cover the CUs -- at least 4 tiles a chunk (a workgroup's prologue
+// is two tiles deep), at most 64 chunks (the merge takes one (m, l) pair per
+// lane).  kv_chunk is a hint, rounded up to tiles.  Chunk partials: f32,
+// [S][Y][chunks][64 rows] x 512, merged in a second launch (no arrival words).
+inline int size_mla(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N) {
+    SplitArgs& a = pl.a;
+    const bool own = pl.mla_v_off < 0;
+    const int64_t tiles = (N + kStep - 1) / kStep;
+    pl.lds = own ? MlaCfg<true>::ldsBytes : MlaCfg<false>::ldsBytes;
+    int64_t nch;
+    if (kv_chunk > 0) {
+        nch = (N + kv_chunk - 1) / kv_chunk;
+    } else {
+        nch = (pl.cus + Y * S - 1) / (Y * S);
+        nch = std::min<int64_t>(nch, std::max<int64_t>(1, tiles / 4));
+    }
+    nch = std::max<int64_t>(1, std::min<int64_t>(nch, tiles));
+    int64_t tpc = (tiles + nch - 1) / nch;
+    nch = (tiles + tpc - 1) / tpc;
+    while (nch > kWaveMergeParts) {
+        tpc++;
+        nch = (tiles + tpc - 1) / tpc;
+    }
+    a.chunk_len = (int)(tpc * kStep);
+    a.n_chunks = (int)nch;
+    a.ncp = next_pow2(a.n_chunks);
+    a.nbuf = own ? MlaCfg<true>::nBuf : MlaCfg<false>::nBuf;
+    a.merge_launch = nch > 1 ? 1 : 0;
+    pl.grid = dim3(a.n_chunks, (unsigned)Y, (unsigned)S);
+    // two row tiles per kv head: the pair on one XCD, so that its K rows come
+    // from HBM once (fattn_mla_kernel; H = 128, N = 4096, 32 sequences: V of its
+    // own 114.1 -> 106.7 us, V a view of K 103.7 -> 103.3 us)
+    a.xcd_group = a.n_hsub == 2 && (nch * Y * S) % 16 == 0 ? 1 : 0;
+    if (nch > 1) {
+        const size_t parts = (size_t)S * Y * nch * kMlaRows;
+        pl.cnt_bytes = 0;
+        pl.ml_bytes = (parts * 2 * sizeof(float) + 255) / 256 * 256;
+        pl.ws_bytes = pl.ml_bytes + parts * kMlaDV * 4;
+    }
+    return FATTN_OK;
+}
+
 // ---------------------------------------------------------------- the planner
 // Validate and build the launch plan for a device of `cus` compute units.
 // Returns FATTN_OK or an error.
@@ -750,6 +847,17 @@ inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl)
     pl.gran = w.g16 ? 16 : 4;
     SplitArgs& a = pl.a;
     fill_args(p, w, a);
+    // K dim 576 / V dim 512: one kernel for every shape of the op, 64 packed
+    // rows per tile (whole head groups up to 64 heads; rk2 = 128: two tiles)
+    if (w.mla) {
+        pl.kernel = Kernel::Mla;
+        pl.DV = kMlaDV;
+        pl.mla_v_off = (int)w.mla_v_off;
+        pack_tiles(a, kMlaRows, (int)std::min<int64_t>(a.rk2, kMlaRows), w.NQ);
+        const int64_t Ym = (int64_t)w.Hkv * a.n_hsub * a.n_qt;
+        if (Ym > 65535 || w.S > 65535) return FATTN_ERR_INVALID_ARG;
+        return size_mla(pl, p->kv_chunk, Ym, w.S, w.N);
+    }
     choose_kernel(p, w, o, pl);
     const int64_t Y = (int64_t)w.Hkv * a.n_hsub * a.n_qt;
     if (Y > 65535 || w.S > 65535) return FATTN_ERR_INVALID_ARG;

@@ -306,6 +306,10 @@ def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "
     layout "head": [S][Hkv][N][row]   (per-head contiguous; reference decode layout,
                    src/flash_row_float.h:19,58)
     layout "pos":  [S][N][Hkv][row]   (llama.cpp's KV cache: nb1 = Hkv * row)
+
+    An MLA cache is kv_view(buf, TYPE_F16, MLA_DK, N, 1, S): 576-element rows; its
+    V is mla_v_view() of that view (or a kv_view with D = MLA_DV over a buffer of
+    its own).
     """
     rb = row_size(typ, D)
     nb0 = 2 if typ == TYPE_F16 else BLOCK_BYTES[typ]
@@ -316,6 +320,27 @@ def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "
     else:
         raise ValueError(layout)
     return View(_tptr(buf), typ, (D, N, Hkv, S), nb)
+
+
+MLA_DK, MLA_DV = 576, 512   # multi-head latent attention: K row (64 RoPE dims + the latent), V row (the latent)
+
+
+def mla_v_view(k: View, v_off: int = MLA_DK - MLA_DV) -> View:
+    """The V of an MLA call as a view of its K (include/fattn.h): the 512
+    elements of every 576-element f16 cache row from element v_off on -- 64 when
+    the RoPE dims come first (llama.cpp's order), 0 when the latent does.  Same
+    strides as K, so fattn_ext reads each cache row once (describe: v=k+<bytes>)."""
+    if k.type != TYPE_F16 or int(k.ne[0]) != MLA_DK or int(k.nb[0]) != 2:
+        raise ValueError("mla_v_view: K must be an f16 view with 576-element rows")
+    if v_off % 8 or not 0 <= v_off <= MLA_DK - MLA_DV:
+        raise ValueError("mla_v_view: v_off is 0 .. 64 elements, a multiple of 8 (16 bytes)")
+    return View(k.ptr + 2 * v_off, TYPE_F16, (MLA_DV,) + tuple(int(x) for x in k.ne[1:]), tuple(k.nb))
+
+
+def dst_shape(q: View, v: View) -> tuple:
+    """Shape of the f32 output [S][n_q][H][V's row length]: dst's last dim is
+    V's, which differs from Q's only for the MLA pair (576 / 512)."""
+    return (int(q.ne[3]), int(q.ne[1]), int(q.ne[2]), int(v.ne[0]))
 
 
 def q_view(q) -> View:

@@ -47,6 +47,12 @@
 //                        goes to slot perm[n] of a seeded permutation, and the CPU reference
 //                        sees K, V and the mask columns in slot order (Q has no KV axis); implies
 //                        --no-kv-parallel (flash_attn_row's transposed V is no row write)
+//   --mla [--v-off 0|64] multi-head latent attention (DeepSeek-V2/V3, Kimi-K2): one kv head, K rows
+//                        of 576 f16, V the 512 elements of the same rows from element 0 (latent
+//                        first) or 64 (RoPE dims first, llama.cpp's order) -- a view of K, so each
+//                        cache row is read once; --heads (default 16) / --kv-size / --n-q / --mask
+//                        / --iters / --tol / --cpu-only / --dump apply, scale = 1 / sqrt(192); the
+//                        CPU reference is plain C++ over K dim 576 and V dim 512
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -268,9 +274,181 @@ int parse_type(const std::string& s) {
     exit(2);
 }
 
+// --mla: multi-head latent attention, K rows of 576 f16, V the 512 elements of
+// the same rows from element v_off on (one kv head; include/fattn.h).  The CPU
+// reference is cpu_reference's arithmetic over the two row lengths: operands
+// rounded through fp16, fp32 accumulation, single-pass online softmax, P
+// rounded to f16.  q [NQ][H][576], kv [N][576], mask [NQ][N], out [NQ][H][512].
+constexpr int kMlaDK = 576, kMlaDV = 512;
+
+void cpu_reference_mla(const std::vector<float>& q, const std::vector<float>& kv, const std::vector<float>& mask,
+                       std::vector<float>& out, int N, int H, int NQ, int v_off, float scale, int threads) {
+    std::vector<float> qh(q.size()), kh(kv.size());
+    for (size_t i = 0; i < q.size(); i++) qh[i] = rh(q[i]);
+    for (size_t i = 0; i < kv.size(); i++) kh[i] = rh(kv[i]);
+    auto head = [&](int h) {
+        std::vector<float> s(N);
+        for (int row = 0; row < NQ; row++) {
+            const float* qq = qh.data() + ((size_t)row * H + h) * kMlaDK;
+            const float* mrow = mask.data() + (size_t)row * N;
+            for (int c = 0; c < N; c++) {
+                float acc = 0.0f;
+                for (int i = 0; i < kMlaDK; i++) {
+                    const float p = qq[i] * kh[(size_t)c * kMlaDK + i];
+                    acc = acc + p;
+                }
+                s[c] = acc * scale + mrow[c];
+            }
+            float M = -INFINITY, S = 0.0f;
+            for (int i = 0; i < N; i++) {
+                if (s[i] > M) {
+                    S = 1.0f + S * expf(M - s[i]);
+                    M = s[i];
+                } else {
+                    S += expf(s[i] - M);
+                }
+            }
+            for (int i = 0; i < N; i++) s[i] = rh(expf(s[i] - M) / S);
+            float* o = out.data() + ((size_t)row * H + h) * kMlaDV;
+            for (int c = 0; c < kMlaDV; c++) {
+                float acc = 0.0f;
+                for (int i = 0; i < N; i++) {
+                    const float p = s[i] * kh[(size_t)i * kMlaDK + v_off + c];
+                    acc = acc + p;
+                }
+                o[c] = acc;
+            }
+        }
+    };
+    threads = std::max(1, std::min(threads, H));
+    std::vector<std::thread> pool;
+    for (int t = 0; t < threads; t++)
+        pool.emplace_back([&, t] {
+            for (int h = t; h < H; h += threads) head(h);
+        });
+    for (auto& th : pool) th.join();
+}
+
+// the --mla flow: inputs from rand() in the order Q, KV, mask; the CPU
+// reference; fattn_ext with V = K + v_off elements; timing and the verification
+// line of the other branches
+int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool cpu_only, int iters, float tol, const char* dump) {
+    if (H <= 0 || N <= 0 || NQ <= 0 || (v_off != 0 && v_off != kMlaDK - kMlaDV)) {
+        fprintf(stderr, "--mla: --heads, --kv-size, --n-q positive, --v-off 0|64\n");
+        return 2;
+    }
+    const float scale = 1.0f / sqrtf(192.0f);  // the model family's: 128 nope + 64 rope dims before absorption
+    std::vector<float> query((size_t)kMlaDK * H * NQ), kv((size_t)kMlaDK * N), mask((size_t)N * NQ);
+    random_fill(query);
+    random_fill(kv);
+    random_fill(mask);
+    if (mask_kind != "random") std::fill(mask.begin(), mask.end(), 0.0f);
+    const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::vector<float> ref((size_t)kMlaDV * H * NQ), got(ref.size());
+    cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads);
+    print_array("Reference", ref.data(), 16);
+    if (cpu_only) {
+        if (dump) {
+            FILE* f = fopen(dump, "wb");
+            if (!f || fwrite(ref.data(), sizeof(float), ref.size(), f) != ref.size()) {
+                fprintf(stderr, "cannot write %s\n", dump);
+                return 2;
+            }
+            fclose(f);
+        }
+        return 0;
+    }
+    const bool has_mask = mask_kind != "none";
+    const int mask_rows = (NQ + 31) / 32 * 32, Np = N + (N & 1);
+    std::vector<uint16_t> kv16(kv.size()), mask16((size_t)Np * mask_rows, f2h(0.0f));
+    for (size_t i = 0; i < kv.size(); i++) kv16[i] = f2h(kv[i]);
+    for (int r = 0; r < NQ; r++)
+        for (int i = 0; i < N; i++) mask16[(size_t)r * Np + i] = f2h(mask[(size_t)r * N + i]);
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    float *d_q, *d_out;
+    void *d_kv, *d_mask, *d_ws;
+    HIP_CHECK(hipMalloc(&d_q, 4 * query.size()));
+    HIP_CHECK(hipMalloc(&d_out, 4 * got.size()));
+    HIP_CHECK(hipMalloc(&d_kv, 2 * kv16.size()));
+    HIP_CHECK(hipMalloc(&d_mask, 2 * mask16.size()));
+    HIP_CHECK(hipMemcpyAsync(d_q, query.data(), 4 * query.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_kv, kv16.data(), 2 * kv16.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, st));
+    fattn_params p;
+    std::memset(&p, 0, sizeof(p));
+    const int64_t rk = kMlaDK * 2;
+    p.q = {d_q, FATTN_TYPE_F32, 0, {kMlaDK, NQ, H, 1}, {4, (int64_t)H * kMlaDK * 4, kMlaDK * 4, (int64_t)NQ * H * kMlaDK * 4}};
+    p.k = {d_kv, FATTN_TYPE_F16, 0, {kMlaDK, N, 1, 1}, {2, rk, rk * N, rk * N}};
+    // V: a view of the same rows, v_off elements in (ggml_view of the cache's latent part)
+    p.v = {(const uint8_t*)d_kv + 2 * v_off, FATTN_TYPE_F16, 0, {kMlaDV, N, 1, 1}, {2, rk, rk * N, rk * N}};
+    if (has_mask)
+        p.mask = {d_mask, FATTN_TYPE_F16, 0, {Np, mask_rows, 1, 1},
+                  {2, (int64_t)Np * 2, (int64_t)Np * 2 * mask_rows, (int64_t)Np * 2 * mask_rows}};
+    p.dst = d_out;
+    p.scale = scale;
+    const size_t ws_bytes = std::max<size_t>(fattn_workspace_size(&p), 16);
+    HIP_CHECK(hipMalloc(&d_ws, ws_bytes));
+    int rc = fattn_workspace_init(d_ws, ws_bytes, st);
+    p.workspace = d_ws;
+    p.workspace_bytes = ws_bytes;
+    rc = rc ? rc : fattn_ext(&p, st);
+    if (rc) {
+        fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
+        return 2;
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    hipEvent_t start, stop;
+    HIP_CHECK(hipEventCreate(&start));
+    HIP_CHECK(hipEventCreate(&stop));
+    std::vector<float> times;
+    for (int it = 0; it < iters; it++) {
+        HIP_CHECK(hipEventRecord(start, st));
+        rc = fattn_ext(&p, st);
+        HIP_CHECK(hipEventRecord(stop, st));
+        HIP_CHECK(hipEventSynchronize(stop));
+        if (rc) {
+            fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
+            return 2;
+        }
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+        times.push_back(ms);
+    }
+    std::sort(times.begin(), times.end());
+    const float millis = times[times.size() / 2];
+    HIP_CHECK(hipMemcpy(got.data(), d_out, 4 * got.size(), hipMemcpyDeviceToHost));
+    print_array("MLA HIP", got.data(), 16);
+    float max_diff = 0.0f, max_ref = 0.0f;
+    int row_idx = 0, head_idx = 0, dim_idx = 0;
+    for (int r = 0; r < NQ; r++)
+        for (int h = 0; h < H; h++) {
+            const size_t o = ((size_t)r * H + h) * kMlaDV;
+            for (int i = 0; i < kMlaDV; i++) {
+                const float dd = fabsf(ref[o + i] - got[o + i]);
+                max_ref = std::max(max_ref, fabsf(ref[o + i]));
+                if (dd > max_diff || std::isnan(dd)) {
+                    max_diff = std::isnan(dd) ? INFINITY : dd;
+                    row_idx = r, head_idx = h, dim_idx = i;
+                }
+            }
+        }
+    const float worst_rel = max_diff / std::max(max_ref, 1e-30f);
+    const double bytes = (double)(kMlaDK + kMlaDV) * H * NQ * 4 + 2.0 * kMlaDK * N + (has_mask ? 2.0 * N * NQ : 0.0);
+    const double flops = 2.0 * N * (kMlaDK + kMlaDV) * H * NQ;
+    printf("\ncuda time: %.4f ms  (%.1f GB/s, %.3f TFLOP/s; median of %d)\n", millis, bytes / millis / 1e6,
+           flops / millis / 1e9, iters);
+    const size_t at = ((size_t)row_idx * H + head_idx) * kMlaDV + dim_idx;
+    printf("R (%.4f) CUDA(%.4f) diff: %.4f - row = %d, head = %d, dim = %d\n", ref[at], got[at], max_diff, row_idx,
+           head_idx, dim_idx);
+    printf("checked %d of %d query rows x %d heads; n_q %d, 1 GPU(s)\n", NQ, NQ, H, NQ);
+    printf("normwise rel err %.3g (tol %.1g): %s\n", worst_rel, tol, worst_rel <= tol ? "PASS" : "FAIL");
+    return worst_rel <= tol ? 0 : 1;
+}
+
 }  // namespace
 
-#define RCCL_CHECK(x)                                                                             \
+#define RCCL_CHECK(x)                                                                            \
     do {                                                                                          \
         ncclResult_t r_ = (x);                                                                    \
         if (r_ != ncclSuccess) {                                                                  \
@@ -286,7 +464,8 @@ int main(int argc, const char* argv[]) {
     std::string mask_kind = "random";
     const char* dump = nullptr;
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
-    bool use_sinks = false, set_rows = false;
+    bool use_sinks = false, set_rows = false, mla = false, heads_given = false;
+    int mla_v_off = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -304,7 +483,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--dump") dump = next();
         else if (a == "--kv-type") kv_type = parse_type(next());
         else if (a == "--head-dim") head_dim = atoi(next());
-        else if (a == "--heads") num_heads = atoi(next());
+        else if (a == "--heads") num_heads = atoi(next()), heads_given = true;
         else if (a == "--kv-heads") num_kv_heads = atoi(next());
         else if (a == "--iters") iters = std::max(1, atoi(next()));
         else if (a == "--tol") tol = (float)atof(next());
@@ -314,6 +493,8 @@ int main(int argc, const char* argv[]) {
         else if (a == "--max-bias") max_bias = (float)atof(next());
         else if (a == "--softcap") softcap = (float)atof(next());
         else if (a == "--sinks") sink_base = (float)atof(next()), use_sinks = true;
+        else if (a == "--mla") mla = true;
+        else if (a == "--v-off") mla_v_off = atoi(next());
         else if (a == "--mask") {
             mask_kind = next();
             if (mask_kind != "random" && mask_kind != "zero" && mask_kind != "none") {
@@ -349,6 +530,8 @@ int main(int argc, const char* argv[]) {
     if (num_warps != 8 && num_warps != 4 && num_warps != 2 && num_warps != 1)
         printf("invalid num_warps, should be 2, 4, 8\n");  // kernel_test.h:176-178 (informational)
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
+    // (the model family's smallest head count unless --heads says otherwise)
+    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, mask_kind, cpu_only, iters, tol, dump);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)

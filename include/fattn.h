@@ -77,7 +77,7 @@ enum fattn_status {
     FATTN_OK = 0,
     FATTN_ERR_INVALID_ARG = -1,     /* NULL pointer, bad shape, ne not divisible */
     FATTN_ERR_UNSUPPORTED_TYPE = -2,
-    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 */
+    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 -- or the MLA pair, K 576 with V 512 */
     FATTN_ERR_BAD_STRIDE = -4,       /* layout the kernels cannot address */
     FATTN_ERR_WORKSPACE = -5,        /* workspace too small */
     FATTN_ERR_LAUNCH = -6,           /* HIP launch failure */
@@ -191,6 +191,41 @@ size_t fattn_workspace_size(const fattn_params* p);
 int fattn_workspace_init(void* workspace, size_t workspace_bytes, void* stream);
 int fattn_ext(const fattn_params* p, void* stream);
 
+/* MULTI-HEAD LATENT ATTENTION (DeepSeek-V2 / V3 / R1, Kimi-K2 after weight
+ * absorption): the one shape of GGML_OP_FLASH_ATTN_EXT whose V rows are shorter
+ * than its K rows.  fattn_ext and fattn_ext_sinks take it; no other symbol, no
+ * struct change.
+ *   q    F32  ne = [576, n_q, H, S]      alignment as above (16-B base and nb[1..3])
+ *   k    F16  ne = [576, N, Hkv, Skv]    nb[0] == 2
+ *   v    F16  ne = [512, N, Hkv, Skv]    nb[0] == 2 (not transposed)
+ *   dst  f32 contiguous [S][n_q][H][512] -- the last dim is V's
+ *   H % Hkv == 0 with any ratio (the models: Hkv = 1, H = 16 ... 128),
+ *   S % Skv == 0, any N >= 1.
+ *   k.data, v.data and nb[1..3] of both: multiples of 16 (FATTN_ERR_ALIGNMENT) --
+ *   rows are 1152 B and 1024 B, so natural caches, [N][Hkv][row] layouts and
+ *   rows padded by a multiple of 16 qualify; there is no dword path.  Rows may
+ *   be padded, not overlapped: k.nb[1] >= 1152, v.nb[1] >= 1024, and the
+ *   per-plane byte spans stay below 4 GiB (FATTN_ERR_BAD_STRIDE).
+ *   V AS A VIEW OF K -- what llama.cpp builds, V being the 512-element latent of
+ *   the same cache row: when v.data == k.data + off with 0 <= off <= 128 (off a
+ *   multiple of 16 by the alignment rule) and v.nb[1..3] == k.nb[1..3] (a stride
+ *   of a dim of one element is not compared), each cache row is read from HBM
+ *   ONCE and V is taken out of the K tile in LDS.  off = 0: the latent first;
+ *   off = 128: the 64 RoPE dims first (llama.cpp's order).  Any other V is
+ *   loaded on its own, same results.  fattn_describe says which: v=k+<off> or
+ *   v=own.
+ *   Everything else keeps its meaning: the mask contract (f16, 4-byte aligned
+ *   rows, ne[2] / ne[3] planes, N' >= N rounded up to even), scale, max_bias,
+ *   logit_softcap, n_head_total, head_first, sinks, kv_chunk as a hint (rounded
+ *   up to 32-key tiles, at most 64 chunks), the workspace rules
+ *   (fattn_workspace_size(p) a function of p alone, 0 for a single chunk;
+ *   several chunks merge in a second launch, nothing is allocated, the launch
+ *   is capturable), NaN for a row masked -inf everywhere and zeros with sinks.
+ *   Refused: q.ne[0] == 576 with any K / V row lengths but (576, 512)
+ *   FATTN_ERR_UNSUPPORTED_HEAD_DIM; a quantised or transposed K / V at this
+ *   shape FATTN_ERR_UNSUPPORTED_TYPE.  Every other head dim keeps
+ *   k.ne[0] == v.ne[0] == q.ne[0] (FATTN_ERR_INVALID_ARG). */
+
 /* fattn_ext with attention sinks: src[4] of ggml's GGML_OP_FLASH_ATTN_EXT (the
  * gpt-oss family).  A sink is one extra logit per q head: it joins the softmax
  * denominator and has no value row.  ggml passes it as a tensor of its own, and
@@ -223,7 +258,10 @@ int fattn_ext_sinks(const fattn_params* p, const float* sinks, void* stream);
 
 /* flash-llama.h:7-32 argument list (K and V share nb11..nb13, flash-llama.h:123-125;
  * mask rows padded to ne31, nb31 bytes per row; one mask plane -- the list has
- * no ne32 / ne33 -- as for fattn_row below). */
+ * no ne32 / ne33 -- as for fattn_row below).  The one ne10 is K's and V's row
+ * length, so the list cannot name the MLA shape (K 576, V 512): that one goes
+ * through fattn_ext / fattn_ext_sinks only, and ne00 = 576 here is
+ * FATTN_ERR_UNSUPPORTED_HEAD_DIM. */
 int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void* mask, float* dst, float scale,
                          int ne00, int ne01, int ne02, int ne03, int ne10, int ne11, int ne12, int ne13, int ne31,
                          int nb31, int nb01, int nb02, int nb03, int nb11, int nb12, int nb13, int ne0, int ne1,
