@@ -111,7 +111,7 @@ const char* fattn_strerror(int s) {
         case FATTN_OK: return "ok";
         case FATTN_ERR_INVALID_ARG: return "invalid argument";
         case FATTN_ERR_UNSUPPORTED_TYPE: return "unsupported tensor type";
-        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256; K 576 with V 512, f16)";
+        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256; K 576 with V 512: f16, or q8_0 / q4_0 with V a view of K)";
         case FATTN_ERR_BAD_STRIDE: return "unsupported strides / layout";
         case FATTN_ERR_WORKSPACE: return "workspace too small";
         case FATTN_ERR_LAUNCH: return "HIP launch failed";
@@ -158,8 +158,10 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
         case Kernel::Mla: {  // (f32 partials, plain loads: no other merge form)
             char vform[24] = "v=own";
             if (pl.mla_v_off >= 0) std::snprintf(vform, sizeof vform, "v=k+%d", pl.mla_v_off);
-            std::snprintf(kern, sizeof kern, "fattn_mla_kernel<f16,DK%d,DV%d,%s,%s>%s%s", pl.D, pl.DV, hm, vform, xcd,
-                          pl.a.merge_launch ? " + fattn_mla_merge_kernel" : "");
+            // (quantised cache: wave 0 computes, waves 1 - 3 load and convert; ... whole tiles in 16-B pieces)
+            const char* solo = pl.mla_raw16 ? " (solo, 16-B tiles)" : pl.mla_solo ? " (solo)" : "";
+            std::snprintf(kern, sizeof kern, "fattn_mla_kernel<%s,DK%d,DV%d,%s,%s>%s%s%s", tn(pl.kt), pl.D, pl.DV, hm, vform, solo,
+                          xcd, pl.a.merge_launch ? " + fattn_mla_merge_kernel" : "");
             break;
         }
         case Kernel::Pf:

@@ -32,7 +32,7 @@ enum class Kernel {
     Pf4,      // ... its one-wave-per-SIMD body (fattn_pf4.h; f16 rows, D = 128)
     Bd,       // batched-decode kernel, all waves alike (fattn_bd.h)
     Bdp,      // ... in its compute / build-role form (fattn_bdp.h; Q8_0 / Q4_0)
-    Mla,      // MLA kernel (fattn_mla.h): K dim 576, V dim 512, f16
+    Mla,      // MLA kernel (fattn_mla.h): K dim 576, V dim 512; f16, or Q8_0 / Q4_0 with V a view of K
 };
 
 struct Plan {
@@ -41,7 +41,10 @@ struct Plan {
     int kt = 0, vt = 0;  // vt may be VT_F16T
     int D = 0;           // head dim (Kernel::Mla: K's, 576)
     int DV = 0;          // Kernel::Mla: V's row length, 512 -- dst's last dim (0 on every other plan: D)
-    int mla_v_off = -1;  // Kernel::Mla: V is a view of K, this many bytes into each row; -1: V of its own
+    int mla_v_off = -1;  // Kernel::Mla: V is a view of K, this many bytes into each row (Q8_0 / Q4_0: whole blocks); -1: V of its own
+    // Kernel::Mla over Q8_0 / Q4_0: no tile has more than one wave's 16 rows -- wave 0 computes, waves 1 - 3 load
+    // and convert (fattn_mla_kernel's SOLO); ... and the rows are contiguous on 16-B aligned planes (16-B pieces)
+    bool mla_solo = false, mla_raw16 = false;
     int gran = 0;
     dim3 grid;
     int lds = 0;
@@ -405,6 +408,9 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
 
 // the MLA kernels (instantiated in fattn_launch_mla.hip)
 int launch_mla(const Plan& pl, hipStream_t st, const Events& ev);
+void launch_mla_merge(const Plan& pl, hipStream_t st);
+// ... over a Q8_0 / Q4_0 cache (instantiated in fattn_launch_mla_q.hip)
+int launch_mla_q(const Plan& pl, hipStream_t st, const Events& ev);
 
 extern template int launch_types<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_types<80>(const Plan&, hipStream_t, const Events&);

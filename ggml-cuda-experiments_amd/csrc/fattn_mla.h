@@ -31,6 +31,14 @@
 // only copy.  The KV sequence splits over chunks (grid.x) to fill the chip;
 // chunk partials (f32 O, (m, l)) merge in a second launch by the LSE rule
 // (merge_row_parts at 256 columns, twice per row), where the sink enters.
+//
+// A Q8_0 / Q4_0 CACHE (V a view of K, whole blocks in):
+// the ring holds RAW tiles (32 rows of 18 blocks, by LDS-DMA) and every tile is
+// dequantised once, in LDS, into the f16 K image above -- the tile loop then
+// runs unchanged over that image, so the result is the f16 form's bit for bit.
+// The pipeline is skewed (iteration s converts tile s + 1, then computes tile
+// s: still one barrier per tile).  Where no tile has more than one wave's rows
+// (H = 16 decode) wave 0 computes and waves 1 - 3 load and convert (SOLO).
 #pragma once
 
 #include "fattn_split.h"
@@ -46,10 +54,17 @@ constexpr int kMlaVOffMax = 128;
 struct MlaArgs {
     SplitArgs a;
     int v_off;  // view form: byte offset of V's row inside K's row (0 .. 128, a multiple of 16); else 0
+    int raw16;  // SOLO form of a quantised cache: contiguous rows on a 16-B aligned plane -- whole tiles land in 16-B pieces
 };
 
-template <bool VOWN>
+// KT: the cache's type.  F16: the ring holds f16 tiles as they come from HBM.
+// Q8_0 / Q4_0 (V a view of K only): the ring holds RAW tiles -- 32 rows of 18
+// blocks, landed in dword pieces -- and two f16 images that all 256 threads
+// convert them into (mla_convert_tile), in the layout the f16 form loads.
+template <bool VOWN, int KT = FATTN_TYPE_F16>
 struct MlaCfg {
+    static constexpr bool QUANT = KT != FATTN_TYPE_F16;
+    static_assert(!QUANT || ((KT == FATTN_TYPE_Q8_0 || KT == FATTN_TYPE_Q4_0) && !VOWN), "");
     static constexpr int NT = kMlaWaves * kWave;
     static constexpr int rowK = kMlaDK * 2, rowV = kMlaDV * 2;
     static constexpr int CPK = rowK / 16, CPV = rowV / 16;  // 16-B chunks per row: 72, 64
@@ -58,8 +73,20 @@ struct MlaCfg {
     static constexpr int mBytes = kMlaRows * kStep * 2;     // 64 mask rows x 32 f16
     static constexpr int tileBytes = kBytes + vBytes + mBytes;
     static constexpr int nBuf = VOWN ? 2 : 3;
-    static constexpr int ldsBytes = nBuf * tileBytes;       // 122,880 / 147,456
-    static constexpr int NIK = kBytes / 16 / NT;            // 9
+    // quantised cache: a raw row is 612 B (Q8_0) / 324 B (Q4_0); a raw tile's
+    // 4896 / 2592 dwords take 20 / 11 dword DMAs of the workgroup, the last one
+    // part-filled (its other lanes are requested past the descriptor and write
+    // zeros: the slot is padded to whole instructions, 20,480 / 11,264 B)
+    static constexpr int blockBytes = QUANT ? TypeInfo<KT>::block_bytes : 0;
+    static constexpr int rawRow = kMlaDK / QK * blockBytes;
+    static constexpr int rawDw = kStep * rawRow / 4;
+    static constexpr int NIR = (rawDw + NT - 1) / NT;
+    static constexpr int rawBytes = NIR * NT * 4;
+    static constexpr int slotBytes = rawBytes + mBytes;     // raw tile | mask rows: 24,576 / 15,360
+    static constexpr int nRaw = 3, nImg = 2;
+    static constexpr int ldsBytes = QUANT ? nImg * kBytes + nRaw * slotBytes  // 147,456 / 119,808
+                                          : nBuf * tileBytes;                 // 122,880 / 147,456
+    static constexpr int NIK = QUANT ? NIR : kBytes / 16 / NT;  // 9 (f16)
     static constexpr int NIV = vBytes / 16 / NT;            // 8
     static constexpr int NIM = mBytes / 4 / NT;             // 4
     static_assert(kBytes % (16 * NT) == 0 && vBytes % (16 * NT) == 0 && mBytes % (4 * NT) == 0, "");
@@ -127,6 +154,63 @@ __device__ __forceinline__ MlaLaneOffs<VOWN> mla_lane_offs(int g, int i16, int v
     return L;
 }
 
+// One raw tile -> the f16 K image.  A group of 8 lanes (l8 = lane & 7) owns CNT
+// image slots l8 + 8 i, i = i0 .. i0 + CNT - 1, of one row.  Slot cs holds chunk
+// c = cs ^ mla_ksw(row) (8 elements: a quarter of block c >> 2), as the f16
+// form's source-side swizzle leaves it; the XOR stays below 8, so the block and
+// the quarter move by constants with i.  Values: h(q d), the exact product
+// rounded once (kv_stage_f16_block's, the oracle's K operand).
+//   reads: a block's qs start 2 mod 4 in even blocks, 0 mod 4 in odd ones
+//   (34 / 18-B blocks in rows of whole dwords): three aligned dwords and a byte
+//   alignment by the offset's bit 1.  Q4_0: quarters 0 / 1 are the low nibbles
+//   of qs[0..7] / qs[8..15], quarters 2 / 3 the high ones.
+//   writes: ds_write_b128 goes in groups of 8 contiguous lanes -- one row's
+//   128 contiguous bytes, 32 distinct banks: conflict-free.
+template <int KT, int CNT>
+__device__ __forceinline__ void mla_convert_part(const uint8_t* raw, uint8_t* img, int row, int l8, int i0) {
+    constexpr int BB = TypeInfo<KT>::block_bytes, RR = kMlaDK / QK * BB;
+    const int c0 = l8 ^ mla_ksw(row);
+    const int sub = c0 & 3;
+    const uint32_t b0 = row * RR + (c0 >> 2) * BB + 2 * BB * i0;             // the block of i = i0
+    const uint32_t q0 = b0 + 2 + 8 * (KT == FATTN_TYPE_Q8_0 ? sub : sub & 1);  // its 8 code bytes
+    const uint32_t qa = q0 & ~3u, sh = q0 & 2u;                              // (2 BB is 0 mod 4: the same for every i)
+    uint8_t* out = img + row * (kMlaDK * 2) + l8 * 16 + 128 * i0;
+#pragma unroll
+    for (int i = 0; i < CNT; i++) {
+        const uint32_t dbits = *(const uint16_t*)(raw + b0 + 2 * BB * i);
+        const uint32_t w0 = *(const uint32_t*)(raw + qa + 2 * BB * i);
+        const uint32_t w1 = *(const uint32_t*)(raw + qa + 2 * BB * i + 4);
+        const uint32_t w2 = *(const uint32_t*)(raw + qa + 2 * BB * i + 8);
+        uint32_t x0 = alignbyte(w1, w0, sh), x1 = alignbyte(w2, w1, sh);
+        const f16x2 d2 = bcast_h(dbits);
+        f16x2 h0, h1, h2, h3;
+        if constexpr (KT == FATTN_TYPE_Q8_0) {
+            i8x4_to_h2x2(x0, h0, h1);
+            i8x4_to_h2x2(x1, h2, h3);
+        } else {
+            const uint32_t ns = 2 * (sub & 2);  // 0: low nibbles, 4: high
+            u4x4_to_h2x2((x0 >> ns) & 0x0F0F0F0Fu, h0, h1);
+            u4x4_to_h2x2((x1 >> ns) & 0x0F0F0F0Fu, h2, h3);
+        }
+        const u32x4 r = {as_u32(h0 * d2), as_u32(h1 * d2), as_u32(h2 * d2), as_u32(h3 * d2)};
+        *(u32x4*)(out + 128 * i) = r;
+    }
+}
+// ... by all 256 threads (thread t: row t >> 3, all nine slots), or -- SOLO, a
+// tile whose rows fill one wave (H = 16 decode): wave 0 computes and waves 1 - 3
+// convert -- by the 192 threads u = t - 64: rows 0 .. 23 as above, then three
+// slots each of rows 24 .. 31 (12 chunks per thread).
+template <int KT, bool SOLO>
+__device__ __forceinline__ void mla_convert_tile(const uint8_t* raw, uint8_t* img, int tid) {
+    constexpr int NS = kMlaDK / 64;  // 9
+    if constexpr (!SOLO) return mla_convert_part<KT, NS>(raw, img, tid >> 3, tid & 7, 0);
+    if (tid < kWave) return;
+    const int g8 = (tid - kWave) >> 3;  // 0 .. 23
+    mla_convert_part<KT, NS>(raw, img, g8, tid & 7, 0);
+    const int third = (g8 * 11) >> 5;   // g8 / 3
+    mla_convert_part<KT, NS / 3>(raw, img, 24 + third, tid & 7, 3 * (g8 - 3 * third));
+}
+
 __device__ __forceinline__ f16x8 mla_tr_pair(const uint8_t* lo_p, const uint8_t* hi_p) {
     typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
     const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)lo_p);
@@ -152,9 +236,14 @@ __device__ __forceinline__ void mla_tile_of(const SplitArgs& a, int y, int& qt, 
     }
 }
 
-template <bool VOWN, bool HM>
+// SOLO (quantised cache only; the launcher's choice): no tile of the launch has
+// more than one wave's 16 rows (H = 16 decode), so wave 0 computes and waves
+// 1 - 3 load and convert -- the conversion leaves the computing wave's chain.
+template <bool VOWN, bool HM, int KT = FATTN_TYPE_F16, bool SOLO = false>
 __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const MlaArgs ma) {
-    using C = MlaCfg<VOWN>;
+    using C = MlaCfg<VOWN, KT>;
+    constexpr bool QUANT = C::QUANT;
+    static_assert(QUANT || !SOLO, "");
     const SplitArgs& a = ma.a;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NB = kMlaDK / QK;   // 18 k-steps
@@ -162,7 +251,7 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     constexpr int KB = 3, VB = 8;     // k-steps / column groups per batch of LDS reads (12 b128 / 16 tr_b64 in flight)
     static_assert(NB % KB == 0 && NC % VB == 0, "");
     constexpr int NI = C::ni(HM);
-    constexpr int PRE = C::nBuf - 1;  // tiles issued ahead of the one being computed
+    constexpr int PRE = C::nBuf - 1;  // tiles issued ahead of the one being computed (f16)
     constexpr float kNegInf = -__builtin_inff();
     constexpr float kDeferLog2 = 8.0f;
     const int tid = threadIdx.x;
@@ -280,9 +369,103 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
         }
     };
     auto buf_of = [&](int s) { return smem + (s % C::nBuf) * C::tileBytes; };
+    // Quantised cache: raw tile [n0, n0 + 32) | mask rows into a raw slot.  Dword
+    // w of the tile is dword w % (rawRow / 4) of row w / (rawRow / 4); dwords
+    // past the tile (the last instruction's tail) and rows from c_hi on are
+    // requested past the descriptor.
+    // SOLO: waves 1 - 3 issue all of it, wave-sized pieces dealt round-robin
+    // (piece j: dwords 64 j .. 64 j + 63)
+    constexpr bool solo = SOLO;
+    auto raw_off = [&](int w, int n0) -> uint32_t {
+        constexpr int RD = QUANT ? C::rawRow / 4 : 1;
+        const int row = w / RD, col = w - row * RD;
+        return w < C::rawDw && n0 + row < c_hi ? (uint32_t)(n0 + row) * (uint32_t)a.k_nb1 + (uint32_t)(col * 4) : a.k_span;
+    };
+    auto issue_raw = [&](int n0, uint8_t* slot) {
+        if constexpr (solo) {
+            if (wave == 0) return;
+            const int h = wave - 1;
+            // pieces: 80 / 44 of the raw tile; of the mask rows only wave 0's 16 (4 pieces of 4 rows)
+            constexpr int NP = C::NIR * kMlaWaves, NPM = kRows / 4;
+            // Contiguous rows on a 16-B aligned plane (MlaArgs::raw16): a whole tile is
+            // one 16-B aligned run of 32 x 612 = 16 x 1224 (Q4_0: 16 x 648) bytes and
+            // lands in 20 (11) wave pieces of 16 B a lane -- a quarter of the requests.
+            // Not the part-filled last tile of N: its rows from N on must read as
+            // zeros, and a 16-B piece can straddle the end of a 612-B row.
+            constexpr int NP16 = (kStep * C::rawRow / 16 + kWave - 1) / kWave;
+            if (ma.raw16 && n0 + kStep <= c_hi) {
+#pragma unroll
+                for (int jj = 0; jj < (NP16 + 2) / 3; jj++) {
+                    const int j = 3 * jj + h;
+                    const int pc = j * kWave + lane;
+                    if (j < NP16)
+                        dma<16>(rs.k, lds_addr(slot) + j * kWave * 16,
+                                pc < kStep * C::rawRow / 16 ? (uint32_t)n0 * (uint32_t)C::rawRow + (uint32_t)pc * 16 : a.k_span);
+                }
+            } else {
+                // (only a chunk's last tile, or every tile of a cache that does not
+                // qualify: the offsets are redone per tile, not kept in registers)
+                int lane_o = lane;
+                if (ma.raw16) asm volatile("" : "+v"(lane_o));
+#pragma unroll
+                for (int jj = 0; jj < (NP + 2) / 3; jj++) {
+                    const int j = 3 * jj + h;
+                    if (j < NP) dma<4>(rs.k, lds_addr(slot) + j * kWave * 4, raw_off(j * kWave + lane_o, n0));
+                }
+            }
+            const int lane_o = lane;
+            if constexpr (HM) {
+#pragma unroll
+                for (int jj = 0; jj < (NPM + 2) / 3; jj++) {
+                    const int j = 3 * jj + h;  // piece j: 4 packed rows of 16 dwords (moff's rows, re-dealt)
+                    if (j < NPM) {
+                        const int pr = 4 * j + (lane_o >> 4);
+                        const int mq = div_R(a, pr);
+                        const int mh = ik2 * a.rk2 + hs * a.R + (pr - mq * a.R);
+                        const uint32_t mo = pr < nvalid ? (uint32_t)(qt * a.QPT + mq) * (uint32_t)a.m_nb1 + mask_head_off(a, mh) +
+                                                              (lane_o & 15) * 4 + (uint32_t)n0 * 2
+                                                        : a.m_span_h;
+                        dma<4>(rs.m, lds_addr(slot) + C::rawBytes + j * kWave * 4, mo);
+                    }
+                }
+            }
+            return;
+        }
+        const uint32_t lb = __builtin_amdgcn_readfirstlane(lds_addr(slot) + wave * kWave * 4);
+#pragma unroll
+        for (int i = 0; i < C::NIR; i++) dma<4>(rs.k, lb + i * C::NT * 4, raw_off(i * C::NT + tid, n0));
+        if constexpr (HM) {
+            const uint32_t lm = __builtin_amdgcn_readfirstlane(lds_addr(slot) + C::rawBytes + wave * kWave * 4);
+#pragma unroll
+            for (int i = 0; i < C::NIM; i++)
+                dma<4>(rs.m, lm + i * C::NT * 4, moff[i] == 0xFFFFFFFFu ? a.m_span_h : moff[i] + (uint32_t)n0 * 2);
+        }
+    };
+    auto img_of = [&](int s) { return smem + (s & 1) * C::kBytes; };
+    auto raw_of = [&](int s) { return smem + C::nImg * C::kBytes + (s % C::nRaw) * C::slotBytes; };
 
     // (Q's loads are compiler-tracked and converted above: they have landed)
-    for (int s = 0; s < PRE && s < ntiles; s++) issue(c_lo + s * kStep, buf_of(s));
+    if constexpr (QUANT) {
+        // A SKEWED pipeline, one barrier per tile: iteration s converts raw tile
+        // s + 1 into the image tile s - 1 was computed from, then computes tile s.
+        // Prologue: raw tiles 0 and 1 in flight, tile 0 converted.
+        // (SOLO: a loading wave has issued 26 or 27 (14 / 15) + 1 or 2 mask pieces
+        // of tile 1; waiting down to the smallest count is safe for all three)
+        // (16-B pieces: 6 or 7 (3 or 4) of them; the smaller count is safe for both forms)
+        constexpr int NI_SOLO = (kStep * C::rawRow / 16 + kWave - 1) / kWave / 3 + (HM ? kRows / 4 / 3 : 0);
+        issue_raw(c_lo, raw_of(0));
+        if (ntiles > 1) {
+            issue_raw(c_lo + kStep, raw_of(1));
+            if constexpr (solo) wait_vmcnt_c<NI_SOLO>();
+            else wait_vmcnt_c<NI>();
+        } else {
+            wait_vmcnt_c<0>();
+        }
+        __syncthreads();
+        mla_convert_tile<KT, SOLO>(raw_of(0), img_of(0), tid);
+    } else {
+        for (int s = 0; s < PRE && s < ntiles; s++) issue(c_lo + s * kStep, buf_of(s));
+    }
 
     float m_run = kNegInf, l_run = 0.0f;
     f32x4 o[NC];
@@ -294,14 +477,26 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     // One barrier per tile: past the barrier of iteration s every thread's
     // pieces of tile s have landed and every wave is done with tile s - 1,
     // whose buffer takes tile s + PRE.
+    // Quantised cache: past the barrier of iteration s every thread's pieces of
+    // raw tile s + 1 have landed (the only DMAs in flight), image s is whole
+    // (written in iteration s - 1, or the prologue) and every wave is done with
+    // tile s - 1: its image takes tile s + 1, and its raw slot -- whose mask rows
+    // tile s - 1 read to the end -- takes raw tile s + 2.
     for (int s = 0; s < ntiles; s++) {
-        mla_wait_tiles<(PRE - 1) * NI>(min(PRE - 1, ntiles - 1 - s));
-        __syncthreads();
-        if (s + PRE < ntiles) issue(c_lo + (s + PRE) * kStep, buf_of(s + PRE));
+        if constexpr (QUANT) {
+            wait_vmcnt_c<0>();
+            __syncthreads();
+            if (s + 2 < ntiles) issue_raw(c_lo + (s + 2) * kStep, raw_of(s + 2));
+            if (s + 1 < ntiles) mla_convert_tile<KT, SOLO>(raw_of(s + 1), img_of(s + 1), tid);
+        } else {
+            mla_wait_tiles<(PRE - 1) * NI>(min(PRE - 1, ntiles - 1 - s));
+            __syncthreads();
+            if (s + PRE < ntiles) issue(c_lo + (s + PRE) * kStep, buf_of(s + PRE));
+        }
         if (!active) continue;
-        const uint8_t* kb = buf_of(s);
+        const uint8_t* kb = QUANT ? img_of(s) : buf_of(s);
         const uint8_t* vb = kb + C::kBytes;
-        const uint8_t* mb = kb + C::kBytes + C::vBytes;
+        const uint8_t* mb = QUANT ? raw_of(s) + C::rawBytes : kb + C::kBytes + C::vBytes;
         const int n0 = c_lo + s * kStep;
 
         // -- S^T = K.Q^T for the two 16-key subtiles

@@ -263,15 +263,20 @@ inline int check_mask(const fattn_tensor& mk, Views& w, int64_t N, int64_t NQ, i
 }
 
 // The one pair of unequal row lengths: q.ne[0] = k.ne[0] = 576, v.ne[0] = 512,
-// f16 rows, not transposed (multi-head latent attention, include/fattn.h).  16-B
-// pieces only: bases and nb[1..3] multiples of 16.  V is a VIEW of K when it
-// starts 0 .. 128 bytes (a multiple of 16) into K's first row with K's strides
-// (a stride of a dim of one element is not looked at): the kernel then loads
-// each cache row once and takes V out of the K tile.
+// not transposed (multi-head latent attention, include/fattn.h).
+// f16 rows: 16-B pieces only, bases and nb[1..3] multiples of 16.  V is a VIEW of
+// K when it starts 0 .. 128 bytes (a multiple of 16) into K's first row with K's
+// strides (a stride of a dim of one element is not looked at): the kernel then
+// loads each cache row once and takes V out of the K tile.
+// Q8_0 / Q4_0 rows (18 blocks, 612 / 324 B): dword pieces, bases and nb[1..3]
+// multiples of 4; V MUST be such a view, 0, 1 or 2 whole blocks into the row.
 inline int check_views_mla(const fattn_params* p, Views& w) {
     const fattn_tensor &q = p->q, &k = p->k, &v = p->v, &mk = p->mask;
     if (k.ne[0] != kMlaDK || v.ne[0] != kMlaDV) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
-    if (k.type != FATTN_TYPE_F16 || v.type != FATTN_TYPE_F16 || k.nb[0] != 2 || v.nb[0] != 2) return FATTN_ERR_UNSUPPORTED_TYPE;
+    const bool quant = k.type == FATTN_TYPE_Q8_0 || k.type == FATTN_TYPE_Q4_0;
+    const int64_t bb = quant ? (int64_t)row_size(k.type, QK) : 2;  // nb[0]: a block's / an element's bytes
+    const int64_t rowK = quant ? kMlaDK / QK * bb : kMlaDK * 2, rowV = quant ? kMlaDV / QK * bb : kMlaDV * 2;
+    if ((k.type != FATTN_TYPE_F16 && !quant) || v.type != k.type || k.nb[0] != bb || v.nb[0] != bb) return FATTN_ERR_UNSUPPORTED_TYPE;
     w.mla = true;
     const int64_t NQ = w.NQ = q.ne[1], H = w.H = q.ne[2], S = w.S = q.ne[3];
     const int64_t N = w.N = k.ne[1], Hkv = w.Hkv = k.ne[2], Skv = w.Skv = k.ne[3];
@@ -282,17 +287,24 @@ inline int check_views_mla(const fattn_params* p, Views& w) {
     w.mixed = w.v_trans = false;
     if ((uintptr_t)q.data % 16 || q.nb[1] % 16 || q.nb[2] % 16 || q.nb[3] % 16) return FATTN_ERR_ALIGNMENT;
     if (const int rc = check_scalars(p, w, H)) return rc;
-    for (const fattn_tensor* t : {&k, &v})
-        if ((uintptr_t)t->data % 16 || t->nb[1] % 16 || t->nb[2] % 16 || t->nb[3] % 16) return FATTN_ERR_ALIGNMENT;
-    // (rows may be padded, not overlapped: a row past N must lie past the span)
-    if (k.nb[1] < kMlaDK * 2 || v.nb[1] < kMlaDV * 2) return FATTN_ERR_BAD_STRIDE;
-    if (const int rc = check_mask(mk, w, N, NQ, H, S)) return rc;
-    w.g16 = true;
     const int64_t off = (int64_t)((uintptr_t)v.data - (uintptr_t)k.data);
     const bool same_nb = (N == 1 || v.nb[1] == k.nb[1]) && (Hkv == 1 || v.nb[2] == k.nb[2]) && (Skv == 1 || v.nb[3] == k.nb[3]);
-    if ((uintptr_t)v.data >= (uintptr_t)k.data && off <= kMlaVOffMax && same_nb) w.mla_v_off = off;
-    w.k_span = (N - 1) * k.nb[1] + kMlaDK * 2;
-    w.v_span = (N - 1) * v.nb[1] + kMlaDV * 2;
+    // a quantised cache has no V of its own: the view is looked at before the
+    // alignment (a V 17 bytes into the row is no view, not a misaligned one)
+    if (quant && !((uintptr_t)v.data >= (uintptr_t)k.data && off <= 2 * bb && off % bb == 0 && same_nb)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    // (a quantised V is K's base plus whole blocks of 34 / 18 B -- 2 mod 4 one
+    // block in: the kernel never addresses through it, only K's base counts)
+    const int al = quant ? 4 : 16;
+    for (const fattn_tensor* t : {&k, &v})
+        if ((!(quant && t == &v) && (uintptr_t)t->data % al) || t->nb[1] % al || t->nb[2] % al || t->nb[3] % al)
+            return FATTN_ERR_ALIGNMENT;
+    // (rows may be padded, not overlapped: a row past N must lie past the span)
+    if (k.nb[1] < rowK || v.nb[1] < rowV) return FATTN_ERR_BAD_STRIDE;
+    if (const int rc = check_mask(mk, w, N, NQ, H, S)) return rc;
+    w.g16 = !quant;
+    if ((uintptr_t)v.data >= (uintptr_t)k.data && off <= (quant ? 2 * bb : kMlaVOffMax) && same_nb) w.mla_v_off = off;
+    w.k_span = (N - 1) * k.nb[1] + rowK;
+    w.v_span = (N - 1) * v.nb[1] + rowV;
     w.m_span = w.has_mask ? (NQ - 1) * mk.nb[1] + mk.ne[0] * 2 : 0;
     w.m_span_h = w.m_span + (w.m_ne2 - 1) * w.m_nb2;
     w.q_span = (NQ - 1) * q.nb[1] + (H - 1) * q.nb[2] + kMlaDK * 4;
@@ -797,7 +809,12 @@ inline int size_mla(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N) {
     SplitArgs& a = pl.a;
     const bool own = pl.mla_v_off < 0;
     const int64_t tiles = (N + kStep - 1) / kStep;
-    pl.lds = own ? MlaCfg<true>::ldsBytes : MlaCfg<false>::ldsBytes;
+    // (the cache's type picks the LDS figure and nothing else: a quantised
+    // cache is cut into the chunks of the f16 one)
+    pl.lds = pl.kt == FATTN_TYPE_Q8_0   ? MlaCfg<false, FATTN_TYPE_Q8_0>::ldsBytes
+             : pl.kt == FATTN_TYPE_Q4_0 ? MlaCfg<false, FATTN_TYPE_Q4_0>::ldsBytes
+             : own                      ? MlaCfg<true>::ldsBytes
+                                        : MlaCfg<false>::ldsBytes;
     int64_t nch;
     if (kv_chunk > 0) {
         nch = (N + kv_chunk - 1) / kv_chunk;
@@ -815,7 +832,7 @@ inline int size_mla(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N) {
     a.chunk_len = (int)(tpc * kStep);
     a.n_chunks = (int)nch;
     a.ncp = next_pow2(a.n_chunks);
-    a.nbuf = own ? MlaCfg<true>::nBuf : MlaCfg<false>::nBuf;
+    a.nbuf = own ? MlaCfg<true>::nBuf : MlaCfg<false>::nBuf;  // (quantised: three raw slots)
     a.merge_launch = nch > 1 ? 1 : 0;
     pl.grid = dim3(a.n_chunks, (unsigned)Y, (unsigned)S);
     // two row tiles per kv head: the pair on one XCD, so that its K rows come
@@ -854,6 +871,12 @@ inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl)
         pl.DV = kMlaDV;
         pl.mla_v_off = (int)w.mla_v_off;
         pack_tiles(a, kMlaRows, (int)std::min<int64_t>(a.rk2, kMlaRows), w.NQ);
+        if (pl.kt != FATTN_TYPE_F16) {
+            // (tile_rows: at most min(QPT, NQ) x R rows a tile)
+            pl.mla_solo = std::min<int64_t>(a.QPT, w.NQ) * a.R <= kRows;
+            pl.mla_raw16 = pl.mla_solo && p->k.nb[1] == (int64_t)row_size(pl.kt, kMlaDK) && (uintptr_t)p->k.data % 16 == 0 &&
+                           (w.Hkv == 1 || p->k.nb[2] % 16 == 0) && (w.Skv == 1 || p->k.nb[3] % 16 == 0);
+        }
         const int64_t Ym = (int64_t)w.Hkv * a.n_hsub * a.n_qt;
         if (Ym > 65535 || w.S > 65535) return FATTN_ERR_INVALID_ARG;
         return size_mla(pl, p->kv_chunk, Ym, w.S, w.N);

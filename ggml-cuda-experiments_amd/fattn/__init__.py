@@ -329,7 +329,16 @@ def mla_v_view(k: View, v_off: int = MLA_DK - MLA_DV) -> View:
     """The V of an MLA call as a view of its K (include/fattn.h): the 512
     elements of every 576-element f16 cache row from element v_off on -- 64 when
     the RoPE dims come first (llama.cpp's order), 0 when the latent does.  Same
-    strides as K, so fattn_ext reads each cache row once (describe: v=k+<bytes>)."""
+    strides as K, so fattn_ext reads each cache row once (describe: v=k+<bytes>).
+
+    A Q8_0 / Q4_0 K view (18 blocks per row): v_off is 0, 32 or 64 elements --
+    whole blocks -- and the pointer advances by row_size(type, v_off)."""
+    if k.type in (TYPE_Q8_0, TYPE_Q4_0):
+        if int(k.ne[0]) != MLA_DK or int(k.nb[0]) != BLOCK_BYTES[k.type]:
+            raise ValueError("mla_v_view: a quantised K must have 576-element rows of whole blocks")
+        if v_off not in (0, 32, 64):
+            raise ValueError("mla_v_view: v_off is 0, 32 or 64 elements (whole blocks) for a quantised K")
+        return View(k.ptr + row_size(k.type, v_off), k.type, (MLA_DV,) + tuple(int(x) for x in k.ne[1:]), tuple(k.nb))
     if k.type != TYPE_F16 or int(k.ne[0]) != MLA_DK or int(k.nb[0]) != 2:
         raise ValueError("mla_v_view: K must be an f16 view with 576-element rows")
     if v_off % 8 or not 0 <= v_off <= MLA_DK - MLA_DV:

@@ -52,7 +52,10 @@
 //                        first) or 64 (RoPE dims first, llama.cpp's order) -- a view of K, so each
 //                        cache row is read once; --heads (default 16) / --kv-size / --n-q / --mask
 //                        / --iters / --tol / --cpu-only / --dump apply, scale = 1 / sqrt(192); the
-//                        CPU reference is plain C++ over K dim 576 and V dim 512
+//                        CPU reference is plain C++ over K dim 576 and V dim 512.  With
+//                        --kv-type q8_0|q4_0 the cache rows are quantised (fattn_quantize; on the
+//                        host with --cpu-only), V is the view --v-off 0|32|64 elements (whole
+//                        blocks) in, and the reference takes the blocks dequantised on the host
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -329,12 +332,63 @@ void cpu_reference_mla(const std::vector<float>& q, const std::vector<float>& kv
     for (auto& th : pool) th.join();
 }
 
+// ggml's quantize_row_q8_0_ref / quantize_row_q4_0_ref and their dequantisation
+// in plain C++ (every operation rounded on its own): `rows` rows of D values.
+// The --mla --cpu-only path has no device to quantise on.
+void quant_host_q80_q40(int type, const float* src, uint8_t* dst, int D, int64_t rows) {
+    const int bb = type == FATTN_TYPE_Q8_0 ? 34 : 18;
+    for (int64_t i = 0; i < rows * (D / 32); i++) {
+        const float* x = src + i * 32;
+        uint8_t* b = dst + i * bb;
+        float amax = 0.0f, mx = 0.0f;
+        for (int j = 0; j < 32; j++)
+            if (amax < fabsf(x[j])) amax = fabsf(x[j]), mx = x[j];
+        const float d = type == FATTN_TYPE_Q8_0 ? amax / 127.0f : mx / -8.0f;
+        const float id = d ? 1.0f / d : 0.0f;
+        const uint16_t dh = f2h(d);
+        b[0] = (uint8_t)(dh & 0xFF), b[1] = (uint8_t)(dh >> 8);
+        if (type == FATTN_TYPE_Q8_0) {
+            for (int j = 0; j < 32; j++) b[2 + j] = (uint8_t)(int8_t)roundf(x[j] * id);
+        } else {
+            for (int j = 0; j < 16; j++) {
+                const uint8_t q0 = (uint8_t)std::min(15, (int)(int8_t)(x[j] * id + 8.5f));
+                const uint8_t q1 = (uint8_t)std::min(15, (int)(int8_t)(x[j + 16] * id + 8.5f));
+                b[2 + j] = (uint8_t)(q0 | (q1 << 4));
+            }
+        }
+    }
+}
+void dequant_host_q80_q40(int type, const uint8_t* src, float* dst, int D, int64_t rows) {
+    const int bb = type == FATTN_TYPE_Q8_0 ? 34 : 18;
+    for (int64_t i = 0; i < rows * (D / 32); i++) {
+        const uint8_t* b = src + i * bb;
+        const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
+        float* y = dst + i * 32;
+        if (type == FATTN_TYPE_Q8_0) {
+            for (int j = 0; j < 32; j++) y[j] = (float)(int8_t)b[2 + j] * d;
+        } else {
+            for (int j = 0; j < 16; j++) {
+                y[j] = (float)((b[2 + j] & 0x0F) - 8) * d;
+                y[j + 16] = (float)((b[2 + j] >> 4) - 8) * d;
+            }
+        }
+    }
+}
+
 // the --mla flow: inputs from rand() in the order Q, KV, mask; the CPU
 // reference; fattn_ext with V = K + v_off elements; timing and the verification
-// line of the other branches
-int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool cpu_only, int iters, float tol, const char* dump) {
-    if (H <= 0 || N <= 0 || NQ <= 0 || (v_off != 0 && v_off != kMlaDK - kMlaDV)) {
-        fprintf(stderr, "--mla: --heads, --kv-size, --n-q positive, --v-off 0|64\n");
+// line of the other branches.  --kv-type q8_0 | q4_0: the cache rows are
+// quantised (fattn_quantize; on the host with --cpu-only), the reference takes
+// the blocks dequantised on the host, and V is the view v_off / 32 blocks in.
+int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mask_kind, bool cpu_only, int iters, float tol,
+            const char* dump) {
+    const bool quant = kv_type == FATTN_TYPE_Q8_0 || kv_type == FATTN_TYPE_Q4_0;
+    if (kv_type != FATTN_TYPE_F16 && !quant) {
+        fprintf(stderr, "--mla: --kv-type f16|q8_0|q4_0\n");
+        return 2;
+    }
+    if (H <= 0 || N <= 0 || NQ <= 0 || (v_off != 0 && v_off != kMlaDK - kMlaDV && !(quant && v_off == 32))) {
+        fprintf(stderr, "--mla: --heads, --kv-size, --n-q positive, --v-off 0|64 (q8_0 / q4_0: 0|32|64)\n");
         return 2;
     }
     const float scale = 1.0f / sqrtf(192.0f);  // the model family's: 128 nope + 64 rope dims before absorption
@@ -343,6 +397,30 @@ int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool 
     random_fill(kv);
     random_fill(mask);
     if (mask_kind != "random") std::fill(mask.begin(), mask.end(), 0.0f);
+    const size_t rowb = quant ? fattn_row_size(kv_type, kMlaDK) : (size_t)kMlaDK * 2;
+    std::vector<uint8_t> blocks;
+    if (quant) {
+        blocks.resize(rowb * N);
+        if (cpu_only) {
+            quant_host_q80_q40(kv_type, kv.data(), blocks.data(), kMlaDK, N);
+        } else {
+            float* d_f;
+            void* d_b;
+            HIP_CHECK(hipMalloc(&d_f, 4 * kv.size()));
+            HIP_CHECK(hipMalloc(&d_b, blocks.size()));
+            HIP_CHECK(hipMemcpy(d_f, kv.data(), 4 * kv.size(), hipMemcpyHostToDevice));
+            const int qrc = fattn_quantize(kv_type, d_f, d_b, kMlaDK, N, nullptr);
+            if (qrc) {
+                fprintf(stderr, "quantize failed: %s\n", fattn_strerror(qrc));
+                return 2;
+            }
+            HIP_CHECK(hipDeviceSynchronize());
+            HIP_CHECK(hipMemcpy(blocks.data(), d_b, blocks.size(), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipFree(d_f));
+            HIP_CHECK(hipFree(d_b));
+        }
+        dequant_host_q80_q40(kv_type, blocks.data(), kv.data(), kMlaDK, N);  // (the reference rounds to f16: h(q d))
+    }
     const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
     std::vector<float> ref((size_t)kMlaDV * H * NQ), got(ref.size());
     cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads);
@@ -360,8 +438,12 @@ int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool 
     }
     const bool has_mask = mask_kind != "none";
     const int mask_rows = (NQ + 31) / 32 * 32, Np = N + (N & 1);
-    std::vector<uint16_t> kv16(kv.size()), mask16((size_t)Np * mask_rows, f2h(0.0f));
-    for (size_t i = 0; i < kv.size(); i++) kv16[i] = f2h(kv[i]);
+    std::vector<uint16_t> mask16((size_t)Np * mask_rows, f2h(0.0f));
+    if (!quant) {
+        blocks.resize(rowb * N);
+        uint16_t* kv16 = (uint16_t*)blocks.data();
+        for (size_t i = 0; i < kv.size(); i++) kv16[i] = f2h(kv[i]);
+    }
     for (int r = 0; r < NQ; r++)
         for (int i = 0; i < N; i++) mask16[(size_t)r * Np + i] = f2h(mask[(size_t)r * N + i]);
     hipStream_t st;
@@ -370,18 +452,19 @@ int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool 
     void *d_kv, *d_mask, *d_ws;
     HIP_CHECK(hipMalloc(&d_q, 4 * query.size()));
     HIP_CHECK(hipMalloc(&d_out, 4 * got.size()));
-    HIP_CHECK(hipMalloc(&d_kv, 2 * kv16.size()));
+    HIP_CHECK(hipMalloc(&d_kv, blocks.size()));
     HIP_CHECK(hipMalloc(&d_mask, 2 * mask16.size()));
     HIP_CHECK(hipMemcpyAsync(d_q, query.data(), 4 * query.size(), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(d_kv, kv16.data(), 2 * kv16.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_kv, blocks.data(), blocks.size(), hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemcpyAsync(d_mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, st));
     fattn_params p;
     std::memset(&p, 0, sizeof(p));
-    const int64_t rk = kMlaDK * 2;
+    const int64_t rk = (int64_t)rowb, eb = quant ? (int64_t)fattn_row_size(kv_type, 32) : 2;
     p.q = {d_q, FATTN_TYPE_F32, 0, {kMlaDK, NQ, H, 1}, {4, (int64_t)H * kMlaDK * 4, kMlaDK * 4, (int64_t)NQ * H * kMlaDK * 4}};
-    p.k = {d_kv, FATTN_TYPE_F16, 0, {kMlaDK, N, 1, 1}, {2, rk, rk * N, rk * N}};
+    p.k = {d_kv, kv_type, 0, {kMlaDK, N, 1, 1}, {eb, rk, rk * N, rk * N}};
     // V: a view of the same rows, v_off elements in (ggml_view of the cache's latent part)
-    p.v = {(const uint8_t*)d_kv + 2 * v_off, FATTN_TYPE_F16, 0, {kMlaDV, N, 1, 1}, {2, rk, rk * N, rk * N}};
+    p.v = {(const uint8_t*)d_kv + (quant ? (int64_t)fattn_row_size(kv_type, v_off) : 2 * v_off), kv_type, 0, {kMlaDV, N, 1, 1},
+           {eb, rk, rk * N, rk * N}};
     if (has_mask)
         p.mask = {d_mask, FATTN_TYPE_F16, 0, {Np, mask_rows, 1, 1},
                   {2, (int64_t)Np * 2, (int64_t)Np * 2 * mask_rows, (int64_t)Np * 2 * mask_rows}};
@@ -434,7 +517,7 @@ int run_mla(int H, int N, int NQ, int v_off, const std::string& mask_kind, bool 
             }
         }
     const float worst_rel = max_diff / std::max(max_ref, 1e-30f);
-    const double bytes = (double)(kMlaDK + kMlaDV) * H * NQ * 4 + 2.0 * kMlaDK * N + (has_mask ? 2.0 * N * NQ : 0.0);
+    const double bytes = (double)(kMlaDK + kMlaDV) * H * NQ * 4 + (double)rowb * N + (has_mask ? 2.0 * N * NQ : 0.0);
     const double flops = 2.0 * N * (kMlaDK + kMlaDV) * H * NQ;
     printf("\ncuda time: %.4f ms  (%.1f GB/s, %.3f TFLOP/s; median of %d)\n", millis, bytes / millis / 1e6,
            flops / millis / 1e9, iters);
@@ -531,7 +614,7 @@ int main(int argc, const char* argv[]) {
         printf("invalid num_warps, should be 2, 4, 8\n");  // kernel_test.h:176-178 (informational)
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
     // (the model family's smallest head count unless --heads says otherwise)
-    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, mask_kind, cpu_only, iters, tol, dump);
+    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)

@@ -77,7 +77,7 @@ enum fattn_status {
     FATTN_OK = 0,
     FATTN_ERR_INVALID_ARG = -1,     /* NULL pointer, bad shape, ne not divisible */
     FATTN_ERR_UNSUPPORTED_TYPE = -2,
-    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 -- or the MLA pair, K 576 with V 512 */
+    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 -- or the MLA pair, K 576 with V 512 (f16, Q8_0 or Q4_0) */
     FATTN_ERR_BAD_STRIDE = -4,       /* layout the kernels cannot address */
     FATTN_ERR_WORKSPACE = -5,        /* workspace too small */
     FATTN_ERR_LAUNCH = -6,           /* HIP launch failure */
@@ -221,10 +221,36 @@ int fattn_ext(const fattn_params* p, void* stream);
  *   (fattn_workspace_size(p) a function of p alone, 0 for a single chunk;
  *   several chunks merge in a second launch, nothing is allocated, the launch
  *   is capturable), NaN for a row masked -inf everywhere and zeros with sinks.
+ *   A Q8_0 OR Q4_0 CACHE (llama.cpp's --cache-type-k; with MLA there is no V
+ *   cache, so K's type is the cache's type):
+ *   k    Q8_0 | Q4_0  ne = [576, N, Hkv, Skv]: 18 blocks per row, nb[0] the
+ *        block size (34 / 18 B), rows of 612 / 324 B, k.nb[1] >= that (padded,
+ *        not overlapped)
+ *   v    K's type, ne = [512, N, Hkv, Skv], and it MUST be a view of K:
+ *        v.data == k.data + b * nb[0] with b = 0, 1 or 2 whole blocks (byte 0 /
+ *        34 / 68 for Q8_0, 0 / 18 / 36 for Q4_0; b = 2 is llama.cpp's row with
+ *        the 64 RoPE dims first, ggml_row_size(type_k, 64)), v.nb[0] == k.nb[0]
+ *        and v.nb[1..3] == k.nb[1..3] (a stride of a one-element dim is not
+ *        compared)
+ *   k.data and nb[1..3]: multiples of 4 (FATTN_ERR_ALIGNMENT) -- these rows are
+ *   whole dwords, not 16-B multiples, and a natural cache (612-B row stride)
+ *   works unpadded.  v.data is k.data plus whole blocks (2 mod 4 one block in):
+ *   only K's base is addressed.  Spans below 4 GiB as above.  q, mask, dst, every
+ *   scalar, sinks, kv_chunk and the workspace rules are those of the f16 form:
+ *   the workspace is 0 bytes for one chunk and the f16 view plan's for several
+ *   (the cache is never staged to f16 in memory).
+ *   Values: element (n, j) of K is the f16 rounding of ggml's dequantisation,
+ *   h(qs[j] * d) for Q8_0 and h((nibble - 8) * d) for Q4_0 (the product is exact
+ *   in f32: one rounding); V is elements [32 b, 32 b + 512) of the same.  A
+ *   launch returns bit for bit what the f16 form returns over an f16 cache
+ *   holding those values (same shape, mask, scalars, sinks and kv_chunk).
+ *   fattn_describe: fattn_mla_kernel<q8_0,DK576,DV512,...,v=k+68>.
  *   Refused: q.ne[0] == 576 with any K / V row lengths but (576, 512)
- *   FATTN_ERR_UNSUPPORTED_HEAD_DIM; a quantised or transposed K / V at this
- *   shape FATTN_ERR_UNSUPPORTED_TYPE.  Every other head dim keeps
- *   k.ne[0] == v.ne[0] == q.ne[0] (FATTN_ERR_INVALID_ARG). */
+ *   FATTN_ERR_UNSUPPORTED_HEAD_DIM (looked at before the types); a transposed V,
+ *   Q4_1 / Q5_0 / Q5_1, K and V of different types, or a Q8_0 / Q4_0 K whose V is
+ *   not such a view (a buffer of its own, an offset of no 0 / 1 / 2 whole
+ *   blocks, other strides) FATTN_ERR_UNSUPPORTED_TYPE.  Every other head dim
+ *   keeps k.ne[0] == v.ne[0] == q.ne[0] (FATTN_ERR_INVALID_ARG). */
 
 /* fattn_ext with attention sinks: src[4] of ggml's GGML_OP_FLASH_ATTN_EXT (the
  * gpt-oss family).  A sink is one extra logit per q head: it joins the softmax

@@ -16,6 +16,15 @@ algorithmic bytes (Q, the cache rows once, the mask, dst) and of 2.5 PFLOP/s
 over 2 * S * H * N * (576 + 512) flops.
 
   python tools/bench_mla.py --rounds 7 --steps 50 --json profiles/mla/bench.json
+
+--kv-type q8_0 / q4_0 (repeatable) times the f16 view form against the same
+rows quantised (fattn.quantize; V the view two blocks in), alternating in the
+same way, instead of view against own.  R then comes from the smallest cache
+among the forms, every form rotates over the same R, and each record carries
+`stored_bytes` (the cache rows as stored: 1152 / 612 / 324 B each) with its
+fraction of 8 TB/s, `hbm_frac_stored`, next to the algorithmic figures.
+
+  python tools/bench_mla.py --kv-type q8_0 --kv-type q4_0 --json profiles/mla_quant/bench.json
 """
 import argparse
 import json
@@ -42,6 +51,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--json", default="")
+    ap.add_argument("--kv-type", action="append", default=[], choices=["q8_0", "q4_0"])
     args = ap.parse_args()
     import ctypes as C
     import torch
@@ -58,9 +68,17 @@ def main():
         H, N, S = SHAPES[name]["H"], SHAPES[name]["N"], SHAPES[name]["S"]
         g = torch.Generator(device=dev)
         g.manual_seed(4321)
-        R = max(4, -(-(512 << 20) // (S * N * DK * 2)))
-        caches = [torch.randn((S * N, DK), generator=g, device=dev).to(torch.float16) for _ in range(R)]
-        owns = [c[:, DK - DV:].contiguous() for c in caches]
+        qtypes = {t: fattn.TYPE_NAMES[t] for t in args.kv_type}
+        row_min = min([DK * 2] + [fattn.row_size(t, DK) for t in qtypes.values()])
+        R = max(4, -(-(512 << 20) // (S * N * row_min)))
+        caches, qcaches = [], {t: [] for t in qtypes}
+        for _ in range(R):
+            x = torch.randn((S * N, DK), generator=g, device=dev)
+            caches.append(x.to(torch.float16))
+            for t, ty in qtypes.items():
+                qcaches[t].append(fattn.quantize(x, ty))
+            del x
+        owns = [] if qtypes else [c[:, DK - DV:].contiguous() for c in caches]
         q = torch.randn((S, 1, H, DK), generator=g, device=dev)
         npad = (N + 63) // 64 * 64
         mask = (torch.rand((1, npad), generator=g, device=dev) * 2 - 1).to(torch.float16)
@@ -69,16 +87,23 @@ def main():
         flops = 2 * S * H * N * (DK + DV)
         scale = 1.0 / 192 ** 0.5
         kv0 = fattn.kv_view(caches[0], fattn.TYPE_F16, DK, N, 1, S)
-        forms = {
-            "view": (fattn.mla_v_view(kv0), [c.data_ptr() + 2 * (DK - DV) for c in caches]),
-            "own": (fattn.kv_view(owns[0], fattn.TYPE_F16, DV, N, 1, S), [o.data_ptr() for o in owns]),
-        }
+        # form -> (K view, V view, K pointers, V pointers, bytes of a stored row)
+        forms = {"view": (kv0, fattn.mla_v_view(kv0), [c.data_ptr() for c in caches],
+                          [c.data_ptr() + 2 * (DK - DV) for c in caches], DK * 2)}
+        if not qtypes:
+            forms["own"] = (kv0, fattn.kv_view(owns[0], fattn.TYPE_F16, DV, N, 1, S), forms["view"][2],
+                            [o.data_ptr() for o in owns], DK * 2)
+        for t, ty in qtypes.items():
+            kq = fattn.kv_view(qcaches[t][0], ty, DK, N, 1, S)
+            voff = fattn.row_size(ty, DK - DV)
+            forms[t] = (kq, fattn.mla_v_view(kq), [c.data_ptr() for c in qcaches[t]],
+                        [c.data_ptr() + voff for c in qcaches[t]], fattn.row_size(ty, DK))
         graphs = {}
-        for form, (vv, vptrs) in forms.items():
-            att = fattn.Attention(fattn.q_view(q), kv0, vv, fattn.mask_view(mask), outs[0], scale)
+        for form, (kk, vv, kptrs, vptrs, _row) in forms.items():
+            att = fattn.Attention(fattn.q_view(q), kk, vv, fattn.mask_view(mask), outs[0], scale)
 
-            def step(i, att=att, vptrs=vptrs):
-                att.retarget(k=caches[i % R].data_ptr(), v=vptrs[i % R], dst=outs[i % R].data_ptr())
+            def step(i, att=att, kptrs=kptrs, vptrs=vptrs):
+                att.retarget(k=kptrs[i % R], v=vptrs[i % R], dst=outs[i % R].data_ptr())
                 att()
 
             gs.wait_stream(torch.cuda.current_stream(dev))
@@ -99,7 +124,8 @@ def main():
                 graphs[form][0].replay()
             torch.cuda.synchronize()
             graphs[form] += (outs[0].clone(),)
-        same = bool(torch.equal(graphs["view"][3], graphs["own"][3]))
+        # (a quantised cache holds other values than the f16 one: no such comparison)
+        same = bool(torch.equal(graphs["view"][3], graphs["own"][3])) if not qtypes else None
         us = {form: [] for form in graphs}
         for r in range(args.rounds):
             for form, (gr, *_rest) in graphs.items():
@@ -120,9 +146,12 @@ def main():
                        min_us=round(min(v), 3), max_us=round(max(v), 3), rounds=len(v), steps=args.steps, rotated_caches=R,
                        alg_bytes=alg, flops=flops, hbm_frac=round(alg / (med * 1e-6) / HBM_BPS, 4),
                        mfma_frac=round(flops / (med * 1e-6) / MFMA_FLOPS, 4), forms_bit_equal=same)
+            if qtypes:
+                stored = S * N * forms[form][4]
+                rec.update(stored_bytes=stored, hbm_frac_stored=round(stored / (med * 1e-6) / HBM_BPS, 4))
             results.append(rec)
             print(json.dumps(rec), flush=True)
-        del caches, owns, outs, graphs
+        del caches, qcaches, owns, outs, graphs
         torch.cuda.empty_cache()
     if args.json:
         os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
