@@ -539,6 +539,23 @@ constexpr float v_code_off() {
 template <int VT, int D>
 constexpr int corr_len() { return (D + QK - 1) / QK * (has_min(VT) ? 2 : 1); }
 
+// Column-packed V scales (one-row tiles, Q8_0 / Q4_0 V): of the 16 MFMA columns
+// of a one-row tile only column 0 is live, so columns 0 .. D/QK - 1 all carry the
+// tile's one query row (same Q operand, mask row, slope: the same S^T, softmax
+// state and P on each), and column b's lanes fold the scales of V block b alone
+// into P -- one P'_b per lane, one corr -- where the plain form builds P'_b of
+// every block on every lane.  Block b's O^T tiles 2b, 2b+1 are then read from
+// column b; that column holds there exactly what column 0 holds in the plain
+// form (same operands, same MFMAs, same order): bit-identical results.
+// EPI: the kernel's epilogue (split_epilogue); 1 and 2 are the one-row forms.
+// (Q4_1 / Q5_0 / Q5_1 keep the plain form: their kernels sit at 2 waves per
+// SIMD by the qh words and the second accumulator, not by the scales.)
+template <int VT, int EPI>
+constexpr bool col_packed() { return EPI != 0 && (VT == FATTN_TYPE_Q8_0 || VT == FATTN_TYPE_Q4_0); }
+// f32 accumulators beside O in the kernel: one corr when column-packed
+template <int VT, int D, bool CP>
+constexpr int corr_regs() { return CP ? 1 : corr_len<VT, D>(); }
+
 // The f16 scale of block b of a raw ggml row sits at byte BB*b.  row_scales()
 // fetches the dwords holding all of a row's scales (2 x ds_read2_b32 for 4
 // blocks); scale_bits() extracts block b's 16 bits.
@@ -836,7 +853,7 @@ __device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, i
 // fa_reduce math as combine_tile (src/flash_row_float.h:415-472), fixed order.
 constexpr int kWaveMergeParts = 64;  // parts per tile (one (m, l) pair per lane)
 constexpr int kWaveMergeBatch = 32;  // parts loaded per round trip
-template <int D, bool VQ8, int NW = kSplitWaves>
+template <int D, bool VQ8, int NW = kSplitWaves, bool CP = false>
 __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f32x4 (&o)[D / 16], float m_run,
                                                     float l_tot, int chunk, int wave, int lane, int qt, int hs,
                                                     int ik2, int iq3, int y) {
@@ -850,7 +867,22 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
     const int part = chunk * NW + wave;
     float* po = a.ws_o + (tile * NP + part) * D;  // row 0 of the part: [NP][D] per tile
     auto bits = [](float x) { return __builtin_bit_cast(uint32_t, x); };
-    if (m == 0) {  // column 0 = the tile's row; its dims sit on lanes 0, 16, 32, 48
+    if constexpr (CP) {  // block b's dims sit on column b (col_packed): one masked write per block
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            if (m != b) continue;
+            if constexpr (VQ8) {
+                const f32x4 e = o[2 * b], od = o[2 * b + 1];
+                st_sc1(po + 32 * b + 8 * g, u32x4{bits(e.x), bits(od.x), bits(e.y), bits(od.y)});
+                st_sc1(po + 32 * b + 8 * g + 4, u32x4{bits(e.z), bits(od.z), bits(e.w), bits(od.w)});
+            } else {
+#pragma unroll
+                for (int c = 2 * b; c < 2 * b + 2; c++)
+                    st_sc1(po + 16 * c + 4 * g, u32x4{bits(o[c].x), bits(o[c].y), bits(o[c].z), bits(o[c].w)});
+            }
+        }
+        if (lane == 0) st_sc1_x2(a.ws_ml + 2 * (tile * NP + part), u32x2{bits(m_run), bits(l_tot)});
+    } else if (m == 0) {  // column 0 = the tile's row; its dims sit on lanes 0, 16, 32, 48
         if constexpr (VQ8) {
 #pragma unroll
             for (int b = 0; b < NB; b++) {
@@ -1111,7 +1143,7 @@ __device__ __forceinline__ void merge_row_parts_h(const uint16_t* parts_o, const
 // workgroup on the tile's arrival word, and the last workgroup's wave 0 merges
 // the chunks (merge_row_parts).  The cross-workgroup hand-off carries one row
 // per workgroup instead of one per wave.
-template <int D, bool VQ8, int NW>
+template <int D, bool VQ8, int NW, bool CP = false>
 __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o)[D / 16], float m_run, float l_tot,
                                              int chunk, int wave, int lane, int qt, int hs, int ik2, int iq3,
                                              int y, uint8_t* smem, int region) {
@@ -1122,7 +1154,21 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
     constexpr int PPR = 64 % LPP == 0 ? 64 / LPP : 1;  // (D = 80 / 96: one part per lane row)
     const int g = lane >> 4, m = lane & 15;
     float* so = (float*)(smem + wave * region);  // [D] O row, then (m, l)
-    if (m == 0) {  // column 0 = the tile's row; its dims sit on lanes 0, 16, 32, 48
+    if constexpr (CP) {  // block b's dims sit on column b (col_packed): one masked write per block
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            if (m != b) continue;
+            if constexpr (VQ8) {
+                const f32x4 e = o[2 * b], od = o[2 * b + 1];
+                *(f32x4*)(so + 32 * b + 8 * g) = f32x4{e.x, od.x, e.y, od.y};
+                *(f32x4*)(so + 32 * b + 8 * g + 4) = f32x4{e.z, od.z, e.w, od.w};
+            } else {
+                *(f32x4*)(so + 32 * b + 4 * g) = o[2 * b];
+                *(f32x4*)(so + 32 * b + 16 + 4 * g) = o[2 * b + 1];
+            }
+        }
+        if (lane == 0) *(f32x2*)(so + D) = f32x2{m_run, l_tot};
+    } else if (m == 0) {  // column 0 = the tile's row; its dims sit on lanes 0, 16, 32, 48
         if constexpr (VQ8) {
 #pragma unroll
             for (int b = 0; b < NB; b++) {
@@ -1238,9 +1284,9 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
 // alias step buffers, so wait for every wave before writing them.
 template <int KT, int VT, int D, int NW, int EPI>
 __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D / 16], float m_run, float l_run,
-                                               float (&corr)[corr_len<VT, D>()], int wave, int lane, int qt, int hs, int ik2,
-                                               int iq3, int y, int chunk, uint8_t* smem, int region, bool active,
-                                               bool sync_first) {
+                                               float (&corr)[corr_regs<VT, D, col_packed<VT, EPI>()>()], int wave, int lane,
+                                               int qt, int hs, int ik2, int iq3, int y, int chunk, uint8_t* smem, int region,
+                                               bool active, bool sync_first) {
     using C = SplitCfg<KT, VT, D>;
     constexpr int NB = D / QK;
     constexpr int NC = D / 16;
@@ -1248,12 +1294,20 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     constexpr bool kVQ8 = C::VTT == FATTN_TYPE_Q8_0;
     constexpr bool kVQ = C::VTT != FATTN_TYPE_F16;
     constexpr float kVOff = v_code_off<C::VTT>();
+    constexpr bool CP = col_packed<C::VTT, EPI>();
     const int g = lane >> 4;
     const int m = lane & 15;
     // split_step keeps the reference max in natural units; the merges work in log2
     m_run = m_run == kNegInf ? kNegInf : m_run * 1.4426950408889634f;
     const float l_tot = grp4_sum(l_run);
-    if constexpr (kVQ) {
+    if constexpr (CP) {
+        // column b's one corr is block b's; the tiles of block b are read from column b
+        // alone (wave_merge_epilogue, wg_row_merge), every other tile of that column is
+        // never read
+        const float cb = kVOff * grp4_sum(corr[0]);
+#pragma unroll
+        for (int c = 0; c < NC; c++) o[c] -= cb;
+    } else if constexpr (kVQ) {
         // O^T tiles of block b (columns 32b..32b+31) carry kVOff * sum(P'_b) too
 #pragma unroll
         for (int b = 0; b < NB; b++) {
@@ -1269,10 +1323,10 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     }
     if constexpr (EPI == 1) {
         static_assert(D == 128, "per-wave merge: lane i <-> dims 2i, 2i+1");
-        wave_merge_epilogue<D, kVQ8, NW>(a, o, m_run, l_tot, chunk, wave, lane, qt, hs, ik2, iq3, y);
+        wave_merge_epilogue<D, kVQ8, NW, CP>(a, o, m_run, l_tot, chunk, wave, lane, qt, hs, ik2, iq3, y);
         return;
     } else if constexpr (EPI == 2) {
-        wg_row_merge<D, kVQ8, NW>(a, o, m_run, l_tot, chunk, wave, lane, qt, hs, ik2, iq3, y, smem, region);
+        wg_row_merge<D, kVQ8, NW, CP>(a, o, m_run, l_tot, chunk, wave, lane, qt, hs, ik2, iq3, y, smem, region);
         return;
     }
     constexpr int MS = C::kMergeStride;
@@ -1452,6 +1506,54 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     FATTN_SSTAMP(13);
 }
 
+// The P.V MFMA pair of block b of a Q8_0 / Q4_0 V step (split_step): the A
+// operands are the exact integer codes of this lane's 8 rows (4g..4g+3,
+// 16+4g..16+4g+3) as f16 magic numbers 0x64xx = 1024 + xx (v_code_off), `pbd`
+// the block's scales folded into P.  Q8_0: one u16 per row carries columns 2i
+// (-> tile E_b = oe) and 2i+1 (-> tile O_b = oo), bytes xor 0x80: 1152 + q.
+// Q4_0: byte i carries column i (low nibble, oe) and 16 + i (high nibble, oo):
+// 1032 + (nib - 8).  b is unrolled at every call site.
+template <int VT, int D>
+__device__ __forceinline__ void pv_block_q(const uint8_t* vb, int b, int g, int i16, const f16x8& pbd, f32x4& oe,
+                                           f32x4& oo) {
+    static_assert(VT == FATTN_TYPE_Q8_0 || VT == FATTN_TYPE_Q4_0, "");
+    constexpr int BB = TypeInfo<VT>::block_bytes;
+    constexpr int RV = row_bytes<VT, D>();
+    const int rA = 4 * g, rB = 16 + 4 * g;
+    uint32_t w[8];
+    u32x4 a0, a1;
+    if constexpr (VT == FATTN_TYPE_Q8_0) {
+        const uint8_t* cp = vb + b * BB + 2 + 2 * i16;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            w[r] = *(const uint16_t*)(cp + (rA + r) * RV);
+            w[4 + r] = *(const uint16_t*)(cp + (rB + r) * RV);
+        }
+#pragma unroll
+        for (int pr = 0; pr < 4; pr++) {
+            // bytes [e_r, o_r, e_r+1, o_r+1] -> xor 0x80 -> f16 magic 0x64xx
+            const uint32_t t2 = (w[2 * pr] | (w[2 * pr + 1] << 16)) ^ 0x80808080u;
+            a0[pr] = perm_b32(0x64646464u, t2, 0x04020400u);
+            a1[pr] = perm_b32(0x64646464u, t2, 0x04030401u);
+        }
+    } else {
+        const uint8_t* cp = vb + b * BB + 2 + i16;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            w[r] = cp[(rA + r) * RV];
+            w[4 + r] = cp[(rB + r) * RV];
+        }
+#pragma unroll
+        for (int pr = 0; pr < 4; pr++) {
+            const uint32_t x = w[2 * pr] | (w[2 * pr + 1] << 16);
+            a0[pr] = (x & 0x000F000Fu) | 0x64006400u;
+            a1[pr] = ((x >> 4) & 0x000F000Fu) | 0x64006400u;
+        }
+    }
+    oe = mfma16(__builtin_bit_cast(f16x8, a0), pbd, oe);
+    oo = mfma16(__builtin_bit_cast(f16x8, a1), pbd, oo);
+}
+
 // One 32-position step of one wave: S^T = K.Q^T for the step's two 16-row
 // key tiles, scale + mask, online softmax of the wave's 16 packed columns,
 // O^T += V^T.P^T.  `buf` is the step's LDS image [K rows | V rows | mask rows];
@@ -1464,10 +1566,10 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
 // this column's q head's); a template parameter, because the arguments and
 // the slope held across the loop by a wave-uniform branch cost the bodies at
 // their register limit spills (profiles/op_params/registers.txt).
-template <int KT, int VT, int D, bool HM, bool XF, typename WaitV>
+template <int KT, int VT, int D, bool HM, bool XF, bool CP, typename WaitV>
 __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mrow,
                                            float slope, int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
-                                           f32x4 (&o)[D / 16], float (&corr)[corr_len<VT, D>()], WaitV&& wait_v) {
+                                           f32x4 (&o)[D / 16], float (&corr)[corr_regs<VT, D, CP>()], WaitV&& wait_v) {
     using C = SplitCfg<KT, VT, D>;
     constexpr int NB = (D + QK - 1) / QK;  // k-steps of S^T (D = 80: the last one half zero)
     constexpr int NC = D / 16;
@@ -1553,7 +1655,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
             for (int c = 0; c < NC; c++) o[c] *= alpha;
             if constexpr (kVQ) {
 #pragma unroll
-                for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] *= alpha;
+                for (int b = 0; b < corr_regs<VT, D, CP>(); b++) corr[b] *= alpha;
             }
         }
         m_run = m_new;
@@ -1573,6 +1675,37 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
     if constexpr (C::VTT == FATTN_TYPE_F16) {
 #pragma unroll
         for (int c = 0; c < NC; c++) o[c] = mfma16(v_operand_f16<VT, D>(vb, c, g, i16), pb, o[c]);
+    } else if constexpr (CP) {
+        // column-packed (col_packed): this lane's column c folds block min(c, NB - 1)
+        // alone -- the scales of its 8 rows (4g..4g+3, 16+4g..16+4g+3) as u16 reads at
+        // a per-lane offset (columns >= NB: a valid block, their tiles are never
+        // read), one P' and one corr; every block's MFMA pair takes that P'
+        static_assert(D % QK == 0, "quantised rows are whole blocks");
+        constexpr int BB = TypeInfo<C::VTT>::block_bytes;
+        const int rA = 4 * g, rB = 16 + 4 * g;
+        const uint8_t* sp = vb + BB * min(i16, NB - 1);
+        uint32_t sw[8];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            sw[r] = *(const uint16_t*)(sp + (rA + r) * C::rowV);
+            sw[4 + r] = *(const uint16_t*)(sp + (rB + r) * C::rowV);
+        }
+        const f16x2 d01 = as_h2(perm_b32(sw[1], sw[0], 0x05040100u)), d23 = as_h2(perm_b32(sw[3], sw[2], 0x05040100u));
+        const f16x2 d45 = as_h2(perm_b32(sw[5], sw[4], 0x05040100u)), d67 = as_h2(perm_b32(sw[7], sw[6], 0x05040100u));
+        f16x8 pbd;
+        pbd.s01 = pb.s01 * d01;
+        pbd.s23 = pb.s23 * d23;
+        pbd.s45 = pb.s45 * d45;
+        pbd.s67 = pb.s67 * d67;
+        const f16x2 one2 = {(f16)1.0f, (f16)1.0f};
+        corr[0] = __builtin_amdgcn_fdot2(pbd.s01, one2, corr[0], false);
+        corr[0] = __builtin_amdgcn_fdot2(pbd.s23, one2, corr[0], false);
+        corr[0] = __builtin_amdgcn_fdot2(pbd.s45, one2, corr[0], false);
+        corr[0] = __builtin_amdgcn_fdot2(pbd.s67, one2, corr[0], false);
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            pv_block_q<C::VTT, D>(vb, b, g, i16, pbd, o[2 * b], o[2 * b + 1]);
+        }
     } else {
         const int rA = 4 * g, rB = 16 + 4 * g;
 #pragma unroll
@@ -1605,26 +1738,9 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
             corr[b] = __builtin_amdgcn_fdot2(pbd.s23, one2, corr[b], false);
             corr[b] = __builtin_amdgcn_fdot2(pbd.s45, one2, corr[b], false);
             corr[b] = __builtin_amdgcn_fdot2(pbd.s67, one2, corr[b], false);
-            if constexpr (kVQ8) {
-                // one u16 per row carries columns 2i (-> tile E_b) and 2i+1 (-> tile O_b)
-                const uint8_t* cp = vb + b * BB + 2 + 2 * i16;
-                uint32_t w[8];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    w[r] = *(const uint16_t*)(cp + (rA + r) * C::rowV);
-                    w[4 + r] = *(const uint16_t*)(cp + (rB + r) * C::rowV);
-                }
-                u32x4 ae, ao;  // f16 pairs 1152 + q (exact)
-#pragma unroll
-                for (int pr = 0; pr < 4; pr++) {
-                    // bytes [e_r, o_r, e_r+1, o_r+1] -> xor 0x80 -> f16 magic 0x64xx
-                    const uint32_t t2 = (w[2 * pr] | (w[2 * pr + 1] << 16)) ^ 0x80808080u;
-                    ae[pr] = perm_b32(0x64646464u, t2, 0x04020400u);
-                    ao[pr] = perm_b32(0x64646464u, t2, 0x04030401u);
-                }
-                o[2 * b] = mfma16(__builtin_bit_cast(f16x8, ae), pbd, o[2 * b]);
-                o[2 * b + 1] = mfma16(__builtin_bit_cast(f16x8, ao), pbd, o[2 * b + 1]);
-            } else if constexpr (is_kv_ext(C::VTT)) {
+            if constexpr (!is_kv_ext(C::VTT)) {  // Q8_0 / Q4_0
+                pv_block_q<C::VTT, D>(vb, b, g, i16, pbd, o[2 * b], o[2 * b + 1]);
+            } else {
                 // Q4_1 / Q5_0 / Q5_1: byte i of qs carries column i (low nibble) and 16 + i
                 // (high nibble), bits i and 16 + i of the row's qh their fifth bits
                 constexpr int VTT = C::VTT;
@@ -1673,23 +1789,6 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
                         al[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c040c00u) << 4;
                         ah[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c060c02u) << 4;
                     }
-                }
-                o[2 * b] = mfma16(__builtin_bit_cast(f16x8, al), pbd, o[2 * b]);
-                o[2 * b + 1] = mfma16(__builtin_bit_cast(f16x8, ah), pbd, o[2 * b + 1]);
-            } else {  // Q4_0: byte i carries column i (low nibble) and 16+i (high nibble)
-                const uint8_t* cp = vb + b * BB + 2 + i16;
-                uint32_t w[8];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    w[r] = cp[(rA + r) * C::rowV];
-                    w[4 + r] = cp[(rB + r) * C::rowV];
-                }
-                u32x4 al, ah;  // f16 pairs 1032 + (nib - 8) (exact)
-#pragma unroll
-                for (int pr = 0; pr < 4; pr++) {
-                    const uint32_t x = w[2 * pr] | (w[2 * pr + 1] << 16);
-                    al[pr] = (x & 0x000F000Fu) | 0x64006400u;
-                    ah[pr] = ((x >> 4) & 0x000F000Fu) | 0x64006400u;
                 }
                 o[2 * b] = mfma16(__builtin_bit_cast(f16x8, al), pbd, o[2 * b]);
                 o[2 * b + 1] = mfma16(__builtin_bit_cast(f16x8, ah), pbd, o[2 * b + 1]);
@@ -1748,8 +1847,10 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     }
     if (a.rk3 != 1) ik3 = iq3 / a.rk3;
 
-    // this lane's MFMA column m = i16 -> (query row, q head)
-    const int m = i16;
+    // this lane's MFMA column m = i16 -> (query row, q head); column-packed
+    // (col_packed): columns 0 .. D/QK - 1 all carry the tile's one row, packed row 0
+    constexpr bool CP = col_packed<C::VTT, EPI>();
+    const int m = (CP && i16 < D / QK) ? 0 : i16;
     const int mq = div_R(a, m);
     const int mh = hs * a.R + (m - mq * a.R);
     const int iq1 = qt * a.QPT + mq;
@@ -1884,9 +1985,9 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     f32x4 o[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) o[c] = f32x4{0, 0, 0, 0};
-    float corr[corr_len<VT, D>()];
+    float corr[corr_regs<VT, D, CP>()];
 #pragma unroll
-    for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] = 0.0f;
+    for (int b = 0; b < corr_regs<VT, D, CP>(); b++) corr[b] = 0.0f;
 
     int cur = 0;  // buffer of step s
     for (int s = 0; s < nsteps; s++) {
@@ -1906,8 +2007,8 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;  // hides "first step" from loop peeling (a second copy of the body)
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM, XF>(a, wbuf + cur * C::stepBytes, qop, mrow, slope, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
-                                  m_run, l_run, o, corr, [&] { wait_steps<NI>(ahead); });
+        split_step<KT, VT, D, HM, XF, CP>(a, wbuf + cur * C::stepBytes, qop, mrow, slope, g, i16, min(kStep, w_hi - n0),
+                                          s_opaque == 0, m_run, l_run, o, corr, [&] { wait_steps<NI>(ahead); });
         if (nsteps <= 4 && s < 2) FATTN_SSTAMP(6 + 2 * s);  // (stamps build: step s computed)
 
         // -- refill this buffer with step s + nbuf (K/V not fetched if -inf)
@@ -2034,7 +2135,9 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
     }
 
     // ---- compute wave: the split kernel's, its later steps refilled by the loaders
-    const int m = i16;
+    // (column-packed as there: columns 0 .. D/QK - 1 carry the tile's one row)
+    constexpr bool CP = col_packed<C::VTT, 2>();
+    const int m = (CP && i16 < D / QK) ? 0 : i16;
     const int mq = div_R(a, m);
     const int mh = hs * a.R + (m - mq * a.R);
     const int iq1 = qt * a.QPT + mq;
@@ -2084,9 +2187,9 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
     f32x4 o[NC];
 #pragma unroll
     for (int c = 0; c < NC; c++) o[c] = f32x4{0, 0, 0, 0};
-    float corr[corr_len<VT, D>()];
+    float corr[corr_regs<VT, D, CP>()];
 #pragma unroll
-    for (int b = 0; b < corr_len<VT, D>(); b++) corr[b] = 0.0f;
+    for (int b = 0; b < corr_regs<VT, D, CP>(); b++) corr[b] = 0.0f;
     for (int s = 0; s < nsteps; s++) {
         const uint32_t* f = flags + (wave * spw + s) * 2;
         if (s == 0) wait_steps_plus<NI, P::NIV>(0);  // own DMA: K + mask landed
@@ -2095,7 +2198,7 @@ __global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(
         const int n0 = w_lo + s * kStep;
         int s_opaque = s;
         asm volatile("" : "+s"(s_opaque));
-        split_step<KT, VT, D, HM, false>(a, wbuf + s * C::stepBytes, qop, mrow, 1.0f, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
+        split_step<KT, VT, D, HM, false, CP>(a, wbuf + s * C::stepBytes, qop, mrow, 1.0f, g, i16, min(kStep, w_hi - n0), s_opaque == 0,
                                   m_run, l_run, o, corr, [&] {
                                       if (s == 0) wait_vmcnt_c<0>();
                                       else wait_lds_flag(f + 1);
