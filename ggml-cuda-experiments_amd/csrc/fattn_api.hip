@@ -111,7 +111,7 @@ const char* fattn_strerror(int s) {
         case FATTN_OK: return "ok";
         case FATTN_ERR_INVALID_ARG: return "invalid argument";
         case FATTN_ERR_UNSUPPORTED_TYPE: return "unsupported tensor type";
-        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1), 128, 256; K 576 with V 512: f16, or q8_0 / q4_0 with V a view of K)";
+        case FATTN_ERR_UNSUPPORTED_HEAD_DIM: return "unsupported head dim (64, 80 (f16 K/V), 96 (not q4_1 / q5_0 / q5_1 / bf16), 128, 256; K 576 with V 512: f16, or q8_0 / q4_0 with V a view of K)";
         case FATTN_ERR_BAD_STRIDE: return "unsupported strides / layout";
         case FATTN_ERR_WORKSPACE: return "workspace too small";
         case FATTN_ERR_LAUNCH: return "HIP launch failed";
@@ -141,7 +141,8 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
     if (rc != FATTN_OK) return rc;
     auto tn = [](int t) {
         return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
-               : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == VT_F16T ? "f16T" : "f16";
+               : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == VT_F16T ? "f16T"
+               : t == FATTN_TYPE_BF16 ? "bf16" : "f16";
     };
     const char* hm = pl.a.has_mask ? "mask" : "nomask";
     // the second-launch merge `name` of the plan, or its in-kernel merge (split, batched decode)
@@ -281,8 +282,8 @@ int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void
     fattn_params p;
     std::memset(&p, 0, sizeof(p));
     p.q = {q, FATTN_TYPE_F32, 0, {ne00, ne01, ne02, ne03}, {4, nb01, nb02, nb03}};
-    const int64_t kb0 = k_type == FATTN_TYPE_F16 ? 2 : (int64_t)fattn_row_size(k_type, 32);
-    const int64_t vb0 = v_type == FATTN_TYPE_F16 ? 2 : (int64_t)fattn_row_size(v_type, 32);
+    const int64_t kb0 = is_row16(k_type) ? 2 : (int64_t)fattn_row_size(k_type, 32);
+    const int64_t vb0 = is_row16(v_type) ? 2 : (int64_t)fattn_row_size(v_type, 32);
     p.k = {k, k_type, 0, {ne10, ne11, ne12, ne13}, {kb0, nb11, nb12, nb13}};
     p.v = {v, v_type, 0, {ne10, ne11, ne12, ne13}, {vb0, nb11, nb12, nb13}};
     // mask rows hold nb31 / 2 halves: ggml pads them (GGML_KQ_MASK_PAD) past ne11,
@@ -354,6 +355,9 @@ int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n
     if (type == FATTN_TYPE_F16) {
         hipLaunchKernelGGL(dequant_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                            (const uint16_t*)src, dst, n);
+    } else if (type == FATTN_TYPE_BF16) {
+        hipLaunchKernelGGL(dequant_bf16_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           (const uint16_t*)src, dst, n);
     } else if (is_quant(type)) {
         if (k % QK) return FATTN_ERR_INVALID_ARG;
         const int64_t nb = n / QK;
@@ -378,9 +382,15 @@ int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n
 
 int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_rows, void* stream) {
     if (!src || !dst || k <= 0 || n_rows <= 0) return FATTN_ERR_INVALID_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (type == FATTN_TYPE_BF16) {  // per element: any row length, 4-byte aligned src, 2-byte aligned dst
+        if ((uintptr_t)src % 4 || (uintptr_t)dst % 2) return FATTN_ERR_ALIGNMENT;
+        const int64_t n = k * n_rows;
+        hipLaunchKernelGGL(quant_bf16_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, (uint16_t*)dst, n);
+        return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
+    }
     if (k % QK) return FATTN_ERR_INVALID_ARG;
     if ((uintptr_t)src % 16) return FATTN_ERR_ALIGNMENT;
-    hipStream_t st = (hipStream_t)stream;
     const int64_t nb = k * n_rows / QK;
     if (type == FATTN_TYPE_Q8_0)
         hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q8_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
@@ -406,10 +416,10 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     if (!src || !dst || !src->data || !dst->data) return FATTN_ERR_INVALID_ARG;
     if (src->type != FATTN_TYPE_F32 || src->nb[0] != 4) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int t = dst->type;
-    if (t != FATTN_TYPE_F16 && !is_quant(t)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (!is_row16(t) && !is_quant(t)) return FATTN_ERR_UNSUPPORTED_TYPE;
     for (int i = 0; i < 4; i++)
         if (src->ne[i] != dst->ne[i] || src->ne[i] <= 0) return FATTN_ERR_INVALID_ARG;
-    const int64_t ue = t == FATTN_TYPE_F16 ? 1 : QK;
+    const int64_t ue = is_row16(t) ? 1 : QK;
     if (src->ne[0] % ue) return FATTN_ERR_INVALID_ARG;
     if (dst->nb[0] != (int64_t)fattn_row_size(t, ue)) return FATTN_ERR_BAD_STRIDE;
     if ((uintptr_t)src->data % 4 || src->nb[1] % 4 || src->nb[2] % 4 || src->nb[3] % 4) return FATTN_ERR_ALIGNMENT;
@@ -425,6 +435,7 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     if (t == FATTN_TYPE_F16) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_F16>, grid, dim3(256), 0, st, a, units);
+    else if (t == FATTN_TYPE_BF16) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_BF16>, grid, dim3(256), 0, st, a, units);
     else if (t == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q8_0>, grid, dim3(256), 0, st, a, units);
     else if (t == FATTN_TYPE_Q4_1) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, a, units);
     else if (t == FATTN_TYPE_Q5_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, a, units);

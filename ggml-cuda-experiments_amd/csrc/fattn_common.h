@@ -37,6 +37,14 @@ struct TypeInfo<FATTN_TYPE_F16> {
     static constexpr int block_elems = 1;
     static constexpr int block_bytes = 2;
 };
+// BF16 rows are raw 16-bit elements like F16 rows: the same bytes per row, the
+// same HBM -> LDS -> VGPR moves (is_row16); only the MFMA that takes them differs
+template <>
+struct TypeInfo<FATTN_TYPE_BF16> {
+    static constexpr int block_elems = 1;
+    static constexpr int block_bytes = 2;
+};
+__host__ __device__ constexpr bool is_row16(int t) { return t == FATTN_TYPE_F16 || t == FATTN_TYPE_BF16; }
 template <>
 struct TypeInfo<FATTN_TYPE_Q8_0> {
     static constexpr int block_elems = QK;
@@ -368,6 +376,30 @@ __device__ __forceinline__ f32x4 sink_row(f32x4 acc, float inv, bool dead) {
 
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
+// ---------------------------------------------------------------- bf16 operands
+// v_mfma_f32_16x16x32_bf16 over a BF16 cache.  The operands travel as the f16x8
+// register images the f16 path uses (the LDS reads move bits); K and V enter
+// exactly.  The f32 B operand (Q, P) enters as TWO bf16 vectors, hi = bf16(x)
+// and lo = bf16(x - hi), both round-to-nearest-even (v_cvt_pk_bf16_f32), and
+// each k-step issues two MFMAs into one accumulator: 16 operand bits where one
+// bf16 has 8 and f16 has 11
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x4 mfma16_bf(f16x8 a, f16x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+// x[0..7] -> (hi, lo) bf16 vectors (as f16x8 register images)
+__device__ __forceinline__ void bf16_split8(const float (&x)[8], f16x8& hi, f16x8& lo) {
+    bf16x8 h, l;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        h[j] = (__bf16)x[j];
+        l[j] = (__bf16)(x[j] - (float)h[j]);  // exact difference (|x - hi| <= ulp_bf16 / 2), then one rounding
+    }
+    hi = __builtin_bit_cast(f16x8, h);
+    lo = __builtin_bit_cast(f16x8, l);
 }
 
 }  // namespace fattn

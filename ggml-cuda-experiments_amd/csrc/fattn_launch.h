@@ -149,7 +149,7 @@ void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
 int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
     if (pl.kernel == Kernel::SplitLd) {
-        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && !is_kv_ext(KT) && (D == 64 || D == 128)) {
+        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && !is_kv_ext(KT) && KT != FATTN_TYPE_BF16 && (D == 64 || D == 128)) {
             auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders>;
             return launch_kernel((const void*)lk, pl, st, ev, [&] {
                 hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, pl.a);
@@ -354,6 +354,18 @@ FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_0)
 FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_1)
 #undef FATTN_KV_EXT_EXTERN
 
+// split kernel over a BF16 cache (K and V both BF16: raw bf16 rows into
+// v_mfma_f32_16x16x32_bf16, Q and P as bf16 hi / lo pairs; instantiated once per
+// D in fattn_launch_bf16_d<D>.hip; D = 64, 128, 256).  The only kernel of the
+// type: no loader-wave form, and the planner sends every shape here
+template <int D>
+int launch_bf16(const Plan& pl, hipStream_t st, const Events& ev) {
+    return launch_gran<FATTN_TYPE_BF16, FATTN_TYPE_BF16, D>(pl, st, ev);
+}
+extern template int launch_bf16<64>(const Plan&, hipStream_t, const Events&);
+extern template int launch_bf16<128>(const Plan&, hipStream_t, const Events&);
+extern template int launch_bf16<256>(const Plan&, hipStream_t, const Events&);
+
 // every kernel of head dim D (defined here, instantiated once per D in
 // fattn_launch_d<D>.hip)
 template <int D>
@@ -392,6 +404,7 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
                 if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q4_1) return launch_kv_ext<FATTN_TYPE_Q4_1, D>(pl, st, ev);
                 if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_0) return launch_kv_ext<FATTN_TYPE_Q5_0, D>(pl, st, ev);
                 if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_1) return launch_kv_ext<FATTN_TYPE_Q5_1, D>(pl, st, ev);
+                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_BF16) return pl.kernel == Kernel::Split ? launch_bf16<D>(pl, st, ev) : FATTN_ERR_UNSUPPORTED_TYPE;
                 if (pl.kt != pl.vt && pl.vt != VT_F16T) return launch_mixed<D>(pl, st, ev);
             }
             if constexpr (D % QK == 0) {

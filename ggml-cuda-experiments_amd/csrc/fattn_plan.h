@@ -96,7 +96,10 @@ constexpr int kLdsPerCU = 163840;
 template <int KT, int VT, int D>
 int lds_bytes_of(Kernel kern, int waves, int nbuf) {
     constexpr int F16 = FATTN_TYPE_F16;
-    constexpr bool quant = KT != F16 && KT == VT && !is_kv_ext(KT);  // (Q8_0 / Q4_0: the kernels below the split kernel)
+    constexpr bool quant = !is_row16(KT) && KT == VT && !is_kv_ext(KT);  // (Q8_0 / Q4_0: the kernels below the split kernel)
+    if constexpr (KT == FATTN_TYPE_BF16) {  // the split kernel alone (no loader-wave form)
+        if (kern != Kernel::Split) return 0;
+    }
     switch (kern) {
         case Kernel::Split:
         case Kernel::SplitLd: {
@@ -111,7 +114,7 @@ int lds_bytes_of(Kernel kern, int waves, int nbuf) {
                 return waves == 8 ? MQCfg<KT, D, 8, 32>::ldsBytes : MQCfg<KT, D, 4, 16>::ldsBytes;
             break;
         case Kernel::Pf:
-            if constexpr (KT == VT && D != 256 && !is_kv_ext(KT)) return PfCfg<KT, D>::ldsBytes;
+            if constexpr (KT == VT && D != 256 && !is_kv_ext(KT) && KT != FATTN_TYPE_BF16) return PfCfg<KT, D>::ldsBytes;
             break;
         case Kernel::Pf4:
             if constexpr (KT == F16 && VT == F16 && D == 128) return Pf4Cfg<D>::ldsBytes;
@@ -152,12 +155,13 @@ inline int lds_bytes(Kernel kern, int kt, int vt, int D, int waves, int nbuf = 0
             default: return with_d(k, std::integral_constant<int, FATTN_TYPE_F16>());
         }
     };
-    // Q4_1 / Q5_0 / Q5_1: K and V of one type, head dims 64 / 128 / 256 (check_views)
+    // Q4_1 / Q5_0 / Q5_1 / BF16: K and V of one type, head dims 64 / 128 / 256 (check_views)
     auto same = [&](auto k) { return D == 80 || D == 96 ? 0 : with_d(k, k); };
     switch (kt) {
         case FATTN_TYPE_Q4_1: return same(std::integral_constant<int, FATTN_TYPE_Q4_1>());
         case FATTN_TYPE_Q5_0: return same(std::integral_constant<int, FATTN_TYPE_Q5_0>());
         case FATTN_TYPE_Q5_1: return same(std::integral_constant<int, FATTN_TYPE_Q5_1>());
+        case FATTN_TYPE_BF16: return same(std::integral_constant<int, FATTN_TYPE_BF16>());
         case FATTN_TYPE_Q8_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q8_0>());
         case FATTN_TYPE_Q4_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q4_0>());
         default: return with_v(std::integral_constant<int, FATTN_TYPE_F16>());
@@ -174,6 +178,7 @@ inline size_t row_size(int type, int64_t k) {
     switch (type) {
         case FATTN_TYPE_F32: return (size_t)k * 4;
         case FATTN_TYPE_F16: return (size_t)k * 2;
+        case FATTN_TYPE_BF16: return (size_t)k * 2;
         case FATTN_TYPE_Q8_0: return k % QK ? 0 : (size_t)(k / QK) * kQ8Bytes;
         case FATTN_TYPE_Q4_0: return k % QK ? 0 : (size_t)(k / QK) * kQ4Bytes;
         case FATTN_TYPE_Q4_1: return k % QK ? 0 : (size_t)(k / QK) * kQ41Bytes;
@@ -320,6 +325,10 @@ inline int check_views(const fattn_params* p, Views& w) {
     if (D == kMlaDK) return check_views_mla(p, w);
     if (D != 64 && D != 80 && D != 96 && D != 128 && D != 256) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
     if (D % QK && (k.type != FATTN_TYPE_F16 || v.type != FATTN_TYPE_F16)) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
+    // BF16: K and V both BF16 (no mixed pair), D = 64 / 128 / 256, rows not transposed
+    const bool bf16 = k.type == FATTN_TYPE_BF16 || v.type == FATTN_TYPE_BF16;
+    if (bf16 && k.type != v.type) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (bf16 && D == 96) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
     if (k.ne[0] != D || v.ne[0] != D) return FATTN_ERR_INVALID_ARG;
     const int64_t NQ = w.NQ = q.ne[1], H = w.H = q.ne[2], S = w.S = q.ne[3];
     const int64_t N = w.N = k.ne[1], Hkv = w.Hkv = k.ne[2], Skv = w.Skv = k.ne[3];
@@ -327,8 +336,8 @@ inline int check_views(const fattn_params* p, Views& w) {
     if (v.ne[1] != N || v.ne[2] != Hkv || v.ne[3] != Skv) return FATTN_ERR_INVALID_ARG;
     if (H % Hkv || S % Skv) return FATTN_ERR_INVALID_ARG;
     if (N > (int64_t)1 << 30 || NQ * H * S > (int64_t)1 << 31) return FATTN_ERR_INVALID_ARG;
-    if (k.type != FATTN_TYPE_F16 && !is_quant(k.type)) return FATTN_ERR_UNSUPPORTED_TYPE;
-    if (v.type != FATTN_TYPE_F16 && !is_quant(v.type)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (!is_row16(k.type) && !is_quant(k.type)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (!is_row16(v.type) && !is_quant(v.type)) return FATTN_ERR_UNSUPPORTED_TYPE;
     // mixed K/V types (llama.cpp's separate cache types, e.g. K Q8_0 with V F16):
     // the split kernel, head dims 64 / 128 / 256
     w.mixed = k.type != v.type;
@@ -344,7 +353,8 @@ inline int check_views(const fattn_params* p, Views& w) {
 
     const size_t rowK = row_size(k.type, D), rowV = row_size(v.type, D);
     // K rows must be contiguous (nb[0] = element size / block granular)
-    if (k.type == FATTN_TYPE_F16 && k.nb[0] != 2) return FATTN_ERR_BAD_STRIDE;
+    if (is_row16(k.type) && k.nb[0] != 2) return FATTN_ERR_BAD_STRIDE;
+    if (v.type == FATTN_TYPE_BF16 && v.nb[0] != 2) return FATTN_ERR_BAD_STRIDE;  // (no transposed BF16 V)
     if (is_quant(k.type) && k.nb[0] != (int64_t)row_size(k.type, 32)) return FATTN_ERR_BAD_STRIDE;
     w.v_trans = false;
     if (v.type == FATTN_TYPE_F16 && v.nb[0] != 2) {
@@ -540,7 +550,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     SplitArgs& a = pl.a;
     auto lds = [&](int nbuf, int nwv) { return lds_bytes(Kernel::Split, pl.kt, pl.vt, pl.D, nwv, nbuf); };
     const int64_t steps = (N + kStep - 1) / kStep;
-    const int wps = (pl.kt == FATTN_TYPE_F16 || pl.gran == 4 || pl.D == 256 || is_kv_ext(pl.kt)) ? 2 : 4;  // __launch_bounds__ waves/SIMD
+    const int wps = (is_row16(pl.kt) || pl.gran == 4 || pl.D == 256 || is_kv_ext(pl.kt)) ? 2 : 4;  // __launch_bounds__ waves/SIMD
     const int rv_max = std::min<int64_t>(kRows, (int64_t)a.R * std::min<int64_t>(a.QPT, NQ));
     const int64_t total = steps * Y * S;
     const bool fused_merge = o[FATTN_OPT_SPLIT_MERGE] != 0;
@@ -612,7 +622,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     // whole chunk fits the LDS (every step resident), 16-B rows, D = 64 / 128,
     // one K / V type; 4 loader waves issue it all up front
     if (o[FATTN_OPT_SPLIT_LOADERS] == 2 && pl.gran == 16 && a.wave_merge == 2 && nwv == 8 && spw >= 2 && spw <= 3 &&
-        (pl.D == 64 || pl.D == 128) && pl.kt == pl.vt && !is_kv_ext(pl.kt) && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
+        (pl.D == 64 || pl.D == 128) && pl.kt == pl.vt && !is_kv_ext(pl.kt) && pl.kt != FATTN_TYPE_BF16 && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
         lds(spw, nwv) + kSplitLdFlagBytes <= kLdsPerCU) {
         pl.kernel = Kernel::SplitLd;
         nbuf = spw;
@@ -638,7 +648,8 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     // (auto: f16 partials for tiles of 8+ rows -- the 8-rank config-5 shard
     // 11.67 -> 11.50 us; config 4's 4-row tiles were 10.09 -> 10.33 us, so
     // they keep f32; profiles/r06_f)
-    a.part_f16 = part_f16_ok(o, a.merge_launch, pl.D) && (o[FATTN_OPT_PART_F16] == 2 || rv_max >= 8) ? 1 : 0;
+    // (a BF16 cache: f32 partials always -- O / l of a V past 65504 is the overflow the type avoids)
+    a.part_f16 = pl.kt != FATTN_TYPE_BF16 && part_f16_ok(o, a.merge_launch, pl.D) && (o[FATTN_OPT_PART_F16] == 2 || rv_max >= 8) ? 1 : 0;
     pl.grid = dim3(a.n_chunks, (unsigned)Y, (unsigned)S);
     // XCD-grouped order (tile_coords): a tile's chunk workgroups on one XCD.
     // Default for the one-row tiles that merge in-kernel (wg_row_merge):

@@ -100,6 +100,31 @@ static __global__ __launch_bounds__(256) void dequant_f16_kernel(const uint16_t*
     dst[i] = (float)__builtin_bit_cast(f16, src[i]);
 }
 
+// f32 -> bf16 bits, ggml_compute_fp32_to_bf16 bit for bit, in integer arithmetic
+// (the hardware convert's NaN payload is not promised to match): a NaN keeps its
+// top 16 bits and is made quiet; everything else rounds to nearest even on the
+// 16 dropped bits -- subnormals kept, overflow to inf
+__host__ __device__ __forceinline__ uint16_t f32_to_bf16_bits(float x) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
+    return (uint16_t)((u + (0x7fffu + ((u >> 16) & 1u))) >> 16);
+}
+
+// bf16 -> f32 (exact: the bits shifted up) and f32 -> bf16, one thread per element
+// (templates, so that only the translation unit that launches them holds them)
+template <int T = FATTN_TYPE_BF16>
+__global__ __launch_bounds__(256) void dequant_bf16_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dst[i] = __builtin_bit_cast(float, (uint32_t)src[i] << 16);
+}
+template <int T = FATTN_TYPE_BF16>
+__global__ __launch_bounds__(256) void quant_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    dst[i] = f32_to_bf16_bits(src[i]);
+}
+
 // One ggml block of 32 values -> Q8_0 {f16 d; int8 qs[32]} (quantize_row_q8_0_ref)
 __device__ __forceinline__ void quant_block_q8_0(const float (&xv)[QK], uint8_t* blk) {
 #pragma clang fp contract(off)
@@ -232,7 +257,7 @@ __global__ __launch_bounds__(256) void quant_kernel(const float* __restrict__ sr
     quant_block<T>(xv, dst + i * TypeInfo<T>::block_bytes);
 }
 
-// Strided f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 copy: ggml's GGML_OP_CPY into a KV-cache view
+// Strided f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 copy: ggml's GGML_OP_CPY into a KV-cache view
 // (upstream ggml cpy f32 -> f16/q8_0/q4_0).  src and dst
 // have the same ne (ne0 = row length, a multiple of 32 for the block types)
 // and any byte strides nb1..nb3; rows are contiguous (src nb0 = 4, dst nb0 =
@@ -249,7 +274,7 @@ struct CpyArgs {
 
 template <int T>
 __global__ __launch_bounds__(256) void cpy_f32_kernel(const CpyArgs a, int64_t units) {
-    constexpr int UE = T == FATTN_TYPE_F16 ? 1 : QK;  // elements per unit
+    constexpr int UE = is_row16(T) ? 1 : QK;  // elements per unit
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= units) return;
     const int64_t upr = a.ne0 / UE;
@@ -259,6 +284,8 @@ __global__ __launch_bounds__(256) void cpy_f32_kernel(const CpyArgs a, int64_t u
     uint8_t* y = a.dst + i1 * a.dnb1 + i2 * a.dnb2 + i3 * a.dnb3;
     if constexpr (T == FATTN_TYPE_F16) {
         *(uint16_t*)(y + b * 2) = __builtin_bit_cast(uint16_t, (f16)x[0]);
+    } else if constexpr (T == FATTN_TYPE_BF16) {
+        *(uint16_t*)(y + b * 2) = f32_to_bf16_bits(x[0]);
     } else {
         float xv[QK];
 #pragma unroll

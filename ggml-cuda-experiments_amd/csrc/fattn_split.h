@@ -11,7 +11,7 @@
 //    (GQA broadcast ik2 = iq2 / (ne02/ne12), flash-llama.h:128-140), so a
 //    32q/8kv decode packs 4 heads into one tile instead of re-reading K/V 4x.
 //  * Each wave owns a contiguous slice of the chunk and streams it in steps of
-//    32 positions.  The raw ggml rows (f16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 blocks, exactly as in
+//    32 positions.  The raw ggml rows (f16 / bf16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 blocks, exactly as in
 //    HBM) plus the step's mask rows are copied HBM -> LDS with
 //    global_load_lds_dwordx4 (fully coalesced 1 KiB per wave instruction; a
 //    dword-granular variant serves arbitrary ggml row strides), NBUF steps in
@@ -24,7 +24,9 @@
 //    query column on one lane group, so P feeds PV with no lane movement and
 //    the row max/sum need only two xor-shuffles (wave64: lanes l, l^16, l^32,
 //    l^48).  Dequant is h(q*d) with one f16 rounding -- exactly the oracle's
-//    fp16 rounding of the dequantised value (src/utils.h:10-11).
+//    fp16 rounding of the dequantised value (src/utils.h:10-11).  A bf16 cache
+//    takes the f16 rows' moves bit for bit and v_mfma_f32_16x16x32_bf16: K and V
+//    exact, Q and P as bf16 hi / lo operand pairs (bf16_split8, fattn_common.h).
 //  * fp32 MFMA accumulators, fp32 softmax state (the reference keeps fp16).
 //  * The waves' states merge through LDS (or, for one-row tiles, per wave);
 //    with several chunks the partials (O, m, l) go to the caller's workspace
@@ -462,8 +464,8 @@ __device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs
         const int p = i * kWave + lane;
         const int byte = p * GRAN;
         uint32_t off;
-        if constexpr (KT == FATTN_TYPE_F16) {
-            // f16 rows: 16-B chunks XOR-swizzled by row (conflict-free ds_read_b128)
+        if constexpr (is_row16(KT)) {
+            // f16 / bf16 rows: 16-B chunks XOR-swizzled by row (conflict-free ds_read_b128)
             constexpr int SW = swz_mask(C::rowK / 16);
             const int row = byte / C::rowK;
             const int chunk = ((byte % C::rowK) / 16) ^ (row & SW);
@@ -501,7 +503,7 @@ __device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs
             // V^T tile: D rows (one per head dim) of kStep f16; needs N % 32 == 0
             const int d = byte / (kStep * 2);
             off = (uint32_t)d * (uint32_t)a.v_nb0 + (uint32_t)n0 * 2 + (byte % (kStep * 2));
-        } else if constexpr (VT == FATTN_TYPE_F16) {
+        } else if constexpr (is_row16(VT)) {
             constexpr int SW = swz_mask(C::rowV / 16);
             const int row = byte / C::rowV;
             const int chunk = ((byte % C::rowV) / 16) ^ (((row & 7) << 1) & SW);
@@ -536,6 +538,10 @@ constexpr float v_code_off() {
 // per-block f32 accumulators a wave carries beside O: corr[b], and for Q4_1 /
 // Q5_1 behind them sum P (m_b + c d_b) (plain P, not the rounded P d: exact f16
 // products summed in f32), which the epilogue adds to the block's 32 columns
+// f16x8 registers of the Q^T operand a wave holds across its loop: one per
+// k-step, two (the hi parts, then the lo parts) over a BF16 cache
+template <int KT, int D>
+constexpr int qop_len() { return (D + QK - 1) / QK * (KT == FATTN_TYPE_BF16 ? 2 : 1); }
 template <int VT, int D>
 constexpr int corr_len() { return (D + QK - 1) / QK * (has_min(VT) ? 2 : 1); }
 
@@ -616,7 +622,7 @@ __device__ __forceinline__ u32x2 read8_any(const uint8_t* smem, uint32_t off) {
 // lane l -> row 16t + (l&15), elements d = 32b + 8(l>>4) + j.
 template <int KT, int D>
 __device__ __forceinline__ f16x8 k_operand(const uint8_t* kb, int row, int g, int b, uint32_t dbits) {
-    if constexpr (KT == FATTN_TYPE_F16) {
+    if constexpr (is_row16(KT)) {  // (bf16 rows: the same bits, as an f16x8 register image)
         constexpr int CPR = D * 2 / 16;
         const int chunk = (4 * b + g) ^ (row & swz_mask(CPR));
         const f16x8 r = *(const f16x8*)(kb + row * (D * 2) + chunk * 16);
@@ -1292,7 +1298,7 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     constexpr int NC = D / 16;
     constexpr float kNegInf = -__builtin_inff();
     constexpr bool kVQ8 = C::VTT == FATTN_TYPE_Q8_0;
-    constexpr bool kVQ = C::VTT != FATTN_TYPE_F16;
+    constexpr bool kVQ = !is_row16(C::VTT);
     constexpr float kVOff = v_code_off<C::VTT>();
     constexpr bool CP = col_packed<C::VTT, EPI>();
     const int g = lane >> 4;
@@ -1502,7 +1508,7 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     __syncthreads();
     FATTN_SSTAMP(12);
     if (!*last_flag) return;
-    combine_tile<D, (D == 128 && KT != FATTN_TYPE_F16) ? 8 : 2>(a, tile, qt, hs, ik2, iq3, rv, 0, smem);
+    combine_tile<D, (D == 128 && !is_row16(KT)) ? 8 : 2>(a, tile, qt, hs, ik2, iq3, rv, 0, smem);
     FATTN_SSTAMP(13);
 }
 
@@ -1567,7 +1573,7 @@ __device__ __forceinline__ void pv_block_q(const uint8_t* vb, int b, int g, int 
 // the slope held across the loop by a wave-uniform branch cost the bodies at
 // their register limit spills (profiles/op_params/registers.txt).
 template <int KT, int VT, int D, bool HM, bool XF, bool CP, typename WaitV>
-__device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[(D + QK - 1) / QK], int mrow,
+__device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* buf, const f16x8 (&qop)[qop_len<KT, D>()], int mrow,
                                            float slope, int g, int i16, int nvalid, bool first, float& m_run, float& l_run,
                                            f32x4 (&o)[D / 16], float (&corr)[corr_regs<VT, D, CP>()], WaitV&& wait_v) {
     using C = SplitCfg<KT, VT, D>;
@@ -1575,7 +1581,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
     constexpr int NC = D / 16;
     constexpr float kNegInf = -__builtin_inff();
     constexpr bool kVQ8 = C::VTT == FATTN_TYPE_Q8_0;
-    constexpr bool kVQ = C::VTT != FATTN_TYPE_F16;
+    constexpr bool kVQ = !is_row16(C::VTT);
     const float log2e = 1.4426950408889634f;
     const uint8_t* kb = buf;
     const uint8_t* vb = buf + C::kBytes;
@@ -1586,7 +1592,15 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
 #pragma unroll
     for (int t = 0; t < 2; t++) {
         st[t] = f32x4{0, 0, 0, 0};
-        if constexpr (KT == FATTN_TYPE_F16) {
+        if constexpr (KT == FATTN_TYPE_BF16) {
+            // K exact; Q as its bf16 hi and lo parts, two MFMAs per k-step into one accumulator
+#pragma unroll
+            for (int b = 0; b < NB; b++) {
+                const f16x8 kop = k_operand<KT, D>(kb, 16 * t + i16, g, b, 0);
+                st[t] = mfma16_bf(kop, qop[b], st[t]);
+                st[t] = mfma16_bf(kop, qop[NB + b], st[t]);
+            }
+        } else if constexpr (KT == FATTN_TYPE_F16) {
 #pragma unroll
             for (int b = 0; b < NB; b++) st[t] = mfma16(k_operand<KT, D>(kb, 16 * t + i16, g, b, 0), qop[b], st[t]);
         } else if constexpr (is_kv_ext(KT)) {
@@ -1667,12 +1681,25 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
     l_run += ((pv[0] + pv[1]) + (pv[2] + pv[3])) + ((pv[4] + pv[5]) + (pv[6] + pv[7]));
 
     f16x8 pb;
-    pb.s0 = (f16)pv[0]; pb.s1 = (f16)pv[1]; pb.s2 = (f16)pv[2]; pb.s3 = (f16)pv[3];
-    pb.s4 = (f16)pv[4]; pb.s5 = (f16)pv[5]; pb.s6 = (f16)pv[6]; pb.s7 = (f16)pv[7];
+    if constexpr (C::VTT != FATTN_TYPE_BF16) {
+        pb.s0 = (f16)pv[0]; pb.s1 = (f16)pv[1]; pb.s2 = (f16)pv[2]; pb.s3 = (f16)pv[3];
+        pb.s4 = (f16)pv[4]; pb.s5 = (f16)pv[5]; pb.s6 = (f16)pv[6]; pb.s7 = (f16)pv[7];
+    }
 
     // -- O^T += V^T.P^T (V of step s landed)
+    [[maybe_unused]] f16x8 plo;
+    if constexpr (C::VTT == FATTN_TYPE_BF16) bf16_split8(pv, pb, plo);  // (before the wait: V may still fly)
     wait_v();
-    if constexpr (C::VTT == FATTN_TYPE_F16) {
+    if constexpr (C::VTT == FATTN_TYPE_BF16) {
+        // V exact; P as its bf16 hi and lo parts (p <= 2^kRescaleLog2: both finite),
+        // two MFMAs per column group into one accumulator
+#pragma unroll
+        for (int c = 0; c < NC; c++) {
+            const f16x8 vop = v_operand_f16<VT, D>(vb, c, g, i16);
+            o[c] = mfma16_bf(vop, pb, o[c]);
+            o[c] = mfma16_bf(vop, plo, o[c]);
+        }
+    } else if constexpr (C::VTT == FATTN_TYPE_F16) {
 #pragma unroll
         for (int c = 0; c < NC; c++) o[c] = mfma16(v_operand_f16<VT, D>(vb, c, g, i16), pb, o[c]);
     } else if constexpr (CP) {
@@ -1802,7 +1829,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
 // (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4)
 template <int KT, int D, int GRAN>
 constexpr int split_waves_per_simd() {
-    return (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4;
+    return (is_row16(KT) || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4;
 }
 
 // NWV waves per workgroup (4, 8 or 16), each streaming its own slice of the
@@ -1813,7 +1840,7 @@ constexpr int split_waves_per_simd() {
 // XF (split_step): instantiated for NWV = 4 only; the planner sizes a launch
 // with max_bias / logit_softcap live for 4 waves (size_split).
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false>
-__global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4) void fattn_split_kernel(
+__global__ __launch_bounds__(NWV * kWave, (is_row16(KT) || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4) void fattn_split_kernel(
     const SplitArgs a) {
     using C = SplitCfg<KT, VT, D>;
     using P = StepPlan<KT, VT, D, GRAN>;
@@ -1957,14 +1984,20 @@ __global__ __launch_bounds__(NWV * kWave, (KT == FATTN_TYPE_F16 || GRAN == 4 || 
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) reg_fence<kTagMaskWords>(mraw[j]);
-    f16x8 qop[NB];
+    f16x8 qop[qop_len<KT, D>()];
 #pragma unroll
     for (int b = 0; b < NB; b++) {
         const f32x4 x0 = __builtin_bit_cast(f32x4, qraw[b][0]), x1 = __builtin_bit_cast(f32x4, qraw[b][1]);
-        f16x8 h;
-        h.s0 = (f16)x0.x; h.s1 = (f16)x0.y; h.s2 = (f16)x0.z; h.s3 = (f16)x0.w;
-        h.s4 = (f16)x1.x; h.s5 = (f16)x1.y; h.s6 = (f16)x1.z; h.s7 = (f16)x1.w;
-        qop[b] = h;
+        if constexpr (KT == FATTN_TYPE_BF16) {
+            // bf16 cache: Q as its bf16 hi and lo parts (qop[b], qop[NB + b]; bf16_split8)
+            const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+            bf16_split8(x, qop[b], qop[NB + b]);
+        } else {
+            f16x8 h;
+            h.s0 = (f16)x0.x; h.s1 = (f16)x0.y; h.s2 = (f16)x0.z; h.s3 = (f16)x0.w;
+            h.s4 = (f16)x1.x; h.s5 = (f16)x1.y; h.s6 = (f16)x1.z; h.s7 = (f16)x1.w;
+            qop[b] = h;
+        }
     }
     // bit s: step s has a live key (steps past 64 and unprefetched waves: all)
     uint64_t live = ~0ull;

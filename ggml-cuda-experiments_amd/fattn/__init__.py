@@ -23,8 +23,9 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", os.environ.get("
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0 = 0, 1, 2, 8
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
 TYPE_I32, TYPE_I64 = 26, 27   # index tensors of set_rows only
+TYPE_BF16 = 30                # 2-byte elements: K / V of flash_attn_ext, dst of cpy / quantize (not of set_rows)
 TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
-              "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1}
+              "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1, "bf16": TYPE_BF16}
 BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18, TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
 
 FATTN_OK = 0
@@ -300,8 +301,8 @@ def _tptr(t) -> int:
 
 
 def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "head") -> View:
-    """View of a KV cache held in a byte (or f16) torch tensor; typ: TYPE_F16 or a
-    block type (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1).
+    """View of a KV cache held in a byte (or f16) torch tensor; typ: TYPE_F16,
+    TYPE_BF16 or a block type (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1).
 
     layout "head": [S][Hkv][N][row]   (per-head contiguous; reference decode layout,
                    src/flash_row_float.h:19,58)
@@ -312,7 +313,7 @@ def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "
     its own).
     """
     rb = row_size(typ, D)
-    nb0 = 2 if typ == TYPE_F16 else BLOCK_BYTES[typ]
+    nb0 = 2 if typ in (TYPE_F16, TYPE_BF16) else BLOCK_BYTES[typ]
     if layout == "head":
         nb = (nb0, rb, rb * N, rb * N * Hkv)
     elif layout == "pos":
@@ -419,7 +420,8 @@ class Attention:
 
 
 def quantize(x, typ: int, stream=None):
-    """f32 [rows, k] (cuda) -> ggml blocks uint8 [rows, k/32*bytes] (bit-exact ggml quantize_row_*_ref)."""
+    """f32 [rows, k] (cuda) -> ggml blocks uint8 [rows, k/32*bytes] (bit-exact ggml quantize_row_*_ref);
+    TYPE_BF16: the bf16 bits, uint8 [rows, 2k] little endian (ggml_compute_fp32_to_bf16, any k)."""
     import torch
     assert x.dtype == torch.float32 and x.is_contiguous()
     k = x.shape[-1]
@@ -430,7 +432,7 @@ def quantize(x, typ: int, stream=None):
 
 
 def cpy(src: View, dst: View, stream=None):
-    """GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view (the KV-cache
+    """GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view (the KV-cache
     write, include/fattn.h fattn_cpy); src/dst are ggml views of device memory."""
     s, d = src.c(), dst.c()
     _check(lib().fattn_cpy(C.byref(s), C.byref(d), _stream(stream)), "fattn_cpy")
@@ -449,9 +451,10 @@ def set_rows(src: View, idx: View, dst: View, stream=None):
 
 
 def dequantize(blocks, typ: int, k: int, stream=None):
-    """ggml blocks (or f16 bits) -> f32 [rows, k] (bit-exact ggml dequantize_row_*)."""
+    """ggml blocks (or f16 / bf16 bits, in a tensor of any element size) -> f32 [rows, k]
+    (bit-exact ggml dequantize_row_*; bf16: exact, the bits shifted up)."""
     import torch
-    rows = blocks.numel() * (1 if typ != TYPE_F16 else blocks.element_size()) // max(1, row_size(typ, k))
+    rows = blocks.numel() * (1 if typ not in (TYPE_F16, TYPE_BF16) else blocks.element_size()) // max(1, row_size(typ, k))
     out = torch.empty((rows, k), dtype=torch.float32, device=blocks.device)
     _check(lib().fattn_dequantize(typ, _tptr(blocks), _tptr(out), k, rows, _stream(stream)), "fattn_dequantize")
     return out

@@ -19,7 +19,9 @@
 //   --n-warps N          accepted for compatibility (kernel_test.h:9-13); the gfx950
 //                        kernels pick their own wave counts
 //   --kv-size N          KV length, min 256 on the GPU path (kernel_test.h:14-18)
-//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0 | q4_1 | q5_0 | q5_1
+//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0 | q4_1 | q5_0 | q5_1 | bf16
+//                        (bf16: the cache written by fattn_cpy; the reference over the bf16-rounded
+//                        values, rounded on the host; not with --set-rows, which has no bf16 form)
 //   --cpu-only           the CPU reference alone (BASELINE config 1: no GPU is touched,
 //                        any kv_size); with --dump FILE its f32 output is written raw
 //   --head-dim D --heads H --kv-heads Hkv --iters I --tol T
@@ -226,7 +228,18 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
 
 const char* type_name(int t) {
     return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
-           : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : "f16";
+           : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == FATTN_TYPE_BF16 ? "bf16" : "f16";
+}
+
+// f32 -> the f32 value of its bf16 rounding (ggml_compute_fp32_to_bf16: NaN kept
+// and made quiet, else round to nearest even on the 16 dropped bits)
+float round_bf16(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    const uint32_t h = (u & 0x7fffffffu) > 0x7f800000u ? (u >> 16) | 64u : (u + (0x7fffu + ((u >> 16) & 1u))) >> 16;
+    u = h << 16;
+    std::memcpy(&f, &u, 4);
+    return f;
 }
 
 bool is_kv_ext(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1; }
@@ -273,6 +286,7 @@ int parse_type(const std::string& s) {
     if (s == "q4_1") return FATTN_TYPE_Q4_1;
     if (s == "q5_0") return FATTN_TYPE_Q5_0;
     if (s == "q5_1") return FATTN_TYPE_Q5_1;
+    if (s == "bf16") return FATTN_TYPE_BF16;
     fprintf(stderr, "unknown --kv-type %s\n", s.c_str());
     exit(2);
 }
@@ -751,11 +765,18 @@ int main(int argc, const char* argv[]) {
                 rc = fattn_set_rows(&ts, &ti, &td, st0);
                 ts.data = d_vf, td.data = d_vq;
                 rc = rc ? rc : fattn_set_rows(&ts, &ti, &td, st0);
+            } else if (kv_type == FATTN_TYPE_BF16) {
+                // the cache write of a bf16 cache: GGML_OP_CPY f32 -> bf16 into the [Hkv][N][row] view
+                fattn_tensor ts = {d_kf, FATTN_TYPE_F32, 0, {D, N, Hkv, 1}, {4, (int64_t)D * 4, (int64_t)D * 4 * N, (int64_t)D * 4 * N * Hkv}};
+                fattn_tensor td = {d_kq, kv_type, 0, {D, N, Hkv, 1}, {2, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+                rc = fattn_cpy(&ts, &td, st0);
+                ts.data = d_vf, td.data = d_vq;
+                rc = rc ? rc : fattn_cpy(&ts, &td, st0);
             } else {
                 rc = fattn_quantize(kv_type, d_kf, d_kq, D, (int64_t)N * Hkv, st0);
                 rc = rc ? rc : fattn_quantize(kv_type, d_vf, d_vq, D, (int64_t)N * Hkv, st0);
             }
-            if (kv_type != FATTN_TYPE_F16) {
+            if (kv_type != FATTN_TYPE_F16 && kv_type != FATTN_TYPE_BF16) {
                 rc = rc ? rc : fattn_dequantize(kv_type, d_kq, d_kf, D, (int64_t)N * Hkv, st0);
                 rc = rc ? rc : fattn_dequantize(kv_type, d_vq, d_vf, D, (int64_t)N * Hkv, st0);
             }
@@ -763,7 +784,10 @@ int main(int argc, const char* argv[]) {
                 fprintf(stderr, "%s failed: %s\n", set_rows ? "set_rows" : "quantize", fattn_strerror(rc));
                 return 2;
             }
-            if (kv_type != FATTN_TYPE_F16) {  // (f16: the reference rounds key / value itself)
+            if (kv_type == FATTN_TYPE_BF16) {  // the reference's values: the bf16 roundings, in plain C++ on the host
+                for (auto& x : kref) x = round_bf16(x);
+                for (auto& x : vref) x = round_bf16(x);
+            } else if (kv_type != FATTN_TYPE_F16) {  // (f16: the reference rounds key / value itself)
                 HIP_CHECK(hipMemcpyAsync(kref.data(), d_kf, 4 * key.size(), hipMemcpyDeviceToHost, st0));
                 HIP_CHECK(hipMemcpyAsync(vref.data(), d_vf, 4 * value.size(), hipMemcpyDeviceToHost, st0));
             }
@@ -839,7 +863,7 @@ int main(int argc, const char* argv[]) {
         // the ext plan: the flash_attn_ext argument list of kernel_test.h:191-198
         // (n_q = 1) or its ne01 = n_q form, as a fattn_params view
         std::memset(&d.p, 0, sizeof(d.p));
-        const int64_t eb = kv_type == FATTN_TYPE_F16 ? 2 : (int64_t)fattn_row_size(kv_type, 32);
+        const int64_t eb = kv_type == FATTN_TYPE_F16 || kv_type == FATTN_TYPE_BF16 ? 2 : (int64_t)fattn_row_size(kv_type, 32);
         d.p.q = {d.q, FATTN_TYPE_F32, 0, {D, NQ, Hl, 1}, {4, (int64_t)Hl * D * 4, D * 4, (int64_t)NQ * Hl * D * 4}};
         d.p.k = {d.k, kv_type, 0, {D, N, Hkvl, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkvl}};
         d.p.v = {d.v, kv_type, 0, {D, N, Hkvl, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkvl}};

@@ -12,8 +12,8 @@
  *                           src/flash-matrix.cu:198-206).  Same argument meaning
  *                           (q/k/v/mask as ggml ne/nb views, f32 dst in the
  *                           permuted [seq][n_q][H][D] layout of flash-llama.h:434),
- *                           extended with K/V element types F16 / Q8_0 / Q4_0 /
- *                           Q4_1 / Q5_0 / Q5_1.
+ *                           extended with K/V element types F16 / BF16 / Q8_0 /
+ *                           Q4_0 / Q4_1 / Q5_0 / Q5_1.
  *   fattn_ext_sinks()    fattn_ext() with upstream ggml's src[4], the per-head attention
  *                           sinks (absent from the reference; see its comment below).
  *   fattn_ext_f16_launch()  the positional argument list of flash-llama.h:7-32,
@@ -29,7 +29,7 @@
  *                           scratch exactly like d_temporal (kernel_test.h:155).
  *   fattn_workspace_size()  the size of that scratch (kernel_test.h:155 computes
  *                           it inline).
- *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 row conversion on the
+ *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / BF16 row conversion on the
  *                           GPU (bit-exact with upstream ggml; absent from the
  *                           reference) -- the KV-cache write side.
  *   fattn_cpy() / fattn_set_rows()   the cache write itself: GGML_OP_CPY into a
@@ -71,13 +71,14 @@ enum fattn_type {
     FATTN_TYPE_Q8_0 = 8,
     FATTN_TYPE_I32 = 26,  /* index tensors of fattn_set_rows only: every other entry point rejects them */
     FATTN_TYPE_I64 = 27,
+    FATTN_TYPE_BF16 = 30, /* 2 bytes per element; K / V of fattn_ext, dst of fattn_cpy (not of fattn_set_rows) */
 };
 
 enum fattn_status {
     FATTN_OK = 0,
     FATTN_ERR_INVALID_ARG = -1,     /* NULL pointer, bad shape, ne not divisible */
     FATTN_ERR_UNSUPPORTED_TYPE = -2,
-    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1), 128 or 256 -- or the MLA pair, K 576 with V 512 (f16, Q8_0 or Q4_0) */
+    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1 / BF16), 128 or 256 -- or the MLA pair, K 576 with V 512 (f16, Q8_0 or Q4_0) */
     FATTN_ERR_BAD_STRIDE = -4,       /* layout the kernels cannot address */
     FATTN_ERR_WORKSPACE = -5,        /* workspace too small */
     FATTN_ERR_LAUNCH = -6,           /* HIP launch failure */
@@ -95,8 +96,8 @@ typedef struct fattn_tensor {
 
 /* GGML_OP_FLASH_ATTN_EXT:
  *   q    f32  ne = [D, n_q, H, S]        (any nb with nb[0] == 4)
- *   k    F16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
- *   v    the same types  ne = [D, N, Hkv, Skv]; rows contiguous, or for F16 only
+ *   k    F16/BF16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
+ *   v    the same types  ne = [D, N, Hkv, Skv]; rows contiguous, or for F16 only (not BF16)
  *        transposed (nb[1] == 2, nb[0] == N*2 style strides).  v's type may
  *        differ from k's (llama.cpp's separate K / V cache types) at D = 64,
  *        128 and 256: the split-KV kernel takes every such pair of F16 / Q8_0 /
@@ -109,6 +110,31 @@ typedef struct fattn_tensor {
  *        (FATTN_ERR_UNSUPPORTED_HEAD_DIM: Q5_0 rows would be 66 bytes, no whole
  *        number of dwords) and a pair that mixes one of them with any other
  *        type (FATTN_ERR_UNSUPPORTED_TYPE)
+ *        BF16 (ggml type 30, llama.cpp's --cache-type-k/-v bf16: the cache of a
+ *        bf16-trained model, whose K norms and outlier V channels pass f16's
+ *        65504): K and V both BF16, at D = 64, 128 and 256, under the F16 row
+ *        rules unchanged -- nb[0] == 2, rows contiguous, [Hkv][N][row],
+ *        [N][Hkv][row] and padded rows all qualify, the 16-B path when bases and
+ *        strides are multiples of 16 and the dword path otherwise.  Every shape
+ *        (one-row decode, GQA tiles, batched decode, prefill-sized n_q) runs the
+ *        split-KV kernel over the raw rows; nothing is staged or converted to f16.
+ *        Values: K and V enter v_mfma_f32_16x16x32_bf16 exactly (any finite bf16,
+ *        up to 3.4e38); Q and the unnormalised probabilities enter as two bf16
+ *        operands each, hi = bf16(x) and lo = bf16(x - hi) (round to nearest
+ *        even), two MFMAs into one f32 accumulator -- 16 operand bits, so the
+ *        result is closer to exact arithmetic than the F16 path's (11 bits).
+ *        Accumulators, softmax state and every chunk partial are f32 (a BF16
+ *        plan never takes f16 partials).  Mask, mask planes, scale, max_bias,
+ *        logit_softcap, n_head_total / head_first, sinks, kv_chunk and the
+ *        workspace rules keep their meaning; the workspace is the F16 split
+ *        plan's with f32 partials.  fattn_describe:
+ *        fattn_split_kernel<bf16,bf16,D128,gran16,mask,4waves>...  Refused, before
+ *        anything launches: BF16 paired with any other K / V type
+ *        (FATTN_ERR_UNSUPPORTED_TYPE), D = 80 / 96 (FATTN_ERR_UNSUPPORTED_HEAD_DIM),
+ *        a transposed BF16 V, v.nb[0] != 2 (FATTN_ERR_BAD_STRIDE), the MLA shape
+ *        (FATTN_ERR_UNSUPPORTED_TYPE); fattn_row stays f16-only.  The cache write
+ *        is fattn_cpy / fattn_quantize; fattn_set_rows has NO BF16 form yet (a
+ *        BF16 dst there is FATTN_ERR_UNSUPPORTED_TYPE)
  *   mask F16 ne = [N', rows >= n_q] with N' >= N rounded up to even (ggml pads
  *        mask rows to GGML_KQ_MASK_PAD), 4-byte aligned rows; row = query
  *        index; or data == NULL for no mask.  ne[2] and ne[3] are plane counts,
@@ -304,24 +330,32 @@ int fattn_row(const float* query, const void* key, const void* value, const void
               int head_stride, int r_kv_heads, void* stream);
 
 /* ggml row conversions on the GPU (n_rows rows of k elements each, contiguous).
- * dequantize: Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/F16 -> f32 (bit-exact with ggml dequantize_row_*).
- * quantize:   f32 -> Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 (bit-exact with ggml quantize_row_*_ref). */
+ * dequantize: Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/F16/BF16 -> f32 (bit-exact with ggml dequantize_row_*;
+ *             BF16: exact, the bits shifted up by 16).
+ * quantize:   f32 -> Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 (bit-exact with ggml quantize_row_*_ref), or
+ *             f32 -> BF16 (any k >= 1, src 4-byte aligned): ggml_compute_fp32_to_bf16 bit for
+ *             bit, in integer arithmetic -- with u the f32 bits, a NaN ((u & 0x7fffffff) >
+ *             0x7f800000) gives (u >> 16) | 64 (kept, made quiet), anything else
+ *             (u + 0x7fff + ((u >> 16) & 1)) >> 16: round to nearest even, subnormals kept,
+ *             overflow to inf. */
 int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n_rows, void* stream);
 int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_rows, void* stream);
 
-/* GGML_OP_CPY f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view: the KV-cache write
+/* GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view: the KV-cache write
  * (quantize-on-write; upstream ggml cpy_f32_q /
  * cpy_f32_f16, absent from the reference).  src: f32, nb[0] = 4; dst: same ne,
  * nb[0] = element / block bytes, any nb[1..3] -- e.g. one token's Hkv rows
  * written into a [Hkv][N][row] cache (nb1 = N * row bytes) or a [N][Hkv][row]
- * cache (nb1 = row bytes).  ne[0] a multiple of 32 for the block types.  Values
- * bit-exact with ggml quantize_row_*_ref / f16 round-to-nearest-even. */
+ * cache (nb1 = row bytes).  ne[0] a multiple of 32 for the block types; BF16 under
+ * the F16 rules (any ne0 >= 1, nb[0] == 2).  Values bit-exact with ggml
+ * quantize_row_*_ref / f16 round-to-nearest-even / the BF16 rule of fattn_quantize. */
 int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
 
 /* GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: the KV-cache write by slot
  * index (upstream ggml_set_rows(a, b, c) with dst = a, src = b, idx = c; absent
  * from the reference).  The slots are data in device memory, not launch
- * arguments: one captured graph serves every decode step.
+ * arguments: one captured graph serves every decode step.  (No BF16 dst yet:
+ * FATTN_ERR_UNSUPPORTED_TYPE; a BF16 cache is written with fattn_cpy.)
  *   src  F32  ne = [ne0, nr, ne2, ne3]; nb[0] == 4, nb[1..3] any multiples of 4,
  *        4-byte aligned base (a 16-byte aligned base with nb[1..3] multiples of
  *        16 reads 16 B per lane, anything else 4 B at a time: same bytes written)
@@ -354,7 +388,7 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
 int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, const fattn_tensor* dst, void* stream);
 
 const char* fattn_strerror(int status);
-/* bytes of one row of k elements (0 if unsupported) */
+/* bytes of one row of k elements (0 if unsupported; BF16: 2 k) */
 size_t fattn_row_size(int type, int64_t k);
 /* library version string */
 const char* fattn_version(void);

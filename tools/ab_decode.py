@@ -17,6 +17,12 @@ lengths spread evenly over (0, N]; mask=shared (the default) is one full-length
 plane for all of them:
 
   python tools/ab_decode.py --workload config3_s64 --variant shared: --variant ragged:mask=ragged
+
+--kv_type takes every cache type of fattn.TYPE_NAMES (bf16 included); the variant
+key kv_type= gives one variant a cache type of its own over the same values, so
+two types alternate within one run (the bytes of f16 and bf16 are the same):
+
+  python tools/ab_decode.py --workload config2 --variant f16: --variant bf16:kv_type=bf16
 """
 import argparse
 import os
@@ -45,7 +51,7 @@ def main():
     ap.add_argument("--workload", default="config3", choices=sorted(SHAPES))
     ap.add_argument("--variant", action="append", default=[],
                     help="name:OPT=val,OPT=val (OPT without the OPT_ prefix); 'kv_chunk=' sets the chunk, "
-                         "'mask=ragged' a mask plane per sequence")
+                         "'mask=ragged' a mask plane per sequence, 'kv_type=' the variant's own cache type")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--lib", default="", help="FATTN_LIB override (a variant library under lib/)")
@@ -70,15 +76,21 @@ def main():
     dev = torch.device("cuda", 0)
     R = max(16 if S == 1 else 2, -(-(512 << 20) // (2 * S * Hkv * N * rb)))
     g = torch.Generator(device=dev)
-    g.manual_seed(1234)
-    kvs = []
-    for _ in range(R):
-        pair = []
-        for _ in range(2):
-            x = torch.rand((S * Hkv * N, D), generator=g, device=dev) * 2 - 1
-            pair.append(x.to(torch.float16).view(torch.uint8).reshape(-1) if typ == fattn.TYPE_F16
-                        else fattn.quantize(x, typ).reshape(-1))
-        kvs.append(pair)
+
+    def caches(t):
+        """R rotated (K, V) caches of type t, the same values for every type"""
+        g.manual_seed(1234)
+        out = []
+        for _ in range(R):
+            pair = []
+            for _ in range(2):
+                x = torch.rand((S * Hkv * N, D), generator=g, device=dev) * 2 - 1
+                pair.append(x.to(torch.float16).view(torch.uint8).reshape(-1) if t == fattn.TYPE_F16
+                            else fattn.quantize(x, t).reshape(-1))
+            out.append(pair)
+        return out
+
+    kv_of = {typ: caches(typ)}
     q = torch.rand((S, NQ, H, D), generator=g, device=dev) * 2 - 1
     npad = (N + 63) // 64 * 64
     masks = [(torch.rand((NQ, npad), generator=g, device=dev) * 2 - 1).to(torch.float16) for _ in range(R)]
@@ -96,28 +108,33 @@ def main():
     variants = []
     for spec in args.variant or ["base:"]:
         name, _, opts = spec.partition(":")
-        od, chunk, mk = {}, 0, masks
+        od, chunk, mk, vt = {}, 0, masks, typ
         for kv in filter(None, opts.split(",")):
             k, _, v = kv.partition("=")
             if k == "kv_chunk":
                 chunk = int(v)
             elif k == "mask":
                 mk = {"shared": masks, "ragged": ragged}[v]
+            elif k == "kv_type":
+                vt = fattn.TYPE_NAMES[v]
+                if vt not in kv_of:
+                    kv_of[vt] = caches(vt)
             else:
                 od[getattr(fattn, "OPT_" + k)] = int(v)
-        variants.append((name, od, chunk, mk))
+        variants.append((name, od, chunk, mk, vt))
 
     hip, evs = hip_events(2)
     gs = torch.cuda.Stream(dev)
     graphs = []
-    for name, od, chunk, mk in variants:
+    for name, od, chunk, mk, vt in variants:
+        kvs = kv_of[vt]
         with fattn.options(od):
-            att = fattn.Attention(fattn.q_view(q), fattn.kv_view(kvs[0][0], typ, D, N, Hkv, S),
-                                  fattn.kv_view(kvs[0][1], typ, D, N, Hkv, S), fattn.mask_view(mk[0]), outs[0],
+            att = fattn.Attention(fattn.q_view(q), fattn.kv_view(kvs[0][0], vt, D, N, Hkv, S),
+                                  fattn.kv_view(kvs[0][1], vt, D, N, Hkv, S), fattn.mask_view(mk[0]), outs[0],
                                   1.0 / D ** 0.5, kv_chunk=chunk)
             desc = att.describe()
 
-            def step(i, att=att, mk=mk):
+            def step(i, att=att, mk=mk, kvs=kvs):
                 att.retarget(k=kvs[i % R][0].data_ptr(), v=kvs[i % R][1].data_ptr(), dst=outs[i % R].data_ptr(),
                              mask=mk[i % R].data_ptr())
                 att()
