@@ -236,6 +236,21 @@ struct Views {
 };
 constexpr int64_t kSpanMax = (int64_t)0xFFFFFFF0;
 
+// The span of a row-strided K / V view with its N rows rounded up to whole key
+// tiles.  A kernel that fetches whole tiles forms the offset (n0 + row) * nb[1]
+// of the rows from N to the end of the last tile like any other and counts on
+// them to fall past the descriptor (zeros, no traffic).  They do while the
+// offset does not wrap in 32 bits: with rows tens of MiB apart, row N + 1 of a
+// view whose span is near the limit lands back INSIDE the descriptor, and
+// whatever bytes lie there reach the K and V tiles (a NaN among them survives
+// the zero probability: 0 * NaN).  make_plan therefore holds this span, not
+// the view's own, to kSpanMax for the split kernel -- the one kernel that uses
+// such rows unguarded (the MLA kernel guards them, the batched-decode kernels
+// skip their 32-key quarters, the others take whole tiles only).
+inline int64_t tile_span(int64_t span, int64_t nb1, int64_t N, int64_t tile) {
+    return span + ((N + tile - 1) / tile * tile - N) * nb1;
+}
+
 // ggml's op_params[1], [2] and the global head numbering of the slopes
 inline int check_scalars(const fattn_params* p, Views& w, int64_t H) {
     if (!std::isfinite(p->max_bias) || p->max_bias < 0.0f) return FATTN_ERR_INVALID_ARG;
@@ -909,6 +924,12 @@ inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl)
         a.m_hp = 1;
         if (w.m_span_h + w.m_span + 64 > kSpanMax) return FATTN_ERR_BAD_STRIDE;
     }
+    // split kernel: whole 32-key steps without a row guard (issue_step), so the
+    // rows up to the end of the last step must not wrap (tile_span; a
+    // transposed V has N % 32 == 0 and no such rows)
+    if (tile_span(w.k_span, p->k.nb[1], w.N, kStep) > kSpanMax ||
+        (!w.v_trans && tile_span(w.v_span, p->v.nb[1], w.N, kStep) > kSpanMax))
+        return FATTN_ERR_BAD_STRIDE;
     return size_split(pl, o, p->kv_chunk, Y, w.S, w.N, w.NQ);
 }
 

@@ -156,6 +156,15 @@ typedef struct fattn_tensor {
  *        grows with the plane count (fattn_workspace_size)
  *   dst  f32 contiguous [S][n_q][H][D]
  *   H % Hkv == 0 (GQA broadcast), S % Skv == 0.
+ *   Spans: nb[2] / nb[3] of every tensor are 64-bit (planes may lie more than
+ *   4 GiB apart); inside one plane the kernels address with 32 bits, so the
+ *   bytes one (kv head, sequence) plane of K or V covers, (N - 1)*nb[1] + row
+ *   ((D - 1)*nb[0] + 2 N for a transposed V), and the bytes the rows and heads
+ *   of one sequence of Q cover, (n_q - 1)*nb[1] + (H - 1)*nb[2] + 4 D, must not
+ *   exceed 0xFFFFFFF0 (FATTN_ERR_BAD_STRIDE).  The split-KV kernel fetches K
+ *   and V in whole 32-key steps: where it runs, the limit holds for N rounded
+ *   up to a multiple of 32 -- it bites only a cache whose rows lie MiB apart
+ *   and whose span ends within one step of 4 GiB.
  *   softmax(scale * q.k^T + mask) . v per (seq, head, query row).  A row whose
  *   mask is -inf everywhere yields NaN, as the reference's softmax does
  *   (src/utils.h:30-49).
