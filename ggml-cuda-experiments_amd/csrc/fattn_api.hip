@@ -139,11 +139,7 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
     Plan pl;
     const int rc = plan_now(p, pl);
     if (rc != FATTN_OK) return rc;
-    auto tn = [](int t) {
-        return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
-               : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == VT_F16T ? "f16T"
-               : t == FATTN_TYPE_BF16 ? "bf16" : "f16";
-    };
+    auto tn = [](int t) { return t == VT_F16T ? "f16T" : type_name(t); };
     const char* hm = pl.a.has_mask ? "mask" : "nomask";
     // the second-launch merge `name` of the plan, or its in-kernel merge (split, batched decode)
     char merge[64] = "";
@@ -253,6 +249,9 @@ int launch_ext(const fattn_params* p, const float* sinks, void* stream, void* ev
     }
 }
 
+// one 256-thread workgroup per 256 units (elements or blocks) of the conversion kernels
+dim3 grid256(int64_t units) { return dim3((unsigned)((units + 255) / 256)); }
+
 }  // namespace
 
 extern "C" {
@@ -282,8 +281,7 @@ int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void
     fattn_params p;
     std::memset(&p, 0, sizeof(p));
     p.q = {q, FATTN_TYPE_F32, 0, {ne00, ne01, ne02, ne03}, {4, nb01, nb02, nb03}};
-    const int64_t kb0 = is_row16(k_type) ? 2 : (int64_t)fattn_row_size(k_type, 32);
-    const int64_t vb0 = is_row16(v_type) ? 2 : (int64_t)fattn_row_size(v_type, 32);
+    const int64_t kb0 = type_desc(k_type).block_bytes, vb0 = type_desc(v_type).block_bytes;
     p.k = {k, k_type, 0, {ne10, ne11, ne12, ne13}, {kb0, nb11, nb12, nb13}};
     p.v = {v, v_type, 0, {ne10, ne11, ne12, ne13}, {vb0, nb11, nb12, nb13}};
     // mask rows hold nb31 / 2 halves: ggml pads them (GGML_KQ_MASK_PAD) past ne11,
@@ -350,33 +348,16 @@ int fattn_row(const float* query, const void* key, const void* value, const void
 
 int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n_rows, void* stream) {
     if (!src || !dst || k <= 0 || n_rows <= 0) return FATTN_ERR_INVALID_ARG;
+    if (!in_list(CacheTypes(), type)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (is_quant(type) && k % QK) return FATTN_ERR_INVALID_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int64_t n = k * n_rows;
-    if (type == FATTN_TYPE_F16) {
-        hipLaunchKernelGGL(dequant_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           (const uint16_t*)src, dst, n);
-    } else if (type == FATTN_TYPE_BF16) {
-        hipLaunchKernelGGL(dequant_bf16_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                           (const uint16_t*)src, dst, n);
-    } else if (is_quant(type)) {
-        if (k % QK) return FATTN_ERR_INVALID_ARG;
-        const int64_t nb = n / QK;
-        const dim3 grid((unsigned)((nb + 255) / 256));
-        if (type == FATTN_TYPE_Q4_1)
-            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
-        else if (type == FATTN_TYPE_Q5_0)
-            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
-        else if (type == FATTN_TYPE_Q5_1)
-            hipLaunchKernelGGL(dequant_ext_kernel<FATTN_TYPE_Q5_1>, grid, dim3(256), 0, st, (const uint8_t*)src, dst, nb);
-        else if (type == FATTN_TYPE_Q8_0)
-            hipLaunchKernelGGL(dequant_q8_0_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st,
-                               (const uint8_t*)src, dst, nb);
-        else
-            hipLaunchKernelGGL(dequant_q4_0_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st,
-                               (const uint8_t*)src, dst, nb);
-    } else {
-        return FATTN_ERR_UNSUPPORTED_TYPE;
-    }
+    visit(CacheTypes(), type, 0, [&](auto tc) {
+        constexpr int T = decltype(tc)::value;
+        if constexpr (is_row16(T)) hipLaunchKernelGGL(dequant_row16_kernel<T>, grid256(n), dim3(256), 0, st, (const uint16_t*)src, dst, n);
+        else hipLaunchKernelGGL(dequant_kernel<T>, grid256(n / QK), dim3(256), 0, st, (const uint8_t*)src, dst, n / QK);
+        return 0;
+    });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
 }
 
@@ -386,29 +367,17 @@ int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_r
     if (type == FATTN_TYPE_BF16) {  // per element: any row length, 4-byte aligned src, 2-byte aligned dst
         if ((uintptr_t)src % 4 || (uintptr_t)dst % 2) return FATTN_ERR_ALIGNMENT;
         const int64_t n = k * n_rows;
-        hipLaunchKernelGGL(quant_bf16_kernel<>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, (uint16_t*)dst, n);
+        hipLaunchKernelGGL(quant_bf16_kernel<>, grid256(n), dim3(256), 0, st, src, (uint16_t*)dst, n);
         return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
     }
     if (k % QK) return FATTN_ERR_INVALID_ARG;
     if ((uintptr_t)src % 16) return FATTN_ERR_ALIGNMENT;
+    if (!is_quant(type)) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int64_t nb = k * n_rows / QK;
-    if (type == FATTN_TYPE_Q8_0)
-        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q8_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
-                           (uint8_t*)dst, nb);
-    else if (type == FATTN_TYPE_Q4_0)
-        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q4_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
-                           (uint8_t*)dst, nb);
-    else if (type == FATTN_TYPE_Q4_1)
-        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q4_1>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
-                           (uint8_t*)dst, nb);
-    else if (type == FATTN_TYPE_Q5_0)
-        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q5_0>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
-                           (uint8_t*)dst, nb);
-    else if (type == FATTN_TYPE_Q5_1)
-        hipLaunchKernelGGL(quant_kernel<FATTN_TYPE_Q5_1>, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, src,
-                           (uint8_t*)dst, nb);
-    else
-        return FATTN_ERR_UNSUPPORTED_TYPE;
+    visit(StageTypes(), type, 0, [&](auto tc) {
+        hipLaunchKernelGGL(quant_kernel<decltype(tc)::value>, grid256(nb), dim3(256), 0, st, src, (uint8_t*)dst, nb);
+        return 0;
+    });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
 }
 
@@ -416,10 +385,10 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     if (!src || !dst || !src->data || !dst->data) return FATTN_ERR_INVALID_ARG;
     if (src->type != FATTN_TYPE_F32 || src->nb[0] != 4) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int t = dst->type;
-    if (!is_row16(t) && !is_quant(t)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (!in_list(CacheTypes(), t)) return FATTN_ERR_UNSUPPORTED_TYPE;
     for (int i = 0; i < 4; i++)
         if (src->ne[i] != dst->ne[i] || src->ne[i] <= 0) return FATTN_ERR_INVALID_ARG;
-    const int64_t ue = is_row16(t) ? 1 : QK;
+    const int64_t ue = type_desc(t).block_elems;
     if (src->ne[0] % ue) return FATTN_ERR_INVALID_ARG;
     if (dst->nb[0] != (int64_t)fattn_row_size(t, ue)) return FATTN_ERR_BAD_STRIDE;
     if ((uintptr_t)src->data % 4 || src->nb[1] % 4 || src->nb[2] % 4 || src->nb[3] % 4) return FATTN_ERR_ALIGNMENT;
@@ -431,16 +400,12 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     a.snb1 = src->nb[1]; a.snb2 = src->nb[2]; a.snb3 = src->nb[3];
     a.dnb1 = dst->nb[1]; a.dnb2 = dst->nb[2]; a.dnb3 = dst->nb[3];
     const int64_t units = a.ne0 / ue * a.ne1 * a.ne2 * a.ne3;
-    const dim3 grid((unsigned)((units + 255) / 256));
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    if (t == FATTN_TYPE_F16) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_F16>, grid, dim3(256), 0, st, a, units);
-    else if (t == FATTN_TYPE_BF16) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_BF16>, grid, dim3(256), 0, st, a, units);
-    else if (t == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q8_0>, grid, dim3(256), 0, st, a, units);
-    else if (t == FATTN_TYPE_Q4_1) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, a, units);
-    else if (t == FATTN_TYPE_Q5_0) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, a, units);
-    else if (t == FATTN_TYPE_Q5_1) hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q5_1>, grid, dim3(256), 0, st, a, units);
-    else hipLaunchKernelGGL(cpy_f32_kernel<FATTN_TYPE_Q4_0>, grid, dim3(256), 0, st, a, units);
+    visit(CacheTypes(), t, 0, [&](auto tc) {
+        hipLaunchKernelGGL(cpy_f32_kernel<decltype(tc)::value>, grid256(units), dim3(256), 0, st, a, units);
+        return 0;
+    });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
 }
 

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/fattn_debug.h"
 
 namespace fattn {
@@ -27,71 +29,106 @@ typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
 // ggml block geometry
 constexpr int QK = 32;
-constexpr int kQ8Bytes = 34;  // {f16 d; int8 qs[32]}
-constexpr int kQ4Bytes = 18;  // {f16 d; uint8 qs[16]}
 
+// ---------------------------------------------------------------- types
+// A compile-time list of ints (ggml types, head dims), membership in it, and
+// the one dispatcher from a run-time value to a template argument:
+// f(std::integral_constant<int, V>()) for the V of the list equal to v, `none`
+// where v is not of the list.
+template <int... Vs>
+struct ValueList {};
+template <int... Vs>
+__host__ __device__ constexpr bool in_list(ValueList<Vs...>, int v) {
+    return ((v == Vs) || ...);
+}
+template <int... Vs, typename R, typename F>
+R visit(ValueList<Vs...>, int v, R none, F&& f) {
+    R r = none;
+    (void)((v == Vs ? (r = f(std::integral_constant<int, Vs>()), true) : false) || ...);
+    return r;
+}
+
+// One description per type: TypeInfo<T> is all the library knows about the
+// layout of T.  Rows of 16-bit elements (block_elems = 1) or of ggml blocks of
+// 32 elements {f16 d; [f16 m;] [u8 qh[4];] qs}: element j of a 4- / 5-bit block
+// in the low nibble of qs[j], j + 16 in the high one, bit j of the
+// little-endian u32 qh its fifth bit; x = q d + m (has_min) or (q - code_zero) d.
+template <int BE, int BB, bool MIN = false, bool QH = false, int QHO = 4, int QSO = 2, int ZERO = 0>
+struct RowLayout {
+    static constexpr int block_elems = BE, block_bytes = BB;
+    static constexpr bool has_min = MIN, has_qh = QH;        // the block holds m / qh
+    static constexpr int qh_off = QHO, qs_off = QSO;         // ... byte offsets of qh and qs in it
+    static constexpr int code_zero = ZERO;                   // the code's zero point, where the kernels subtract one
+};
 template <int T>
 struct TypeInfo;
-template <>
-struct TypeInfo<FATTN_TYPE_F16> {
-    static constexpr int block_elems = 1;
-    static constexpr int block_bytes = 2;
-};
+template <> struct TypeInfo<FATTN_TYPE_F32> : RowLayout<1, 4> { static constexpr const char* name = "f32"; };
+template <> struct TypeInfo<FATTN_TYPE_F16> : RowLayout<1, 2> { static constexpr const char* name = "f16"; };
 // BF16 rows are raw 16-bit elements like F16 rows: the same bytes per row, the
 // same HBM -> LDS -> VGPR moves (is_row16); only the MFMA that takes them differs
-template <>
-struct TypeInfo<FATTN_TYPE_BF16> {
-    static constexpr int block_elems = 1;
-    static constexpr int block_bytes = 2;
-};
-__host__ __device__ constexpr bool is_row16(int t) { return t == FATTN_TYPE_F16 || t == FATTN_TYPE_BF16; }
-template <>
-struct TypeInfo<FATTN_TYPE_Q8_0> {
-    static constexpr int block_elems = QK;
-    static constexpr int block_bytes = kQ8Bytes;
-};
-template <>
-struct TypeInfo<FATTN_TYPE_Q4_0> {
-    static constexpr int block_elems = QK;
-    static constexpr int block_bytes = kQ4Bytes;
-};
+template <> struct TypeInfo<FATTN_TYPE_BF16> : RowLayout<1, 2> { static constexpr const char* name = "bf16"; };
+template <> struct TypeInfo<FATTN_TYPE_Q8_0> : RowLayout<QK, 34> { static constexpr const char* name = "q8_0"; };  // {f16 d; int8 qs[32]}
+template <> struct TypeInfo<FATTN_TYPE_Q4_0> : RowLayout<QK, 18> { static constexpr const char* name = "q4_0"; };  // {f16 d; u8 qs[16]}, x = (q - 8) d
+template <> struct TypeInfo<FATTN_TYPE_Q4_1> : RowLayout<QK, 20, true, false, 4, 4> { static constexpr const char* name = "q4_1"; };
+template <> struct TypeInfo<FATTN_TYPE_Q5_0> : RowLayout<QK, 22, false, true, 2, 6, 16> { static constexpr const char* name = "q5_0"; };
+template <> struct TypeInfo<FATTN_TYPE_Q5_1> : RowLayout<QK, 24, true, true, 4, 8> { static constexpr const char* name = "q5_1"; };
 
-// Q4_1 {f16 d; f16 m; u8 qs[16]}, Q5_0 {f16 d; u8 qh[4]; u8 qs[16]}, Q5_1 {f16 d;
-// f16 m; u8 qh[4]; u8 qs[16]}: element j in the low nibble of qs[j], j + 16 in
-// the high one, bit j of the little-endian u32 qh its fifth bit.
-// x = q d + m (Q4_1, Q5_1) or (q - 16) d (Q5_0)
-constexpr int kQ41Bytes = 20;
-constexpr int kQ50Bytes = 22;
-constexpr int kQ51Bytes = 24;
-template <>
-struct TypeInfo<FATTN_TYPE_Q4_1> {
-    static constexpr int block_elems = QK;
-    static constexpr int block_bytes = kQ41Bytes;
-};
-template <>
-struct TypeInfo<FATTN_TYPE_Q5_0> {
-    static constexpr int block_elems = QK;
-    static constexpr int block_bytes = kQ50Bytes;
-};
-template <>
-struct TypeInfo<FATTN_TYPE_Q5_1> {
-    static constexpr int block_elems = QK;
-    static constexpr int block_bytes = kQ51Bytes;
-};
+// The type lists every dispatch site names (a new cache type joins the ones it belongs to)
+using CacheTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;
+using RowTypes = ValueList<FATTN_TYPE_F32, FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // fattn_row_size
+using CoreTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0>;  // every kernel family; mixed K / V pairs; MLA
+using QuantTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0>;                 // ... the block types among them
+// the three block types with a fifth bit and / or an affine term (is_kv_ext):
+// only the split kernel and the prefill staging take them
+using ExtTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;
+using SplitOnlyTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_BF16>;  // K and V of one type, D = 64 / 128 / 256
+using StageTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // block types: staged to f16 for prefill, quantize / dequantize
+using SetRowsTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // (no BF16)
 
-// The three block types with a fifth bit and / or an affine term: whether T is
-// one of them, whether its blocks hold m / qh, the byte offsets of qh and qs in
-// a block, and the code's zero point (Q5_0: 16)
-__host__ __device__ constexpr bool is_kv_ext(int t) {
-    return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1;
+// TypeInfo by run-time type: the row of type t, or the empty row (block_elems = 0)
+struct TypeDesc {
+    const char* name;
+    int block_elems, block_bytes;
+    bool has_min, has_qh;
+    int qh_off, qs_off, code_zero;
+};
+template <int T>
+constexpr TypeDesc desc_of() {
+    using I = TypeInfo<T>;
+    return {I::name, I::block_elems, I::block_bytes, I::has_min, I::has_qh, I::qh_off, I::qs_off, I::code_zero};
 }
-__host__ __device__ constexpr bool has_min(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_1; }
-__host__ __device__ constexpr bool has_qh(int t) { return t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1; }
-__host__ __device__ constexpr int qh_off(int t) { return t == FATTN_TYPE_Q5_0 ? 2 : 4; }
-__host__ __device__ constexpr int qs_off(int t) {
-    return t == FATTN_TYPE_Q4_1 ? 4 : t == FATTN_TYPE_Q5_0 ? 6 : t == FATTN_TYPE_Q5_1 ? 8 : 2;
+template <int... Ts>
+__host__ __device__ constexpr TypeDesc type_desc(ValueList<Ts...>, int t) {
+    TypeDesc d = {"?", 0, 0, false, false, 4, 2, 0};
+    ((t == Ts ? (void)(d = desc_of<Ts>()) : (void)0), ...);
+    return d;
 }
-__host__ __device__ constexpr int code_zero(int t) { return t == FATTN_TYPE_Q5_0 ? 16 : 0; }
+__host__ __device__ constexpr TypeDesc type_desc(int t) { return type_desc(CacheTypes(), t); }
+
+constexpr const char* type_name(int t) { return type_desc(t).name; }
+__host__ __device__ constexpr bool is_row16(int t) { return type_desc(t).block_bytes == 2 && type_desc(t).block_elems == 1; }
+__host__ __device__ constexpr bool is_quant(int t) { return type_desc(t).block_elems == QK; }  // the ggml block types a cache may hold
+__host__ __device__ constexpr bool is_kv_ext(int t) { return in_list(ExtTypes(), t); }
+__host__ __device__ constexpr bool has_min(int t) { return type_desc(t).has_min; }
+__host__ __device__ constexpr bool has_qh(int t) { return type_desc(t).has_qh; }
+__host__ __device__ constexpr int qh_off(int t) { return type_desc(t).qh_off; }
+__host__ __device__ constexpr int qs_off(int t) { return type_desc(t).qs_off; }
+__host__ __device__ constexpr int code_zero(int t) { return type_desc(t).code_zero; }
+constexpr int kQ8Bytes = TypeInfo<FATTN_TYPE_Q8_0>::block_bytes;
+constexpr int kQ4Bytes = TypeInfo<FATTN_TYPE_Q4_0>::block_bytes;
+
+// bytes of one row of k elements (fattn_row_size); 0: no whole number of blocks, or no such type
+constexpr size_t row_size(int type, int64_t k) {
+    const TypeDesc d = type_desc(RowTypes(), type);
+    return d.block_elems == 0 || k % d.block_elems ? 0 : (size_t)(k / d.block_elems) * d.block_bytes;
+}
+
+// waves per SIMD of the split kernel's register budget: its __launch_bounds__
+// and the planner's occupancy figure (size_split)
+// (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4)
+__host__ __device__ constexpr int split_bounds_wps(int kt, int gran, int D) {
+    return (is_row16(kt) || gran == 4 || D == 256 || is_kv_ext(kt)) ? 2 : 4;
+}
 
 template <int T, int D>
 constexpr int row_bytes() {

@@ -35,6 +35,41 @@ enum class Kernel {
     Mla,      // MLA kernel (fattn_mla.h): K dim 576, V dim 512; f16, or Q8_0 / Q4_0 with V a view of K
 };
 
+// ---------------------------------------------------------------- which kernels exist
+// The one statement of the (kernel, K type, V type, head dim) the library
+// instantiates: the launchers' `if constexpr` guards, the planner's choice
+// (choose_kernel), its LDS sizes (lds_bytes_of) and make_plan's last check all
+// read it.  vt may be VT_F16T; Kernel::Mla: D is K's row length.
+using HeadDims = ValueList<64, 80, 96, 128, 256>;
+using VTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, VT_F16T>;  // CacheTypes and the transposed f16 V
+// head dims of the split kernel over mixed K / V types and over SplitOnlyTypes
+constexpr bool split_dim3(int D) { return D == 64 || D == 128 || D == 256; }
+// the split kernel's loader-wave form (fattn_split_ld_kernel): one K / V type of CoreTypes, D = 64 / 128
+constexpr bool split_ld_ok(int kt, int vt, int D) { return kt == vt && in_list(CoreTypes(), kt) && (D == 64 || D == 128); }
+
+template <Kernel K>
+using KernelC = std::integral_constant<Kernel, K>;
+
+constexpr bool has_kernel(Kernel kern, int kt, int vt, int D) {
+    const bool f16 = kt == FATTN_TYPE_F16 && vt == FATTN_TYPE_F16;
+    const bool quant = kt == vt && in_list(QuantTypes(), kt);  // Q8_0 / Q4_0: the kernels below the split kernel
+    switch (kern) {
+        case Kernel::Split:
+            if (kt == FATTN_TYPE_F16 && vt == VT_F16T) return in_list(HeadDims(), D);
+            if (kt != vt) return in_list(CoreTypes(), kt) && in_list(CoreTypes(), vt) && split_dim3(D);
+            if (in_list(SplitOnlyTypes(), kt)) return split_dim3(D);
+            return f16 ? in_list(HeadDims(), D) : quant && D != 80 && in_list(HeadDims(), D);  // (80 is not a whole number of ggml blocks)
+        case Kernel::SplitLd: return split_ld_ok(kt, vt, D);
+        case Kernel::Mq: return quant && split_dim3(D);
+        case Kernel::Pf: return (f16 && D == 80) || ((f16 || quant) && (D == 64 || D == 96 || D == 128));
+        case Kernel::Pf4: return f16 && D == 128;
+        case Kernel::Bd: return (quant && D == 128) || (f16 && (D == 64 || D == 96 || D == 128));  // (Q8_0 / Q4_0: D = 128 only)
+        case Kernel::Bdp: return quant && (D == 64 || D == 96 || D == 128);
+        case Kernel::Mla: return kt == vt && in_list(CoreTypes(), kt) && D == kMlaDK;
+    }
+    return false;
+}
+
 struct Plan {
     SplitArgs a = {};
     Kernel kernel = Kernel::Split;
@@ -149,7 +184,7 @@ void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
 int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
     if (pl.kernel == Kernel::SplitLd) {
-        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && KT == VT && !is_kv_ext(KT) && KT != FATTN_TYPE_BF16 && (D == 64 || D == 128)) {
+        if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && split_ld_ok(KT, VT, D)) {
             auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders>;
             return launch_kernel((const void*)lk, pl, st, ev, [&] {
                 hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, pl.a);
@@ -244,8 +279,15 @@ int launch_mq(const Plan& pl, hipStream_t st, const Events& ev) {
     return pl.a.has_mask ? launch_mq_hm<KT, D, 4, true>(pl, st, ev) : launch_mq_hm<KT, D, 4, false>(pl, st, ev);
 }
 
-// the prefill pre-pass staging a Q4_1 / Q5_0 / Q5_1 cache (pf_prepass_kernel<stage_kt>;
-// instantiated in fattn_launch_kv_ext.hip)
+// the prefill pre-pass staging a cache of one of `Types` (pf_prepass_kernel<stage_kt>)
+template <typename Types>
+void launch_prepass(Types, int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa) {
+    visit(Types(), stage_kt, 0, [&](auto t) {
+        hipLaunchKernelGGL(pf_prepass_kernel<decltype(t)::value>, grid, dim3(256), 0, st, pa);
+        return 0;
+    });
+}
+// ... of ExtTypes (instantiated in fattn_launch_kv_ext.hip)
 void launch_prepass_kv_ext(int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa);
 
 template <int KT, int D, bool HM>
@@ -254,7 +296,7 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     // planner keeps such launches off the one-wave-per-SIMD bodies)
     void (*kern)(SplitArgs) = pl.a.xf.live ? fattn_pf_kernel<KT, D, HM, true> : fattn_pf_kernel<KT, D, HM, false>;
     int waves = kPfWaves;
-    if constexpr (KT == FATTN_TYPE_F16 && D == 128) {
+    if constexpr (has_kernel(Kernel::Pf4, KT, KT, D)) {
         if (pl.kernel == Kernel::Pf4) {
             if (pl.pf4_sched == 4) kern = fattn_pf4_kernel<D, HM, 4>;
             else if (pl.pf4_sched == 3) kern = fattn_pf4_kernel<D, HM, 3>;
@@ -285,8 +327,7 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             const dim3 g((unsigned)(nst + nfl));
             if (!staged) hipLaunchKernelGGL(pf_prepass_kernel<0>, g, dim3(256), 0, st, pa);
             else if (is_kv_ext(pl.stage_kt)) launch_prepass_kv_ext(pl.stage_kt, g, st, pa);
-            else if (pl.stage_kt == FATTN_TYPE_Q8_0) hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q8_0>, g, dim3(256), 0, st, pa);
-            else hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q4_0>, g, dim3(256), 0, st, pa);
+            else launch_prepass(QuantTypes(), pl.stage_kt, g, st, pa);
         }
         hipLaunchKernelGGL(kern, pl.grid, dim3(waves * kWave), pl.lds, st, pl.a);
     });
@@ -298,10 +339,10 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
 template <int KT, int D, bool HM>
 int launch_bd_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     void (*kern)(SplitArgs) = nullptr;
-    if constexpr (D == 128 || KT == FATTN_TYPE_F16) {
+    if constexpr (has_kernel(Kernel::Bd, KT, KT, D)) {
         if (pl.kernel == Kernel::Bd) kern = fattn_bd_kernel<KT, D, HM>;
     }
-    if constexpr (KT != FATTN_TYPE_F16) {
+    if constexpr (has_kernel(Kernel::Bdp, KT, KT, D)) {
         if (pl.kernel == Kernel::Bdp) kern = fattn_bdp_kernel<KT, D, HM>;
     }
     if (kern == nullptr) return FATTN_ERR_UNSUPPORTED_TYPE;
@@ -325,14 +366,14 @@ int launch_pf(const Plan& pl, hipStream_t st, const Events& ev) {
 // fattn_launch_mixed_d<D>.hip; D = 64, 128, 256)
 template <int D>
 int launch_mixed(const Plan& pl, hipStream_t st, const Events& ev) {
-    constexpr int F16 = FATTN_TYPE_F16, Q8 = FATTN_TYPE_Q8_0, Q4 = FATTN_TYPE_Q4_0;
-    if (pl.kt == Q8 && pl.vt == F16) return launch_gran<Q8, F16, D>(pl, st, ev);
-    if (pl.kt == Q4 && pl.vt == F16) return launch_gran<Q4, F16, D>(pl, st, ev);
-    if (pl.kt == F16 && pl.vt == Q8) return launch_gran<F16, Q8, D>(pl, st, ev);
-    if (pl.kt == F16 && pl.vt == Q4) return launch_gran<F16, Q4, D>(pl, st, ev);
-    if (pl.kt == Q8 && pl.vt == Q4) return launch_gran<Q8, Q4, D>(pl, st, ev);
-    if (pl.kt == Q4 && pl.vt == Q8) return launch_gran<Q4, Q8, D>(pl, st, ev);
-    return FATTN_ERR_UNSUPPORTED_TYPE;
+    constexpr int none = FATTN_ERR_UNSUPPORTED_TYPE;
+    return visit(CoreTypes(), pl.kt, none, [&](auto k) {
+        return visit(CoreTypes(), pl.vt, none, [&](auto v) {
+            constexpr int KT = decltype(k)::value, VT = decltype(v)::value;
+            if constexpr (KT != VT) return launch_gran<KT, VT, D>(pl, st, ev);
+            else return none;
+        });
+    });
 }
 extern template int launch_mixed<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_mixed<128>(const Plan&, hipStream_t, const Events&);
@@ -370,53 +411,41 @@ extern template int launch_bf16<256>(const Plan&, hipStream_t, const Events&);
 // fattn_launch_d<D>.hip)
 template <int D>
 int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
-    constexpr int F16 = FATTN_TYPE_F16, Q8 = FATTN_TYPE_Q8_0, Q4 = FATTN_TYPE_Q4_0;
-    const bool f16 = pl.kt == F16 && pl.vt == F16, q8 = pl.kt == Q8 && pl.vt == Q8, q4 = pl.kt == Q4 && pl.vt == Q4;
-    // a (kernel, type, D) the library has no instantiation of falls through to the error below
+    // a (kernel, type, D) the library has no instantiation of (has_kernel) is this error
+    constexpr int none = FATTN_ERR_UNSUPPORTED_TYPE;
+    // K and V of one type of `types` that has one of `kerns` at this D: go(type)
+    auto same = [&](auto types, auto go, auto... kerns) {
+        if (pl.kt != pl.vt) return none;
+        return visit(types, pl.kt, none, [&](auto k) {
+            if constexpr ((has_kernel(decltype(kerns)::value, decltype(k)::value, decltype(k)::value, D) || ...)) return go(k);
+            else return none;
+        });
+    };
     switch (pl.kernel) {
         case Kernel::Pf:
         case Kernel::Pf4:
-            if constexpr (D == 64 || D == 80 || D == 96 || D == 128) {
-                if (f16) return launch_pf<F16, D>(pl, st, ev);
-                if constexpr (D != 80) {  // (80 is not a whole number of ggml blocks)
-                    if (q8) return launch_pf<Q8, D>(pl, st, ev);
-                    if (q4) return launch_pf<Q4, D>(pl, st, ev);
-                }
-            }
-            break;
+            return same(CoreTypes(), [&](auto k) { return launch_pf<decltype(k)::value, D>(pl, st, ev); }, KernelC<Kernel::Pf>());
         case Kernel::Bd:
-        case Kernel::Bdp:
-            if constexpr (D == 64 || D == 96 || D == 128) {
-                if (q8) return launch_bd<Q8, D>(pl, st, ev);
-                if (q4) return launch_bd<Q4, D>(pl, st, ev);
-                if (f16) return launch_bd<F16, D>(pl, st, ev);
-            }
-            break;
+        case Kernel::Bdp:  // (a type with either form: launch_bd_hm picks)
+            return same(CoreTypes(), [&](auto k) { return launch_bd<decltype(k)::value, D>(pl, st, ev); }, KernelC<Kernel::Bd>(), KernelC<Kernel::Bdp>());
         case Kernel::Mq:
-            if constexpr (D == 64 || D == 128 || D == 256) {
-                if (q8) return launch_mq<Q8, D>(pl, st, ev);
-                if (q4) return launch_mq<Q4, D>(pl, st, ev);
-            }
-            break;
+            return same(QuantTypes(), [&](auto k) { return launch_mq<decltype(k)::value, D>(pl, st, ev); }, KernelC<Kernel::Mq>());
         case Kernel::Split:
         case Kernel::SplitLd:
-            if constexpr (D == 64 || D == 128 || D == 256) {
-                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q4_1) return launch_kv_ext<FATTN_TYPE_Q4_1, D>(pl, st, ev);
-                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_0) return launch_kv_ext<FATTN_TYPE_Q5_0, D>(pl, st, ev);
-                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_Q5_1) return launch_kv_ext<FATTN_TYPE_Q5_1, D>(pl, st, ev);
-                if (pl.kt == pl.vt && pl.kt == FATTN_TYPE_BF16) return pl.kernel == Kernel::Split ? launch_bf16<D>(pl, st, ev) : FATTN_ERR_UNSUPPORTED_TYPE;
+            if constexpr (split_dim3(D)) {  // (the translation units of their own: extern templates above)
                 if (pl.kt != pl.vt && pl.vt != VT_F16T) return launch_mixed<D>(pl, st, ev);
+                if (pl.kt == pl.vt && in_list(SplitOnlyTypes(), pl.kt))
+                    return visit(SplitOnlyTypes(), pl.kt, none, [&](auto k) {
+                        constexpr int KT = decltype(k)::value;
+                        if constexpr (is_row16(KT)) return pl.kernel == Kernel::Split ? launch_bf16<D>(pl, st, ev) : none;
+                        else return launch_kv_ext<KT, D>(pl, st, ev);
+                    });
             }
-            if constexpr (D % QK == 0) {
-                if (q8) return launch_gran<Q8, Q8, D>(pl, st, ev);
-                if (q4) return launch_gran<Q4, Q4, D>(pl, st, ev);
-            }
-            if (f16) return launch_gran<F16, F16, D>(pl, st, ev);
-            if (pl.kt == F16 && pl.vt == VT_F16T) return launch_gran<F16, VT_F16T, D>(pl, st, ev);
-            break;
+            if (pl.kt == FATTN_TYPE_F16 && pl.vt == VT_F16T) return launch_gran<FATTN_TYPE_F16, VT_F16T, D>(pl, st, ev);
+            return same(CoreTypes(), [&](auto k) { return launch_gran<decltype(k)::value, decltype(k)::value, D>(pl, st, ev); }, KernelC<Kernel::Split>());
         case Kernel::Mla: break;  // (launch_mla: no head dim of this table)
     }
-    return FATTN_ERR_UNSUPPORTED_TYPE;
+    return none;
 }
 
 // the MLA kernels (instantiated in fattn_launch_mla.hip)

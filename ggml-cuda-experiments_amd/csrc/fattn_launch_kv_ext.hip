@@ -5,8 +5,6 @@
 
 namespace fattn {
 void launch_prepass_kv_ext(int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa) {
-    if (stage_kt == FATTN_TYPE_Q4_1) hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q4_1>, grid, dim3(256), 0, st, pa);
-    else if (stage_kt == FATTN_TYPE_Q5_0) hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q5_0>, grid, dim3(256), 0, st, pa);
-    else hipLaunchKernelGGL(pf_prepass_kernel<FATTN_TYPE_Q5_1>, grid, dim3(256), 0, st, pa);
+    launch_prepass(ExtTypes(), stage_kt, grid, st, pa);
 }
 }  // namespace fattn

@@ -32,7 +32,7 @@ int launch_mla_q_type(const Plan& pl, hipStream_t st, const Events& ev) {
 }  // namespace
 
 int launch_mla_q(const Plan& pl, hipStream_t st, const Events& ev) {
-    return pl.kt == FATTN_TYPE_Q8_0 ? launch_mla_q_type<FATTN_TYPE_Q8_0>(pl, st, ev) : launch_mla_q_type<FATTN_TYPE_Q4_0>(pl, st, ev);
+    return visit(QuantTypes(), pl.kt, (int)FATTN_ERR_UNSUPPORTED_TYPE, [&](auto k) { return launch_mla_q_type<decltype(k)::value>(pl, st, ev); });
 }
 
 }  // namespace fattn

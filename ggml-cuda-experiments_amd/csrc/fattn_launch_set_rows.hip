@@ -12,10 +12,6 @@ using namespace fattn;
 
 namespace {
 
-constexpr bool set_rows_dst_type(int t) {
-    return t == FATTN_TYPE_F16 || t == FATTN_TYPE_Q8_0 || t == FATTN_TYPE_Q4_0 || is_kv_ext(t);
-}
-
 // Units (32-element blocks) over all planes from which a lane group takes
 // kSetRowsUnroll of them: 2^17 units are 4096 workgroups at one unit per group,
 // still 1024 -- four per CU of an MI355X -- at four.  Below that the chip is not
@@ -42,14 +38,14 @@ extern "C" int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, 
     if (src->type != FATTN_TYPE_F32) return FATTN_ERR_UNSUPPORTED_TYPE;
     if (idx->type != FATTN_TYPE_I64 && idx->type != FATTN_TYPE_I32) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int t = dst->type;
-    if (!set_rows_dst_type(t)) return FATTN_ERR_UNSUPPORTED_TYPE;
+    if (!in_list(SetRowsTypes(), t)) return FATTN_ERR_UNSUPPORTED_TYPE;
     for (int i = 0; i < 4; i++)
         if (src->ne[i] <= 0 || idx->ne[i] <= 0 || dst->ne[i] <= 0) return FATTN_ERR_INVALID_ARG;
     const int64_t ne0 = src->ne[0], nr = src->ne[1], ne2 = src->ne[2], ne3 = src->ne[3];
     const int64_t ne11 = idx->ne[1], ne12 = idx->ne[2];
     if (dst->ne[0] != ne0 || dst->ne[2] != ne2 || dst->ne[3] != ne3) return FATTN_ERR_INVALID_ARG;
     if (idx->ne[0] != nr || idx->ne[3] != 1 || ne2 % ne11 || ne3 % ne12) return FATTN_ERR_INVALID_ARG;
-    const int64_t ue = t == FATTN_TYPE_F16 ? 1 : QK;
+    const int64_t ue = type_desc(t).block_elems;
     if (ne0 % ue) return FATTN_ERR_INVALID_ARG;
     // units of one [ne0, nr] plane are numbered in 32 bits (one division per thread)
     const int64_t upr = (ne0 + QK - 1) / QK;
@@ -93,13 +89,9 @@ extern "C" int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, 
     const bool unroll = a.units >= 8 * 32 * kSetRowsUnroll && (double)a.units * (double)ne2 * (double)ne3 >= (double)kUnrollMinUnits;
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
-    switch (t) {
-        case FATTN_TYPE_F16: launch<FATTN_TYPE_F16>(vec, unroll, grid, st, a); break;
-        case FATTN_TYPE_Q8_0: launch<FATTN_TYPE_Q8_0>(vec, unroll, grid, st, a); break;
-        case FATTN_TYPE_Q4_0: launch<FATTN_TYPE_Q4_0>(vec, unroll, grid, st, a); break;
-        case FATTN_TYPE_Q4_1: launch<FATTN_TYPE_Q4_1>(vec, unroll, grid, st, a); break;
-        case FATTN_TYPE_Q5_0: launch<FATTN_TYPE_Q5_0>(vec, unroll, grid, st, a); break;
-        default: launch<FATTN_TYPE_Q5_1>(vec, unroll, grid, st, a); break;
-    }
+    visit(SetRowsTypes(), t, 0, [&](auto tc) {
+        launch<decltype(tc)::value>(vec, unroll, grid, st, a);
+        return 0;
+    });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
 }

@@ -91,40 +91,40 @@ constexpr int kMqMinRowsDefault = 64;  // multi-query kernel from this many pack
 constexpr int kLdsPerCU = 163840;
 
 // LDS bytes of one workgroup of `kern` at compile-time (K type, V type, D);
-// 0: no such kernel.  Split kernel: `waves` waves with `nbuf` steps in flight
-// each (a wave's bytes are this / waves; the loader form adds its flags).
+// 0 exactly when there is no such kernel (has_kernel).  Split kernel: `waves`
+// waves with `nbuf` steps in flight each (a wave's bytes are this / waves; the
+// loader form adds its flags).
 template <int KT, int VT, int D>
 int lds_bytes_of(Kernel kern, int waves, int nbuf) {
-    constexpr int F16 = FATTN_TYPE_F16;
-    constexpr bool quant = !is_row16(KT) && KT == VT && !is_kv_ext(KT);  // (Q8_0 / Q4_0: the kernels below the split kernel)
-    if constexpr (KT == FATTN_TYPE_BF16) {  // the split kernel alone (no loader-wave form)
-        if (kern != Kernel::Split) return 0;
-    }
     switch (kern) {
         case Kernel::Split:
-        case Kernel::SplitLd: {
-            using C = SplitCfg<KT, VT, D>;
-            const int w = std::max((nbuf * C::stepBytes + C::vscBytes + 15) / 16 * 16, (int)C::mergeBytes);
-            return waves * w + (kern == Kernel::SplitLd ? kSplitLdFlagBytes : 0);
-        }
-        case Kernel::Mq:
-            if constexpr (quant && D == 256)  // 64-row workgroups only (256 rows' mask tiles do not fit beside the D = 256 images)
+        case Kernel::SplitLd:
+            if constexpr (has_kernel(Kernel::Split, KT, VT, D)) {
+                if (kern == Kernel::SplitLd && !split_ld_ok(KT, VT, D)) break;
+                using C = SplitCfg<KT, VT, D>;
+                const int w = std::max((nbuf * C::stepBytes + C::vscBytes + 15) / 16 * 16, (int)C::mergeBytes);
+                return waves * w + (kern == Kernel::SplitLd ? kSplitLdFlagBytes : 0);
+            }
+            break;
+        case Kernel::Mq:  // D = 256: 64-row workgroups only (256 rows' mask tiles do not fit beside the D = 256 images)
+            if constexpr (has_kernel(Kernel::Mq, KT, VT, D)) {
+                if constexpr (D != 256) {
+                    if (waves == 8) return MQCfg<KT, D, 8, 32>::ldsBytes;
+                }
                 return MQCfg<KT, D, 4, 16>::ldsBytes;
-            else if constexpr (quant && (D == 64 || D == 128))
-                return waves == 8 ? MQCfg<KT, D, 8, 32>::ldsBytes : MQCfg<KT, D, 4, 16>::ldsBytes;
+            }
             break;
         case Kernel::Pf:
-            if constexpr (KT == VT && D != 256 && !is_kv_ext(KT) && KT != FATTN_TYPE_BF16) return PfCfg<KT, D>::ldsBytes;
+            if constexpr (has_kernel(Kernel::Pf, KT, VT, D)) return PfCfg<KT, D>::ldsBytes;
             break;
         case Kernel::Pf4:
-            if constexpr (KT == F16 && VT == F16 && D == 128) return Pf4Cfg<D>::ldsBytes;
+            if constexpr (has_kernel(Kernel::Pf4, KT, VT, D)) return Pf4Cfg<D>::ldsBytes;
             break;
-        case Kernel::Bd:  // (Q8_0 / Q4_0: D = 128 only)
-            if constexpr ((quant && D == 128) || (KT == F16 && VT == F16 && (D == 64 || D == 96 || D == 128)))
-                return BdCfg<KT, D>::ldsBytes;
+        case Kernel::Bd:
+            if constexpr (has_kernel(Kernel::Bd, KT, VT, D)) return BdCfg<KT, D>::ldsBytes;
             break;
         case Kernel::Bdp:
-            if constexpr (quant && (D == 64 || D == 96 || D == 128)) return BdpCfg<KT, D>::ldsBytes;
+            if constexpr (has_kernel(Kernel::Bdp, KT, VT, D)) return BdpCfg<KT, D>::ldsBytes;
             break;
         case Kernel::Mla: break;  // (size_mla: MlaCfg, no head dim of this table)
     }
@@ -133,61 +133,16 @@ int lds_bytes_of(Kernel kern, int waves, int nbuf) {
 
 // the one dispatch from the plan's runtime (K type, V type, D) to the kernels' constants
 inline int lds_bytes(Kernel kern, int kt, int vt, int D, int waves, int nbuf = 0) {
-    auto with_d = [&](auto k, auto v) {
-        constexpr int KT = decltype(k)::value, VT = decltype(v)::value;
-        switch (D) {
-            case 64: return lds_bytes_of<KT, VT, 64>(kern, waves, nbuf);
-            case 80:  // f16 only (80 is not a whole number of 32-element ggml blocks)
-                if constexpr (KT == FATTN_TYPE_F16 && (VT == FATTN_TYPE_F16 || VT == VT_F16T))
-                    return lds_bytes_of<KT, VT, 80>(kern, waves, nbuf);
-                return 0;
-            case 96: return lds_bytes_of<KT, VT, 96>(kern, waves, nbuf);
-            case 128: return lds_bytes_of<KT, VT, 128>(kern, waves, nbuf);
-            case 256: return lds_bytes_of<KT, VT, 256>(kern, waves, nbuf);
-            default: return 0;
-        }
-    };
-    auto with_v = [&](auto k) {
-        switch (vt) {
-            case FATTN_TYPE_Q8_0: return with_d(k, std::integral_constant<int, FATTN_TYPE_Q8_0>());
-            case FATTN_TYPE_Q4_0: return with_d(k, std::integral_constant<int, FATTN_TYPE_Q4_0>());
-            case VT_F16T: return with_d(k, std::integral_constant<int, VT_F16T>());
-            default: return with_d(k, std::integral_constant<int, FATTN_TYPE_F16>());
-        }
-    };
-    // Q4_1 / Q5_0 / Q5_1 / BF16: K and V of one type, head dims 64 / 128 / 256 (check_views)
-    auto same = [&](auto k) { return D == 80 || D == 96 ? 0 : with_d(k, k); };
-    switch (kt) {
-        case FATTN_TYPE_Q4_1: return same(std::integral_constant<int, FATTN_TYPE_Q4_1>());
-        case FATTN_TYPE_Q5_0: return same(std::integral_constant<int, FATTN_TYPE_Q5_0>());
-        case FATTN_TYPE_Q5_1: return same(std::integral_constant<int, FATTN_TYPE_Q5_1>());
-        case FATTN_TYPE_BF16: return same(std::integral_constant<int, FATTN_TYPE_BF16>());
-        case FATTN_TYPE_Q8_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q8_0>());
-        case FATTN_TYPE_Q4_0: return with_v(std::integral_constant<int, FATTN_TYPE_Q4_0>());
-        default: return with_v(std::integral_constant<int, FATTN_TYPE_F16>());
-    }
+    return visit(CacheTypes(), kt, 0, [&](auto k) {
+        return visit(VTypes(), vt, 0, [&](auto v) {
+            return visit(HeadDims(), D, 0, [&](auto d) {
+                return lds_bytes_of<decltype(k)::value, decltype(v)::value, decltype(d)::value>(kern, waves, nbuf);
+            });
+        });
+    });
 }
 
 // ---------------------------------------------------------------- helpers
-// the ggml block types a cache may hold; is_kv_ext (fattn_common.h) names the
-// three of them only the split kernel and the prefill staging take
-inline bool is_quant(int t) { return t == FATTN_TYPE_Q8_0 || t == FATTN_TYPE_Q4_0 || is_kv_ext(t); }
-
-// bytes of one row of k elements (fattn_row_size)
-inline size_t row_size(int type, int64_t k) {
-    switch (type) {
-        case FATTN_TYPE_F32: return (size_t)k * 4;
-        case FATTN_TYPE_F16: return (size_t)k * 2;
-        case FATTN_TYPE_BF16: return (size_t)k * 2;
-        case FATTN_TYPE_Q8_0: return k % QK ? 0 : (size_t)(k / QK) * kQ8Bytes;
-        case FATTN_TYPE_Q4_0: return k % QK ? 0 : (size_t)(k / QK) * kQ4Bytes;
-        case FATTN_TYPE_Q4_1: return k % QK ? 0 : (size_t)(k / QK) * kQ41Bytes;
-        case FATTN_TYPE_Q5_0: return k % QK ? 0 : (size_t)(k / QK) * kQ50Bytes;
-        case FATTN_TYPE_Q5_1: return k % QK ? 0 : (size_t)(k / QK) * kQ51Bytes;
-        default: return 0;
-    }
-}
-
 // Tile packing: R q heads of a kv head x QPT query rows fill a tile of `rows`
 // packed rows; a kv head's rk2 heads take n_hsub tiles, the NQ query rows n_qt.
 inline void pack_tiles(SplitArgs& a, int rows, int R, int64_t NQ) {
@@ -293,7 +248,7 @@ inline int check_mask(const fattn_tensor& mk, Views& w, int64_t N, int64_t NQ, i
 inline int check_views_mla(const fattn_params* p, Views& w) {
     const fattn_tensor &q = p->q, &k = p->k, &v = p->v, &mk = p->mask;
     if (k.ne[0] != kMlaDK || v.ne[0] != kMlaDV) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
-    const bool quant = k.type == FATTN_TYPE_Q8_0 || k.type == FATTN_TYPE_Q4_0;
+    const bool quant = in_list(QuantTypes(), k.type);
     const int64_t bb = quant ? (int64_t)row_size(k.type, QK) : 2;  // nb[0]: a block's / an element's bytes
     const int64_t rowK = quant ? kMlaDK / QK * bb : kMlaDK * 2, rowV = quant ? kMlaDV / QK * bb : kMlaDV * 2;
     if ((k.type != FATTN_TYPE_F16 && !quant) || v.type != k.type || k.nb[0] != bb || v.nb[0] != bb) return FATTN_ERR_UNSUPPORTED_TYPE;
@@ -484,9 +439,9 @@ inline void choose_kernel(const fattn_params* p, const Views& w, const Options& 
     const bool packed_ok = !o[FATTN_OPT_MQ_DISABLE] && !w.mixed && w.g16 && heads_ok;
     // (Q4_1 / Q5_0 / Q5_1: none of the multi-query and batched-decode kernels -- their
     // shapes fall to the split kernel -- and prefill only through the f16 staging)
-    const bool quant_ok = packed_ok && is_quant(kt) && !is_kv_ext(kt);
+    const bool quant_ok = packed_ok && in_list(QuantTypes(), kt);
     const bool stage_ok = packed_ok && is_kv_ext(kt) && o[FATTN_OPT_PF_STAGE] != 1 && N * D * 2 <= kSpanMax;
-    const bool mq_ok = quant_ok && (D == 64 || D == 128 || D == 256);
+    const bool mq_ok = quant_ok && has_kernel(Kernel::Mq, kt, kt, (int)D);
     // the same packing for f16 K/V rows (not transposed V): the prefill and
     // batched-decode kernels fill their f16 images by LDS-DMA straight from the rows
     const bool f16_ok = packed_ok && kt == FATTN_TYPE_F16 && !w.v_trans;
@@ -510,7 +465,9 @@ inline void choose_kernel(const fattn_params* p, const Views& w, const Options& 
     // (D = 80's padding dims are DMA'd from 0x80000000 past the row offset,
     // outside the descriptor only while the spans stay within 2 GiB: fattn_pf.h)
     const bool d80_ok = f16_ok && w.k_span <= (int64_t)0x80000000 && w.v_span <= (int64_t)0x80000000;
-    const bool pf = (quant_ok || f16_ok || stage_ok) && opt_pf != 1 && (D == 64 || D == 96 || D == 128 || (D == 80 && d80_ok)) &&
+    // (a staged cache: the f16 kernel)
+    const bool pf_dim = has_kernel(Kernel::Pf, stage_ok ? FATTN_TYPE_F16 : kt, stage_ok ? FATTN_TYPE_F16 : kt, (int)D) && (D != 80 || d80_ok);
+    const bool pf = (quant_ok || f16_ok || stage_ok) && opt_pf != 1 && pf_dim &&
                     p->kv_chunk <= 0 && N % kPfKeys == 0 && p->scale > 0.0f &&
                     (opt_pf == 2 || Hkv * S * ((rows + kPfRows - 1) / kPfRows) >= pl.cus);
     // batched decode (config 5: 64 query rows per kv head): 64-row workgroups
@@ -521,15 +478,15 @@ inline void choose_kernel(const fattn_params* p, const Views& w, const Options& 
     // FATTN_OPT_BD = 2 asks for the all-waves form; head dims 64 and 96 (Q8_0 /
     // Q4_0) have the role form only (config-5 shape at D = 64: 19.2 us against
     // 21.3 for the multi-query kernel, profiles/r04_e)
-    const bool bd_dim = (D == 128 && (mq_ok || f16_ok)) || ((D == 64 || D == 96) && quant_ok && opt_bd != 2) ||
-                        ((D == 64 || D == 96) && f16_ok);
+    const Kernel bd_form = quant_ok && opt_bd != 2 ? Kernel::Bdp : Kernel::Bd;
+    const bool bd_dim = (quant_ok || f16_ok) && has_kernel(bd_form, kt, kt, (int)D);
     const bool bd = !pf && opt_bd != 1 && bd_dim && N % kStep == 0 && (opt_bd >= 2 || (rows >= kBdRows && wide));
 
     if (pf) {
         pl.kernel = Kernel::Pf;
         pack_tiles(a, kPfRows, a.rk2, NQ);
     } else if (bd) {
-        pl.kernel = quant_ok && opt_bd != 2 ? Kernel::Bdp : Kernel::Bd;
+        pl.kernel = bd_form;
         pack_tiles(a, kBdRows, a.rk2, NQ);
     } else if (mq) {
         pl.kernel = Kernel::Mq;
@@ -565,7 +522,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     SplitArgs& a = pl.a;
     auto lds = [&](int nbuf, int nwv) { return lds_bytes(Kernel::Split, pl.kt, pl.vt, pl.D, nwv, nbuf); };
     const int64_t steps = (N + kStep - 1) / kStep;
-    const int wps = (is_row16(pl.kt) || pl.gran == 4 || pl.D == 256 || is_kv_ext(pl.kt)) ? 2 : 4;  // __launch_bounds__ waves/SIMD
+    const int wps = split_bounds_wps(pl.kt, pl.gran, pl.D);  // __launch_bounds__ waves/SIMD
     const int rv_max = std::min<int64_t>(kRows, (int64_t)a.R * std::min<int64_t>(a.QPT, NQ));
     const int64_t total = steps * Y * S;
     const bool fused_merge = o[FATTN_OPT_SPLIT_MERGE] != 0;
@@ -637,7 +594,7 @@ inline int size_split(Plan& pl, const Options& o, int kv_chunk, int64_t Y, int64
     // whole chunk fits the LDS (every step resident), 16-B rows, D = 64 / 128,
     // one K / V type; 4 loader waves issue it all up front
     if (o[FATTN_OPT_SPLIT_LOADERS] == 2 && pl.gran == 16 && a.wave_merge == 2 && nwv == 8 && spw >= 2 && spw <= 3 &&
-        (pl.D == 64 || pl.D == 128) && pl.kt == pl.vt && !is_kv_ext(pl.kt) && pl.kt != FATTN_TYPE_BF16 && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
+        split_ld_ok(pl.kt, pl.vt, pl.D) && o[FATTN_OPT_SPLIT_INFLIGHT] == 0 &&
         lds(spw, nwv) + kSplitLdFlagBytes <= kLdsPerCU) {
         pl.kernel = Kernel::SplitLd;
         nbuf = spw;
@@ -837,10 +794,8 @@ inline int size_mla(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N) {
     const int64_t tiles = (N + kStep - 1) / kStep;
     // (the cache's type picks the LDS figure and nothing else: a quantised
     // cache is cut into the chunks of the f16 one)
-    pl.lds = pl.kt == FATTN_TYPE_Q8_0   ? MlaCfg<false, FATTN_TYPE_Q8_0>::ldsBytes
-             : pl.kt == FATTN_TYPE_Q4_0 ? MlaCfg<false, FATTN_TYPE_Q4_0>::ldsBytes
-             : own                      ? MlaCfg<true>::ldsBytes
-                                        : MlaCfg<false>::ldsBytes;
+    pl.lds = visit(QuantTypes(), pl.kt, own ? MlaCfg<true>::ldsBytes : MlaCfg<false>::ldsBytes,
+                   [](auto k) { return MlaCfg<false, decltype(k)::value>::ldsBytes; });
     int64_t nch;
     if (kv_chunk > 0) {
         nch = (N + kv_chunk - 1) / kv_chunk;
@@ -875,9 +830,8 @@ inline int size_mla(Plan& pl, int kv_chunk, int64_t Y, int64_t S, int64_t N) {
 }
 
 // ---------------------------------------------------------------- the planner
-// Validate and build the launch plan for a device of `cus` compute units.
-// Returns FATTN_OK or an error.
-inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl) {
+// make_plan's plan, before its last check
+inline int size_plan(const fattn_params* p, const Options& o, int cus, Plan& pl) {
     Views w;
     const int rc = check_views(p, w);
     if (rc != FATTN_OK) return rc;
@@ -931,6 +885,17 @@ inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl)
         (!w.v_trans && tile_span(w.v_span, p->v.nb[1], w.N, kStep) > kSpanMax))
         return FATTN_ERR_BAD_STRIDE;
     return size_split(pl, o, p->kv_chunk, Y, w.S, w.N, w.NQ);
+}
+
+// Validate and build the launch plan for a device of `cus` compute units.
+// Returns FATTN_OK or an error -- the launcher's own for a plan whose kernel
+// the library does not have (has_kernel: choose_kernel and the launchers read
+// the same table, so this cannot happen; it would show here, not at launch).
+inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl) {
+    const int rc = size_plan(p, o, cus, pl);
+    if (rc != FATTN_OK) return rc;
+    if (!has_kernel(pl.kernel, pl.kt, pl.vt, pl.D)) return pl.kernel == Kernel::SplitLd ? FATTN_ERR_INVALID_ARG : FATTN_ERR_UNSUPPORTED_TYPE;
+    return FATTN_OK;
 }
 
 }  // namespace fattn

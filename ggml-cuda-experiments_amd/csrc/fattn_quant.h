@@ -27,77 +27,63 @@ __device__ __forceinline__ float opaque(float x) {
     return x;
 }
 
-static __global__ __launch_bounds__(256) void dequant_q8_0_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                           int64_t nblocks) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nblocks) return;
-    const uint8_t* blk = src + i * kQ8Bytes;
-    const float d = (float)__builtin_bit_cast(f16, (uint16_t)(blk[0] | (blk[1] << 8)));
-    float* y = dst + i * QK;
-#pragma unroll
-    for (int j = 0; j < QK; j += 4) {
-        f32x4 v;
-        v.x = (float)(int8_t)blk[2 + j] * d;
-        v.y = (float)(int8_t)blk[3 + j] * d;
-        v.z = (float)(int8_t)blk[4 + j] * d;
-        v.w = (float)(int8_t)blk[5 + j] * d;
-        *(f32x4*)(y + j) = v;
-    }
-}
-
-static __global__ __launch_bounds__(256) void dequant_q4_0_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                           int64_t nblocks) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nblocks) return;
-    const uint8_t* blk = src + i * kQ4Bytes;
-    const float d = (float)__builtin_bit_cast(f16, (uint16_t)(blk[0] | (blk[1] << 8)));
-    float* y = dst + i * QK;
-#pragma unroll
-    for (int j = 0; j < QK / 2; j++) {
-        const int b = blk[2 + j];
-        y[j] = (float)((b & 0x0F) - 8) * d;
-        y[j + QK / 2] = (float)((b >> 4) - 8) * d;
-    }
-}
-
-// Q4_1 / Q5_0 / Q5_1 -> f32 (dequantize_row_q4_1 / _q5_0 / _q5_1): one thread per block
+// One ggml block -> its 32 f32 values (dequantize_row_q8_0 / _q4_0 / _q4_1 / _q5_0 / _q5_1)
 template <int T>
-__global__ __launch_bounds__(256) void dequant_ext_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst,
-                                                          int64_t nblocks) {
+__device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, float* __restrict__ y) {
 #pragma clang fp contract(off)
-    static_assert(is_kv_ext(T), "");
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nblocks) return;
-    const uint8_t* blk = src + i * TypeInfo<T>::block_bytes;
+    static_assert(is_quant(T), "");
     const float d = (float)__builtin_bit_cast(f16, (uint16_t)(blk[0] | (blk[1] << 8)));
-    float m = 0.0f;
-    if constexpr (has_min(T)) m = (float)__builtin_bit_cast(f16, (uint16_t)(blk[2] | (blk[3] << 8)));
-    uint32_t qh = 0;
-    if constexpr (has_qh(T)) {
-        const uint8_t* h = blk + qh_off(T);
-        qh = (uint32_t)h[0] | ((uint32_t)h[1] << 8) | ((uint32_t)h[2] << 16) | ((uint32_t)h[3] << 24);
-    }
-    float* y = dst + i * QK;
+    if constexpr (T == FATTN_TYPE_Q8_0) {
 #pragma unroll
-    for (int j = 0; j < QK / 2; j++) {
-        const int b = blk[qs_off(T) + j];
-        const int q0 = (b & 0x0F) | (int)(((qh >> j) & 1u) << 4);
-        const int q1 = (b >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4);
-        if constexpr (has_min(T)) {
-            y[j] = opaque((float)q0 * d) + m;
-            y[j + QK / 2] = opaque((float)q1 * d) + m;
-        } else {
-            y[j] = (float)(q0 - code_zero(T)) * d;
-            y[j + QK / 2] = (float)(q1 - code_zero(T)) * d;
+        for (int j = 0; j < QK; j += 4) {
+            f32x4 v;
+            v.x = (float)(int8_t)blk[2 + j] * d;
+            v.y = (float)(int8_t)blk[3 + j] * d;
+            v.z = (float)(int8_t)blk[4 + j] * d;
+            v.w = (float)(int8_t)blk[5 + j] * d;
+            *(f32x4*)(y + j) = v;
+        }
+    } else {
+        constexpr int zero = T == FATTN_TYPE_Q4_0 ? 8 : code_zero(T);  // (Q4_0's 8: the kernels' nibble trick takes it, not code_zero)
+        float m = 0.0f;
+        if constexpr (has_min(T)) m = (float)__builtin_bit_cast(f16, (uint16_t)(blk[2] | (blk[3] << 8)));
+        uint32_t qh = 0;
+        if constexpr (has_qh(T)) {
+            const uint8_t* h = blk + qh_off(T);
+            qh = (uint32_t)h[0] | ((uint32_t)h[1] << 8) | ((uint32_t)h[2] << 16) | ((uint32_t)h[3] << 24);
+        }
+#pragma unroll
+        for (int j = 0; j < QK / 2; j++) {
+            const int b = blk[qs_off(T) + j];
+            const int q0 = (b & 0x0F) | (int)(((qh >> j) & 1u) << 4);
+            const int q1 = (b >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4);
+            if constexpr (has_min(T)) {
+                y[j] = opaque((float)q0 * d) + m;
+                y[j + QK / 2] = opaque((float)q1 * d) + m;
+            } else {
+                y[j] = (float)(q0 - zero) * d;
+                y[j + QK / 2] = (float)(q1 - zero) * d;
+            }
         }
     }
 }
 
-static __global__ __launch_bounds__(256) void dequant_f16_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst,
-                                                          int64_t n) {
+// block type -> f32: one thread per block
+template <int T>
+__global__ __launch_bounds__(256) void dequant_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int64_t nblocks) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblocks) return;
+    dequant_block<T>(src + i * TypeInfo<T>::block_bytes, dst + i * QK);
+}
+
+// f16 / bf16 -> f32 (bf16: exact, the bits shifted up): one thread per element
+template <int T>
+__global__ __launch_bounds__(256) void dequant_row16_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, int64_t n) {
+    static_assert(is_row16(T), "");
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    dst[i] = (float)__builtin_bit_cast(f16, src[i]);
+    if constexpr (T == FATTN_TYPE_F16) dst[i] = (float)__builtin_bit_cast(f16, src[i]);
+    else dst[i] = __builtin_bit_cast(float, (uint32_t)src[i] << 16);
 }
 
 // f32 -> bf16 bits, ggml_compute_fp32_to_bf16 bit for bit, in integer arithmetic
@@ -110,14 +96,8 @@ __host__ __device__ __forceinline__ uint16_t f32_to_bf16_bits(float x) {
     return (uint16_t)((u + (0x7fffu + ((u >> 16) & 1u))) >> 16);
 }
 
-// bf16 -> f32 (exact: the bits shifted up) and f32 -> bf16, one thread per element
-// (templates, so that only the translation unit that launches them holds them)
-template <int T = FATTN_TYPE_BF16>
-__global__ __launch_bounds__(256) void dequant_bf16_kernel(const uint16_t* __restrict__ src, float* __restrict__ dst, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    dst[i] = __builtin_bit_cast(float, (uint32_t)src[i] << 16);
-}
+// f32 -> bf16, one thread per element
+// (a template, so that only the translation unit that launches it holds it)
 template <int T = FATTN_TYPE_BF16>
 __global__ __launch_bounds__(256) void quant_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -294,44 +274,6 @@ __global__ __launch_bounds__(256) void cpy_f32_kernel(const CpyArgs a, int64_t u
     }
 }
 
-// kv_stage_f16_block (below) for a Q4_1 / Q5_0 / Q5_1 block: the f16 the split kernel's K operand
-// (k_operand_ext, fattn_split.h) produces for the same element.  Q5_0:
-// h((q - 16) d), the exact product rounded once.  Q4_1 / Q5_1: the f16 fma
-// h(q d + m) of the exact code and the block's two f16 fields -- one rounding
-// of the exact sum, where f32 arithmetic (dequantize_row_*, then f16) rounds the
-// sum to f32 first: the two differ by one f16 ulp where that f32 rounding lands
-// on an f16 tie, and nowhere else.
-template <int KT>
-__device__ __forceinline__ void kv_stage_f16_block_ext(const uint8_t* __restrict__ src, int64_t nb2, int64_t nb3,
-                                                       uint16_t* __restrict__ dst, int64_t nblk, int64_t bx, int head,
-                                                       int seq, int gy) {
-    const int64_t t = bx * 256 + threadIdx.x;
-    if (t >= 4 * nblk) return;
-    const int64_t b = t >> 2;
-    const int j = (int)(t & 3);
-    const uint16_t* blk = (const uint16_t*)(src + (int64_t)seq * nb3 + (int64_t)head * nb2 + b * TypeInfo<KT>::block_bytes);
-    const f16 d = __builtin_bit_cast(f16, blk[0]);  // (blocks are 2-byte aligned)
-    f16 m = (f16)0.0f;
-    if constexpr (has_min(KT)) m = __builtin_bit_cast(f16, blk[1]);
-    uint32_t qh8 = 0;  // the fifth bits of elements 8j .. 8j + 7
-    if constexpr (has_qh(KT)) qh8 = ((uint32_t)blk[qh_off(KT) / 2 + (j >> 1)] >> (8 * (j & 1))) & 0xFFu;
-    const uint16_t* qw = blk + qs_off(KT) / 2 + 4 * (j & 1);
-    f16x8 h;
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const uint32_t w = qw[e];
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const uint32_t by = k ? w >> 8 : w & 0xFF;
-            const int q = (int)((j < 2 ? by & 0x0F : by >> 4) | (((qh8 >> (2 * e + k)) & 1u) << 4));
-            if constexpr (has_min(KT)) h[2 * e + k] = __builtin_fmaf16((f16)q, d, m);
-            else h[2 * e + k] = (f16)(q - code_zero(KT)) * d;
-        }
-    }
-    uint16_t* y = dst + (((int64_t)seq * gy + head) * nblk + b) * QK + 8 * j;
-    *(f16x8*)y = h;
-}
-
 // Prefill K/V staging (the prefill planner's default for Q8_0 / Q4_0 caches):
 // the quantised rows of every (sequence, kv head) -- contiguous blocks, head
 // base at ik3 * nb3 + ik2 * nb2 -- become f16 rows [Skv][Hkv][N][D] in the
@@ -346,29 +288,55 @@ template <int KT>
 __device__ __forceinline__ void kv_stage_f16_block(const uint8_t* __restrict__ src, int64_t nb2, int64_t nb3,
                                                    uint16_t* __restrict__ dst, int64_t nblk, int64_t bx, int head,
                                                    int seq, int gy) {
-    if constexpr (is_kv_ext(KT)) return kv_stage_f16_block_ext<KT>(src, nb2, nb3, dst, nblk, bx, head, seq, gy);
     const int64_t t = bx * 256 + threadIdx.x;
     if (t >= 4 * nblk) return;
     const int64_t b = t >> 2;
     const int j = (int)(t & 3);
-    constexpr int BB = KT == FATTN_TYPE_Q8_0 ? kQ8Bytes : kQ4Bytes;
-    const uint8_t* blk = src + (int64_t)seq * nb3 + (int64_t)head * nb2 + b * BB;
-    const float d = (float)__builtin_bit_cast(f16, *(const uint16_t*)blk);  // (blocks are 2-byte aligned)
-    const uint16_t* qw = (const uint16_t*)(blk + 2 + (KT == FATTN_TYPE_Q8_0 ? 8 * j : 8 * (j & 1)));
-    uint32_t by[8];
-#pragma unroll
-    for (int e = 0; e < 4; e++) {
-        const uint32_t w = qw[e];
-        by[2 * e] = w & 0xFF;
-        by[2 * e + 1] = w >> 8;
-    }
+    const uint8_t* blk8 = src + (int64_t)seq * nb3 + (int64_t)head * nb2 + b * TypeInfo<KT>::block_bytes;
+    const uint16_t* blk = (const uint16_t*)blk8;  // (blocks are 2-byte aligned)
     f16x8 h;
+    if constexpr (is_kv_ext(KT)) {
+        // Q4_1 / Q5_0 / Q5_1: the f16 the split kernel's K operand (k_operand_ext,
+        // fattn_split.h) produces for the same element.  Q5_0: h((q - 16) d), the
+        // exact product rounded once.  Q4_1 / Q5_1: the f16 fma h(q d + m) of the
+        // exact code and the block's two f16 fields -- one rounding of the exact
+        // sum, where f32 arithmetic (dequantize_row_*, then f16) rounds the sum to
+        // f32 first: the two differ by one f16 ulp where that f32 rounding lands on
+        // an f16 tie, and nowhere else.
+        const f16 d = __builtin_bit_cast(f16, blk[0]);
+        f16 m = (f16)0.0f;
+        if constexpr (has_min(KT)) m = __builtin_bit_cast(f16, blk[1]);
+        uint32_t qh8 = 0;  // the fifth bits of elements 8j .. 8j + 7
+        if constexpr (has_qh(KT)) qh8 = ((uint32_t)blk[qh_off(KT) / 2 + (j >> 1)] >> (8 * (j & 1))) & 0xFFu;
+        const uint16_t* qw = blk + qs_off(KT) / 2 + 4 * (j & 1);
 #pragma unroll
-    for (int e = 0; e < 8; e++) {
-        float q;
-        if constexpr (KT == FATTN_TYPE_Q8_0) q = (float)(int8_t)by[e];
-        else q = (float)((int)(j < 2 ? by[e] & 0x0F : by[e] >> 4) - 8);  // elements 0-15 low nibbles, 16-31 high
-        h[e] = (f16)(q * d);  // exact product (<= 19 significant bits), one rounding to f16
+        for (int e = 0; e < 4; e++) {
+            const uint32_t w = qw[e];
+#pragma unroll
+            for (int k = 0; k < 2; k++) {
+                const uint32_t by = k ? w >> 8 : w & 0xFF;
+                const int q = (int)((j < 2 ? by & 0x0F : by >> 4) | (((qh8 >> (2 * e + k)) & 1u) << 4));
+                if constexpr (has_min(KT)) h[2 * e + k] = __builtin_fmaf16((f16)q, d, m);
+                else h[2 * e + k] = (f16)(q - code_zero(KT)) * d;
+            }
+        }
+    } else {
+        const float d = (float)__builtin_bit_cast(f16, blk[0]);
+        const uint16_t* qw = (const uint16_t*)(blk8 + 2 + (KT == FATTN_TYPE_Q8_0 ? 8 * j : 8 * (j & 1)));
+        uint32_t by[8];
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const uint32_t w = qw[e];
+            by[2 * e] = w & 0xFF;
+            by[2 * e + 1] = w >> 8;
+        }
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            float q;
+            if constexpr (KT == FATTN_TYPE_Q8_0) q = (float)(int8_t)by[e];
+            else q = (float)((int)(j < 2 ? by[e] & 0x0F : by[e] >> 4) - 8);  // elements 0-15 low nibbles, 16-31 high
+            h[e] = (f16)(q * d);  // exact product (<= 19 significant bits), one rounding to f16
+        }
     }
     uint16_t* y = dst + (((int64_t)seq * gy + head) * nblk + b) * QK + 8 * j;
     *(f16x8*)y = h;

@@ -1826,10 +1826,9 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
 }
 
 // waves per SIMD the split kernel's register budget allows (__launch_bounds__)
-// (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4)
 template <int KT, int D, int GRAN>
 constexpr int split_waves_per_simd() {
-    return (is_row16(KT) || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4;
+    return split_bounds_wps(KT, GRAN, D);
 }
 
 // NWV waves per workgroup (4, 8 or 16), each streaming its own slice of the
@@ -1840,7 +1839,7 @@ constexpr int split_waves_per_simd() {
 // XF (split_step): instantiated for NWV = 4 only; the planner sizes a launch
 // with max_bias / logit_softcap live for 4 waves (size_split).
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false>
-__global__ __launch_bounds__(NWV * kWave, (is_row16(KT) || GRAN == 4 || D == 256 || is_kv_ext(KT)) ? 2 : 4) void fattn_split_kernel(
+__global__ __launch_bounds__(NWV * kWave, split_bounds_wps(KT, GRAN, D)) void fattn_split_kernel(
     const SplitArgs a) {
     using C = SplitCfg<KT, VT, D>;
     using P = StepPlan<KT, VT, D, GRAN>;

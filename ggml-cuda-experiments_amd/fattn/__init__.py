@@ -26,7 +26,7 @@ TYPE_I32, TYPE_I64 = 26, 27   # index tensors of set_rows only
 TYPE_BF16 = 30                # 2-byte elements: K / V of flash_attn_ext, dst of cpy / quantize (not of set_rows)
 TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
               "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1, "bf16": TYPE_BF16}
-BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18, TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
+BLOCK_TYPES = (TYPE_Q8_0, TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1)
 
 FATTN_OK = 0
 ERRORS = {
@@ -192,6 +192,17 @@ def row_size(typ: int, k: int) -> int:
     return int(lib().fattn_row_size(typ, k))
 
 
+def elem_bytes(typ: int) -> int:
+    """nb[0] of a contiguous row of typ: an element's bytes, or a ggml block's."""
+    return row_size(typ, 1) or row_size(typ, 32)
+
+
+def __getattr__(name):
+    if name == "BLOCK_BYTES":   # {block type: bytes of a block}, as the library has them
+        return {t: row_size(t, 32) for t in BLOCK_TYPES}
+    raise AttributeError(name)
+
+
 def strerror(code: int) -> str:
     return lib().fattn_strerror(code).decode()
 
@@ -313,7 +324,7 @@ def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "
     its own).
     """
     rb = row_size(typ, D)
-    nb0 = 2 if typ in (TYPE_F16, TYPE_BF16) else BLOCK_BYTES[typ]
+    nb0 = elem_bytes(typ)
     if layout == "head":
         nb = (nb0, rb, rb * N, rb * N * Hkv)
     elif layout == "pos":
@@ -335,7 +346,7 @@ def mla_v_view(k: View, v_off: int = MLA_DK - MLA_DV) -> View:
     A Q8_0 / Q4_0 K view (18 blocks per row): v_off is 0, 32 or 64 elements --
     whole blocks -- and the pointer advances by row_size(type, v_off)."""
     if k.type in (TYPE_Q8_0, TYPE_Q4_0):
-        if int(k.ne[0]) != MLA_DK or int(k.nb[0]) != BLOCK_BYTES[k.type]:
+        if int(k.ne[0]) != MLA_DK or int(k.nb[0]) != elem_bytes(k.type):
             raise ValueError("mla_v_view: a quantised K must have 576-element rows of whole blocks")
         if v_off not in (0, 32, 64):
             raise ValueError("mla_v_view: v_off is 0, 32 or 64 elements (whole blocks) for a quantised K")

@@ -35,6 +35,7 @@ import numpy as np
 from numpy.lib.stride_tricks import as_strided
 
 import fattn
+from problems import elem_bytes, row_bytes  # noqa: F401
 
 MiB, GiB = 1 << 20, 1 << 30
 SPAN_MAX = 0xFFFFFFF0            # fattn_plan.h kSpanMax
@@ -47,14 +48,6 @@ FAR = 4 * GiB + 64 * 1024        # planes more than 4 GiB apart
 POISON_KV, POISON_MASK, POISON_Q = 0x7E7E7E7E, 0x7E007E00, 0x7FC00000   # as little-endian dwords
 
 ROW16 = (fattn.TYPE_F16, fattn.TYPE_BF16)
-
-
-def row_bytes(typ: int, D: int) -> int:
-    return D * 2 if typ in ROW16 else D // 32 * fattn.BLOCK_BYTES[typ]
-
-
-def elem_bytes(typ: int) -> int:
-    return 2 if typ in ROW16 else fattn.BLOCK_BYTES[typ]
 
 
 def down16(x: int) -> int:

@@ -34,7 +34,7 @@ import numpy as np
 
 import views
 from oracle import oracle as orc
-from problems import Problem, make_problem
+from problems import Problem, make_problem, row_bytes  # noqa: F401 (row_bytes: this module's users take it from here)
 
 F = np.float32
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
@@ -43,10 +43,6 @@ BLOCK_BYTES = {TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
 QS_OFF = {TYPE_Q4_1: 4, TYPE_Q5_0: 6, TYPE_Q5_1: 8}
 QH_OFF = {TYPE_Q5_0: 2, TYPE_Q5_1: 4}
 QK = 32
-
-
-def row_bytes(typ: int, D: int) -> int:
-    return D // QK * BLOCK_BYTES[typ]
 
 
 def _h_bytes(x: np.ndarray) -> np.ndarray:

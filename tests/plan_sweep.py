@@ -10,6 +10,7 @@ As a script it regenerates the fixture or dumps the full text for a diff:
 
 (FATTN_LIB=/path/to/other/libfattn.so dumps another build's plans.)"""
 import ctypes as C
+import dataclasses
 import hashlib
 import json
 import os
@@ -23,11 +24,15 @@ for _p in (ROOT, os.path.join(ROOT, "ggml-cuda-experiments_amd")):
 import fattn  # noqa: E402
 
 F16, Q8, Q4 = fattn.TYPE_F16, fattn.TYPE_Q8_0, fattn.TYPE_Q4_0
-TYPE_NAME = {F16: "f16", Q8: "q8_0", Q4: "q4_0"}
+Q41, Q50, Q51, BF16 = fattn.TYPE_Q4_1, fattn.TYPE_Q5_0, fattn.TYPE_Q5_1, fattn.TYPE_BF16
+TYPE_NAME = {F16: "f16", Q8: "q8_0", Q4: "q4_0", Q41: "q4_1", Q50: "q5_0", Q51: "q5_1", BF16: "bf16"}
 PTR = 1 << 20  # (alignment-only placeholder: nothing is launched)
 
 HEAD_DIMS = (64, 80, 96, 128, 256)
 TYPE_PAIRS = ((F16, F16), (Q8, Q8), (Q4, Q4), (Q8, F16), (F16, Q4), (Q8, Q4))
+# the one-type caches of the split kernel (and the staged prefill), and a pair the
+# library rejects: over SHAPES_1T at every head dim, the error codes of D = 80 / 96 included
+TYPE_PAIRS_1T = ((Q41, Q41), (Q50, Q50), (Q51, Q51), (BF16, BF16), (Q50, F16))
 # (NQ, H, Hkv, S, N): the BASELINE configs 2-5, their 2- / 4- / 8-rank head
 # shards, prefill and batched shapes, and small awkward ones
 SHAPES = (
@@ -51,6 +56,13 @@ SHAPES = (
     (1, 8, 8, 1, 131072),      # N = 131072
     (3, 6, 6, 2, 16384),       # few heads, long KV
 )
+# TYPE_PAIRS_1T: decode (configs 3 - 5), prefill (one and two sequences), 64
+# packed rows, and the awkward ones
+SHAPES_1T = tuple(SHAPES[i] for i in (1, 4, 6, 10, 11, 14, 15, 16, 17))
+# MLA (K dim 576, V dim 512, one kv head): (H, NQ, N) over every V form of MLA_V
+MLA_SHAPES = tuple((H, NQ, N) for H in (16, 128) for NQ in (1, 4) for N in (33, 4096, 131072))
+# (K type, V: None of its own, else elements into the K row -- fattn.mla_v_view)
+MLA_V = ((F16, 64), (F16, None), (Q8, 0), (Q8, 64), (Q4, 0), (Q4, 64))
 MASKS = ("none", "one", "head", "seq")
 XFORMS = (dict(), dict(logit_softcap=30.0), dict(max_bias=8.0))
 KV_CHUNKS = (0, 1024)
@@ -114,7 +126,7 @@ def settings():
 
 def _kv(t, D, N, Hkv, S, layout):
     rb = fattn.row_size(t, D)
-    nb0 = 2 if t == F16 else fattn.BLOCK_BYTES[t]
+    nb0 = fattn.elem_bytes(t)
     nb = (nb0, rb, rb * N, rb * N * Hkv) if layout == "head" else (nb0, rb * Hkv, rb, rb * N * Hkv)
     return fattn.View(PTR, t, (D, N, Hkv, S), nb)
 
@@ -132,23 +144,54 @@ def group_name(D, kt, vt):
     return f"D{D}/{TYPE_NAME[kt]}/{TYPE_NAME[vt]}"
 
 
+def _variants(q, k, v, NQ, H, S, N):
+    """(label suffix, FattnParams) of one (q, k, v) over the masks, score transforms and kv_chunk hints."""
+    for mode in MASKS:
+        m = _mask(mode, NQ, H, S, N)
+        for xi, xf in enumerate(XFORMS):
+            for chunk in KV_CHUNKS:
+                yield f"mask:{mode} xf{xi} chunk{chunk}", fattn.ext_params(q, k, v, m, PTR, 0.088, kv_chunk=chunk, **xf)
+
+
+def mla_group(kt):
+    """The MLA cases of cache type kt: MLA_SHAPES x the type's V forms of MLA_V."""
+    DK, DV = fattn.MLA_DK, fattn.MLA_DV
+    cases = []
+    for H, NQ, N in MLA_SHAPES:
+        q = fattn.View(PTR, fattn.TYPE_F32, (DK, NQ, H, 1), (4, H * DK * 4, DK * 4, NQ * H * DK * 4))
+        k = _kv(kt, DK, N, 1, 1, "head")
+        for t, v_off in MLA_V:
+            if t != kt:
+                continue
+            # (V of its own: another buffer, far from K's rows)
+            v = fattn.mla_v_view(k, v_off) if v_off is not None else dataclasses.replace(_kv(kt, DV, N, 1, 1, "head"), ptr=PTR << 12)
+            vname = "own" if v_off is None else f"k+{v_off}"
+            cases += [(f"NQ{NQ} H{H}/1 S1 N{N} v:{vname} {label}", p) for label, p in _variants(q, k, v, NQ, H, 1, N)]
+    return cases
+
+
+def pair_cases(D, kt, vt, shapes):
+    cases = []
+    for NQ, H, Hkv, S, N in shapes:
+        q = fattn.View(PTR, fattn.TYPE_F32, (D, NQ, H, S), (4, H * D * 4, D * 4, NQ * H * D * 4))
+        for layout in LAYOUTS:
+            k, v = _kv(kt, D, N, Hkv, S, layout), _kv(vt, D, N, Hkv, S, layout)
+            cases += [(f"NQ{NQ} H{H}/{Hkv} S{S} N{N} {layout} {label}", p) for label, p in _variants(q, k, v, NQ, H, S, N)]
+    return cases
+
+
 def groups():
-    """{group name: [(case label, FattnParams)]}, built once and planned under every setting."""
+    """{group name: [(case label, FattnParams)]}, built once and planned under every setting.
+    One group per (head dim, pair of TYPE_PAIRS); one per pair of TYPE_PAIRS_1T,
+    its five head dims together (the fixture stays small); one per MLA cache type."""
     out = {}
     for D in HEAD_DIMS:
         for kt, vt in TYPE_PAIRS:
-            cases = []
-            for NQ, H, Hkv, S, N in SHAPES:
-                q = fattn.View(PTR, fattn.TYPE_F32, (D, NQ, H, S), (4, H * D * 4, D * 4, NQ * H * D * 4))
-                for layout in LAYOUTS:
-                    k, v = _kv(kt, D, N, Hkv, S, layout), _kv(vt, D, N, Hkv, S, layout)
-                    for mode in MASKS:
-                        m = _mask(mode, NQ, H, S, N)
-                        for xi, xf in enumerate(XFORMS):
-                            for chunk in KV_CHUNKS:
-                                p = fattn.ext_params(q, k, v, m, PTR, 0.088, kv_chunk=chunk, **xf)
-                                cases.append((f"NQ{NQ} H{H}/{Hkv} S{S} N{N} {layout} mask:{mode} xf{xi} chunk{chunk}", p))
-            out[group_name(D, kt, vt)] = cases
+            out[group_name(D, kt, vt)] = pair_cases(D, kt, vt, SHAPES)
+    for kt, vt in TYPE_PAIRS_1T:
+        out[group_name("*", kt, vt)] = [(f"D{D} {label}", p) for D in HEAD_DIMS for label, p in pair_cases(D, kt, vt, SHAPES_1T)]
+    for kt in (F16, Q8, Q4):
+        out[f"D{fattn.MLA_DK}/mla/{TYPE_NAME[kt]}"] = mla_group(kt)
     return out
 
 
@@ -198,8 +241,11 @@ def main(argv):
     ap.add_argument("--group", help="--dump: only this group, e.g. D128/q8_0/q8_0")
     a = ap.parse_args(argv)
     if a.write:
-        doc = {"cases_per_group": len(next(iter(groups().values()))), "row_workspace": row_workspace_sizes(),
-               "digests": sweep()}
+        G = groups()
+        n = len(next(iter(G.values())))
+        # (cases_per_group: the TYPE_PAIRS groups'; the others' counts by name)
+        doc = {"cases_per_group": n, "cases_of_group": {g: len(c) for g, c in G.items() if len(c) != n},
+               "row_workspace": row_workspace_sizes(), "digests": sweep()}
         with open(a.write, "w") as f:
             json.dump(doc, f, indent=0, sort_keys=True)
             f.write("\n")

@@ -11,13 +11,19 @@ from typing import Optional
 
 import numpy as np
 
+import fattn
 from oracle import oracle as orc
 
 TYPES = {"f16": orc.TYPE_F16, "q8_0": orc.TYPE_Q8_0, "q4_0": orc.TYPE_Q4_0}
 
 
+# bytes of a row of D elements / of nb[0] (an element or a block) of any cache
+# type: the one definition the test modules share
 def row_bytes(typ: int, D: int) -> int:
-    return D * 2 if typ == orc.TYPE_F16 else D // 32 * orc.BLOCK_BYTES[typ]
+    return fattn.row_size(typ, D)
+
+
+elem_bytes = fattn.elem_bytes
 
 
 def encode_rows(x: np.ndarray, typ: int) -> np.ndarray:
@@ -79,7 +85,7 @@ class Problem:
 
     @property
     def elem_bytes_k(self):
-        return 2 if self.kv_type == orc.TYPE_F16 else orc.BLOCK_BYTES[self.kv_type]
+        return elem_bytes(self.kv_type)
 
     def oracle(self, n_threads=8) -> np.ndarray:
         q = (np.ascontiguousarray(self.q), orc.TYPE_F32, self.q_ne, self.q_nb)
@@ -134,7 +140,7 @@ def make_problem(D=128, NQ=1, H=32, Hkv=None, N=4096, kv_type="q8_0", S=1, Skv=N
 
     def place(rows, t):
         rb = row_bytes(t, D)
-        eb = 2 if t == orc.TYPE_F16 else orc.BLOCK_BYTES[t]
+        eb = elem_bytes(t)
         if layout == "head":
             return np.ascontiguousarray(rows), (eb, rb, rb * N, rb * N * Hkv)
         if layout == "pos":

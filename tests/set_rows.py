@@ -19,6 +19,7 @@ import numpy as np
 
 import kv_types as kt
 from oracle import oracle as orc
+from problems import elem_bytes, row_bytes  # noqa: F401
 
 F = np.float32
 QK = 32
@@ -29,14 +30,6 @@ TYPES = {"f16": TYPE_F16, "q8_0": TYPE_Q8_0, "q4_0": TYPE_Q4_0, "q4_1": TYPE_Q4_
          "q5_1": TYPE_Q5_1}
 BLOCK_BYTES = {TYPE_Q8_0: 34, TYPE_Q4_0: 18, TYPE_Q4_1: 20, TYPE_Q5_0: 22, TYPE_Q5_1: 24}
 IDX_DTYPE = {TYPE_I32: np.int32, TYPE_I64: np.int64}
-
-
-def row_bytes(typ: int, ne0: int) -> int:
-    return ne0 * 2 if typ == TYPE_F16 else ne0 // QK * BLOCK_BYTES[typ]
-
-
-def elem_bytes(typ: int) -> int:
-    return 2 if typ == TYPE_F16 else BLOCK_BYTES[typ]
 
 
 def encode(x: np.ndarray, typ: int) -> np.ndarray:

@@ -26,7 +26,9 @@ def test_fixture_small_and_complete(golden):
     want = {name for name, _ in plan_sweep.settings()}
     assert set(golden["digests"]) == want
     groups = {plan_sweep.group_name(D, kt, vt) for D in plan_sweep.HEAD_DIMS for kt, vt in plan_sweep.TYPE_PAIRS}
-    assert all(set(g) == groups for g in golden["digests"].values())
+    every = set(plan_sweep.groups())  # ... and the one-type pairs and the MLA groups
+    assert groups < every
+    assert all(set(g) == every for g in golden["digests"].values())
 
 
 def test_every_option_in_the_sweep():
@@ -38,6 +40,7 @@ def test_every_option_in_the_sweep():
 def test_plans_match_golden(golden):
     G = plan_sweep.groups()
     assert len(next(iter(G.values()))) == golden["cases_per_group"]
+    assert {g: len(c) for g, c in G.items() if len(c) != golden["cases_per_group"]} == golden["cases_of_group"]
     bad = []
     for name, opts in plan_sweep.settings():
         with fattn.options(opts):
