@@ -150,6 +150,10 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
             std::snprintf(merge, sizeof merge, " (in-kernel merge)");
     };
     const char* xcd = pl.a.xcd_group ? " (xcd order)" : "";
+    // The merge launch is one kernel, fattn_chunk_merge_kernel (fattn_tile.h); the
+    // plan names it by its geometry: fattn_merge_kernel = SplitMergeGeom,
+    // fattn_bd_merge_kernel = BdMergeGeom, fattn_mq_merge_kernel = MqMergeGeom,
+    // fattn_mla_merge_kernel = MlaMergeGeom (the plan vocabulary callers and tests read)
     char kern[160];
     switch (pl.kernel) {
         case Kernel::Mla: {  // (f32 partials, plain loads: no other merge form)

@@ -37,7 +37,8 @@
 //  * epilogue: every wave parks its rows' (O, m, l) in LDS, then all 512
 //    threads merge the four key quarters of a row and store whole rows (no
 //    row-per-lane store tail); one chunk: normalised dst rows; several:
-//    (O, m, l) partials merged by fattn_bd_merge_kernel in a second launch.
+//    (O, m, l) partials merged in a second launch (fattn_chunk_merge_kernel
+//    over BdMergeGeom).
 //
 // LDS (D = 128, Q8_0): [0, 32 KiB) K image, [32, 64 KiB) V image, then 2 raw
 // tiles [K rows | V rows] of 34 KiB, then 8 mask slots of 2 KiB; the epilogue
@@ -45,6 +46,7 @@
 #pragma once
 
 #include "fattn_pf.h"
+#include "fattn_tile.h"
 
 namespace fattn {
 
@@ -93,19 +95,8 @@ struct BdCfg {
 
 template <int KT, int D>
 __device__ __forceinline__ void bd_issue(const StepSrc& rs, int n0, uint32_t lds, int wave, int lane) {
-#ifdef FATTN_MQ_NOMEM
-    return;  // diagnostic build only
-#endif
-    using C = BdCfg<KT, D>;
-    for (int j = wave; j < 2 * C::NI; j += kBdWaves) {  // wave-uniform
-        const bool is_v = j >= C::NI;
-        const int i = is_v ? j - C::NI : j;
-        const int byte = i * 1024 + lane * 16;
-        // pieces past the tile's bytes stay idle (the instruction still counts)
-        if (C::kvRaw % 1024 == 0 || byte < C::kvRaw)
-            dma<16, kDecodeNT>(is_v ? rs.v : rs.k, lds + (is_v ? C::kvRaw : 0) + i * 1024,
-                               (uint32_t)n0 * C::rowB + byte);
-    }
+    for (int j = wave; j < 2 * BdCfg<KT, D>::NI; j += kBdWaves)  // wave-uniform
+        raw_tile_dma<BdCfg<KT, D>, kDecodeNT>(rs, n0, lds, j, lane);
 }
 
 // f16 K/V: tile rows -> the pair's f16 images by LDS-DMA, laid out exactly as
@@ -179,30 +170,16 @@ __device__ __forceinline__ void bd_vm_wait(int wave, int nraw, int nmask) {
 // raw tile -> f16 K and V images (the prefill kernel's layouts, 128 keys):
 // wave w dequantises half h = w & 1 of block b = w >> 1 -- K dim slice w and V
 // dim block b, chunks 2h, 2h + 1 -- of keys lane and 64 + lane; h(q * d), one
-// f16 rounding (src/utils.h:10-11).
-//   K image [8 dim slices][128 keys][32 B], 16-B halves swapped on keys with bit 3 set
-//   V image [4 dim blocks][128 keys][64 B], chunk c of key r at c ^ ((r >> 2) & 3)
+// f16 rounding (src/utils.h:10-11); image_store_half's images at 128 keys, 8
+// dim slices / 4 dim blocks, the prefill kernel's swizzles.
 template <int KT, int D>
 __device__ __forceinline__ void bd_dequant(const uint8_t* raw, uint8_t* k16, uint8_t* v16, int wave, int lane) {
-#ifdef FATTN_MQ_NODEQ
-    return;  // diagnostic build only
-#endif
-    using C = BdCfg<KT, D>;
     const int b = wave >> 1, h = wave & 1;
 #pragma unroll
     for (int i = 0; i < 2; i++) {
         const int r = 64 * i + lane;
-        u32x4 ck[2], cv[2];
-        dequant_half<KT, D>(raw, r, b, h, ck);
-        dequant_half<KT, D>(raw + C::kvRaw, r, b, h, cv);
-        uint8_t* kd = k16 + wave * (kBdKeys * 32) + r * 32;
-        const int sk = (r >> 3) & 1;
-        *(u32x4*)(kd + sk * 16) = ck[0];
-        *(u32x4*)(kd + (sk ^ 1) * 16) = ck[1];
-        uint8_t* vd = v16 + b * (kBdKeys * 64) + r * 64;
-        const int sv = (r >> 2) & 3;
-        *(u32x4*)(vd + ((2 * h) ^ sv) * 16) = cv[0];
-        *(u32x4*)(vd + ((2 * h + 1) ^ sv) * 16) = cv[1];
+        image_store_half<KT, kBdKeys, PfSwz>(dequant_half_load<KT, D>(raw, r, b, h),
+                                             dequant_half_load<KT, D>(raw + BdCfg<KT, D>::kvRaw, r, b, h), k16, v16, r, b, h);
     }
 }
 
@@ -218,11 +195,11 @@ __device__ __forceinline__ void bd_dequant(const uint8_t* raw, uint8_t* k16, uin
 // waves behind a barrier.  Row r of the tile goes to wave (r mod 8) of chunk
 // (r / 8) mod n, one merge_row_parts each: the fa_reduce LSE merge
 // (src/flash_row_float.h:415-472) in fp32, fixed order.  This replaces the
-// second launch (fattn_bd_merge_kernel) and its kernel boundary.
+// second launch (fattn_chunk_merge_kernel) and its kernel boundary.
 template <int D>
 __device__ __forceinline__ void bd_tile_merge(const SplitArgs& a, uint8_t* smem, const float* acc, float M, float L,
                                               int pr, int c0, bool row_valid, int tid, int lane, int wave, int qt,
-                                              int iq3, int y, int chunk) {
+                                              int ik2, int iq3, int y, int chunk) {
     constexpr int kDpt = kBdRows * D / (kBdWaves * kWave);
     const int64_t tile = (int64_t)iq3 * gridDim.y + y;
     const int n = a.n_chunks;
@@ -241,7 +218,6 @@ __device__ __forceinline__ void bd_tile_merge(const SplitArgs& a, uint8_t* smem,
     __syncthreads();
     const bool ok = *flag != 0;
     int qt_rows = min(a.QPT, a.NQ - qt * a.QPT) * a.R;
-    int ik2 = a.n_qt != 1 ? y / a.n_qt : y;
     for (int r = chunk * kBdWaves + wave; r < qt_rows; r += kBdWaves * n) {  // wave-uniform
         const int64_t s0 = tile * n * kBdRows + r;  // chunk 0's row r
         const int rq = div_R(a, r);
@@ -328,7 +304,7 @@ __device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, con
     const int q1 = qt * a.QPT + rq;
     const bool pr_ok = rq < a.QPT && q1 < a.NQ;  // (R not a power of two: rows past QPT * R are none)
     if (a.merge_launch == 2) {
-        bd_tile_merge<D>(a, smem, acc, M, L, pr, c0, pr_ok, tid, lane, wave, qt, iq3, y, chunk);
+        bd_tile_merge<D>(a, smem, acc, M, L, pr, c0, pr_ok, tid, lane, wave, qt, ik2, iq3, y, chunk);
         return;
     }
     if (!pr_ok) return;
@@ -354,7 +330,7 @@ __device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, con
         return;
     }
     // several chunks: the partial (O, m, l) of packed row pr for
-    // fattn_bd_merge_kernel, [tile][chunk][64 rows][D] and [..][64 rows][2] (the
+    // the merge launch, [tile][chunk][64 rows][D] and [..][64 rows][2] (the
     // kernel boundary orders these stores before the merge's loads)
     const int64_t slot = (((int64_t)iq3 * gridDim.y + y) * a.n_chunks + chunk) * kBdRows + pr;
     if (a.part_f16) {  // (SplitArgs::part_f16: O / l in f16)
@@ -371,6 +347,182 @@ __device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, con
 #endif
 }
 
+// ---- the row work both batched-decode kernels do alike (fattn_bdp.h's compute
+// waves as every wave here): wave-local, no waits or barriers of its own
+
+// Q: the workgroup's 64 rows (f32, D per row) copied HBM -> LDS at q_lds by
+// 1-KiB LDS-DMA instructions (2 rows each at D = 128), D / 32 per wave,
+// instruction j = wave + 8 i.  16-B chunk g = 64 j + lane of the image is chunk
+// cc = g % CPR of row g / CPR (CPR = D / 4 chunks a row) and holds the row's
+// chunk cc ^ (row & SW), SW = swz_mask(CPR) (31, 15, 7 at D = 128, 64, 96): the
+// operand reads (32 rows at once) then spread over the banks.  Rows past n_q
+// come from past the descriptor: zeros.
+template <int D>
+__device__ __forceinline__ void bd_stage_q(const SplitArgs& a, uint32_t q_lds, int qt, int ik2, int iq3, int wave,
+                                           int lane) {
+    const i32x4 qs = make_srd(a.q + (int64_t)iq3 * a.q_nb3, a.q_span);
+    constexpr int CPR = D / 4;
+    constexpr int SW = swz_mask(CPR);
+    constexpr int kQInst = kBdRows * D * 4 / 1024;  // 32 at D = 128
+    static_assert(kQInst % kBdWaves == 0, "");
+#pragma unroll
+    for (int i = 0; i < kQInst / kBdWaves; i++) {
+        const int j = wave + kBdWaves * i;
+        const int g = kWave * j + lane;
+        const int pr = g / CPR, cc = g % CPR;  // packed row, chunk of this lane's 16 B
+        const int rq = div_R(a, pr);
+        const int q1 = qt * a.QPT + rq, q2 = ik2 * a.rk2 + (pr - rq * a.R);
+        const uint32_t off = rq < a.QPT && q1 < a.NQ ? (uint32_t)q1 * (uint32_t)a.q_nb1 + (uint32_t)q2 * (uint32_t)a.q_nb2 +
+                                             ((cc ^ (pr & SW)) * 16)
+                                       : a.q_span;
+        dma<16>(qs, q_lds + j * 1024, off);
+    }
+}
+
+// Q^T operands (B of S^T = K.Q^T) out of bd_stage_q's image: dims 16 kk + 8 h
+// .. + 8 of packed row p, rounded to f16 like src/utils.h:10
+template <int D>
+__device__ __forceinline__ void bd_q_operands(const uint8_t* qimg, int p, int h, f16x8 (&qop)[D / 16]) {
+    constexpr int SW = swz_mask(D / 4);
+#pragma unroll
+    for (int kk = 0; kk < D / 16; kk++) {
+        const float* qr = (const float*)qimg + p * D;
+        const f32x4 x0 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h) ^ (p & SW)));
+        const f32x4 x1 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h + 1) ^ (p & SW)));
+        f16x8 hq;
+        hq.s0 = (f16)x0.x; hq.s1 = (f16)x0.y; hq.s2 = (f16)x0.z; hq.s3 = (f16)x0.w;
+        hq.s4 = (f16)x1.x; hq.s5 = (f16)x1.y; hq.s6 = (f16)x1.z; hq.s7 = (f16)x1.w;
+        qop[kk] = hq;
+    }
+}
+
+// byte offset of this lane's mask row: query row iq1 in q head iq2's plane; a
+// row the tile does not have points past the descriptor (zeros: not open)
+__device__ __forceinline__ uint32_t bd_mask_row(const SplitArgs& a, bool row_ok, int iq1, int iq2) {
+    return row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 + mask_head_off(a, iq2) : a.m_span_h;
+}
+
+// this lane's mask values of a tile -- keys 8 u + 4 h + 0..3 of the wave's 32 --
+// out of the wave's slot [4 key octets u][32 rows][16 B]; returns nonzero when
+// any of them is not -inf (f16 0xFC00)
+__device__ __forceinline__ uint32_t bd_mask_read(const uint8_t* slot, int c32, int h, u32x2 (&mh)[4]) {
+    const uint8_t* ms = slot + c32 * 16 + h * 8;
+    uint32_t open = 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        mh[u] = *(const u32x2*)(ms + u * 512);
+        open |= (mh[u].x ^ 0xFC00FC00u) | (mh[u].y ^ 0xFC00FC00u);
+    }
+    return open;
+}
+
+// One wave's 32 keys x 32 rows of a tile, out of the f16 image pair at `img`
+// (K image [D / 16 dim slices][KEYS keys][32 B], then V image [D / 32 dim
+// blocks][KEYS keys][64 B]): S^T = K.Q^T, the scores, the deferred-max softmax
+// and O^T += V^T.P^T.  kbase / vbase: this lane's K read and V^T gather offsets
+// in the images (its 32 keys' offset and the image swizzle folded in).
+template <int KEYS, int D, bool HM>
+__device__ __forceinline__ void bd_tile_step(const SplitArgs& a, const uint8_t* img, uint32_t kbase,
+                                             const uint32_t (&vbase)[2], const f16x8 (&qop)[D / 16],
+                                             const u32x2 (&mh)[4], float scale, float slope, float& m_run, f32x2& l2,
+                                             f32x16 (&o)[D / 32]) {
+    constexpr int NK = D / 16, NDB = D / 32;
+    constexpr float kNegInf = -__builtin_inff();
+    constexpr float kDeferLog2 = 8.0f;
+    const float log2e = 1.4426950408889634f;
+    // -- S^T = K.Q^T for this wave's 32 keys: the K operands are read from the
+    // image before the MFMA chain (one LDS wait, not one per k-step)
+    f16x8 ka[NK];
+#pragma unroll
+    for (int kk = 0; kk < NK; kk++) ka[kk] = *(const f16x8*)(img + kk * (KEYS * 32) + kbase);
+    __builtin_amdgcn_sched_barrier(0);
+    f32x16 st;
+#pragma unroll
+    for (int j = 0; j < 16; j++) st[j] = 0.0f;
+#pragma unroll
+    for (int kk = 0; kk < NK; kk++) st = mfma32(ka[kk], qop[kk], st);
+
+    // -- u = scale * s + mask (natural units); element j = key 8 (j/4) + 4 h + j%4
+    float u[16];
+#pragma unroll
+    for (int uu = 0; uu < 4; uu++) {
+        if constexpr (HM) {
+            const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
+            u[4 * uu + 0] = fmaf(st[4 * uu + 0], scale, (float)m01.x);
+            u[4 * uu + 1] = fmaf(st[4 * uu + 1], scale, (float)m01.y);
+            u[4 * uu + 2] = fmaf(st[4 * uu + 2], scale, (float)m23.x);
+            u[4 * uu + 3] = fmaf(st[4 * uu + 3], scale, (float)m23.y);
+        } else {
+#pragma unroll
+            for (int r = 0; r < 4; r++) u[4 * uu + r] = st[4 * uu + r] * scale;
+        }
+    }
+    // max_bias / logit_softcap (wave-uniform, a kernel argument; off: the
+    // fma above stands): the scores again through xf_score
+    if (a.xf.live) {
+#pragma unroll
+        for (int uu = 0; uu < 4; uu++) {
+            float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (HM) {
+                const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
+                mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) u[4 * uu + r] = xf_score(a.xf, scale, st[4 * uu + r], mv[r], slope);
+        }
+    }
+    float tmax = kNegInf;
+#pragma unroll
+    for (int j = 0; j < 16; j++) tmax = fmaxf(tmax, u[j]);
+    tmax = xor32_pair(tmax, true) * log2e;
+    // deferred max (cdna_hip_programming.md T13): the reference max moves
+    // only when the row's block max passes it by more than 2^8 in p (the whole
+    // previous tile's P.V is already accumulated)
+    if (__builtin_amdgcn_ballot_w64(tmax > m_run + kDeferLog2)) {
+        const float m_new = fmaxf(m_run, tmax);
+        const float alpha = (m_new == kNegInf) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
+        l2 *= alpha;
+#pragma unroll
+        for (int db = 0; db < NDB; db++) o[db] *= alpha;
+        m_run = m_new;
+    }
+    const float nm = (m_run == kNegInf) ? 0.0f : -m_run;
+    f16x8 pb[2];
+    {
+        float pv[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) pv[j] = __builtin_amdgcn_exp2f(fmaf(u[j], log2e, nm));
+#pragma unroll
+        for (int j = 0; j < 16; j += 2) l2 += f32x2{pv[j], pv[j + 1]};
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            f16x8 x;
+            x.s0 = (f16)pv[8 * q]; x.s1 = (f16)pv[8 * q + 1]; x.s2 = (f16)pv[8 * q + 2]; x.s3 = (f16)pv[8 * q + 3];
+            x.s4 = (f16)pv[8 * q + 4]; x.s5 = (f16)pv[8 * q + 5]; x.s6 = (f16)pv[8 * q + 6]; x.s7 = (f16)pv[8 * q + 7];
+            pb[q] = x;
+        }
+    }
+
+    // -- O^T += V^T.P^T: k-step q covers the wave's keys 16 q + 8 (i/4) + 4 h + i%4
+    // (i = 0..7); V^T gathered from the image in that order
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+        u32x4 va[NDB];
+#pragma unroll
+        for (int db = 0; db < NDB; db++) {
+            const uint32_t off = db * (KEYS * 64) + q * 1024;
+            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + vbase[0] + off));
+            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + vbase[1] + off));
+            const u32x2 a2 = __builtin_bit_cast(u32x2, lo), b2 = __builtin_bit_cast(u32x2, hi);
+            va[db] = u32x4{a2.x, a2.y, b2.x, b2.y};
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int db = 0; db < NDB; db++) o[db] = mfma32(__builtin_bit_cast(f16x8, va[db]), pb[q], o[db]);
+    }
+}
+
 template <int KT, int D, bool HM>
 __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const SplitArgs a) {
     using C = BdCfg<KT, D>;
@@ -378,7 +530,6 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     constexpr int NK = D / 16;   // 16-dim k-steps of S^T = K.Q^T
     constexpr int NDB = D / 32;  // 32-dim blocks of O^T (= ggml blocks of a row)
     constexpr float kNegInf = -__builtin_inff();
-    constexpr float kDeferLog2 = 8.0f;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -397,15 +548,11 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     // (no return; it is older than every counted DMA wait below, which it
     // therefore only joins)
     if (a.merge_launch == 2 && tid == 0) arrival_begin(a, (int64_t)iq3 * gridDim.y + y);
-    int qt = 0, ik2 = y, ik3 = iq3;
-    if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
-    }
-    if (a.rk3 != 1) ik3 = iq3 / a.rk3;
+    int qt, hs, ik2, ik3;  // (hs = 0: whole head groups)
+    tile_decode<false>(a, y, iq3, qt, hs, ik2, ik3);
     const int p = kBdRowsW * rg + c32;  // packed row of the workgroup tile (its q head only
     const int rq0 = div_R(a, p);        // matters to Q and dst, both addressed per row below)
-    const int iq1 = qt * a.QPT + rq0;
+    const int iq1 = qt * a.QPT + rq0, iq2 = ik2 * a.rk2 + (p - rq0 * a.R);
     const bool row_ok = rq0 < a.QPT && iq1 < a.NQ;  // (R not a power of two: rows past QPT * R are none)
 
     // ---- this workgroup's KV chunk: 128-key tiles (N % 32 == 0; a tile's
@@ -414,51 +561,21 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     const int c_hi = min(a.N, c_lo + a.chunk_len);
     const int ntiles = c_hi > c_lo ? (c_hi - c_lo + kBdKeys - 1) / kBdKeys : 0;
 
-    StepSrc rs;
-    rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
-    rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3);
     const uint32_t lds0 = lds_addr(smem);
     constexpr int kRing = C::nRaw ? C::nRaw : 1;  // (f16: no raw slots)
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % kRing) * C::rawBytes; };
     auto raw_ptr = [&](int s) { return smem + C::rawOff + (s % kRing) * C::rawBytes; };
 
-    // ---- Q: the workgroup's 64 rows (f32, D per row) copied HBM -> LDS into the
-    // V image's place by 1-KiB LDS-DMA instructions (2 rows each, dealt over
-    // the waves); each wave then reads its rows' Q^T operands from there.
-    // Rows past n_q come from past the descriptor: zeros.
-    const i32x4 qs = make_srd(a.q + (int64_t)iq3 * a.q_nb3, a.q_span);
-    constexpr int CPR = D / 4;             // 16-B chunks of an f32 Q row
-    constexpr int SW = swz_mask(CPR);      // 31, 15, 7 at D = 128, 64, 96
-    {
-        constexpr int kQInst = kBdRows * D * 4 / 1024;  // 32 at D = 128
-        static_assert(kQInst % kBdWaves == 0, "");
-#pragma unroll
-        for (int i = 0; i < kQInst / kBdWaves; i++) {
-            const int j = wave + kBdWaves * i;              // instruction: image chunks 64 j ..
-            const int g = kWave * j + lane;
-            const int pr = g / CPR, cc = g % CPR;            // packed row, chunk of this lane's 16 B
-            const int rq = div_R(a, pr);
-            const int q1 = qt * a.QPT + rq, q2 = ik2 * a.rk2 + (pr - rq * a.R);
-            // LDS chunk cc of row pr holds the row's chunk cc ^ (pr & SW): the
-            // operand reads below (32 rows at once) then spread over the banks
-            const uint32_t off = rq < a.QPT && q1 < a.NQ ? (uint32_t)q1 * (uint32_t)a.q_nb1 + (uint32_t)q2 * (uint32_t)a.q_nb2 +
-                                                 ((cc ^ (pr & SW)) * 16)
-                                           : a.q_span;
-            dma<16>(qs, lds0 + C::qOff + j * 1024, off);
-        }
-    }
-    constexpr int kQInstW = kBdRows * D * 4 / 1024 / kBdWaves;  // Q DMA instructions per wave
+    // ---- Q: the workgroup's 64 rows staged in the K image's place (C::qOff);
+    // each wave then reads its rows' Q^T operands from there
+    bd_stage_q<D>(a, lds0 + C::qOff, qt, ik2, iq3, wave, lane);
 
     // ---- mask: the wave's 32 rows x keys 32 kq .. + 32 of a tile into its slot.
     // DMA instruction i, lane l: octet u = 2 i + (l >> 5) of row l & 31 (rows
     // past n_q come from past the descriptor: zeros, and count as not open)
     const uint32_t mslot = lds0 + C::maskOff + wave * C::maskSlot;
-    uint32_t mrow_l;
-    {
-        // (head planes: the row of this packed row's own q head's plane)
-        mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 + mask_head_off(a, ik2 * a.rk2 + (p - rq0 * a.R)) : a.m_span_h;
-    }
+    const uint32_t mrow_l = bd_mask_row(a, row_ok, iq1, iq2);  // (head planes: this packed row's own q head's)
     auto mask_issue = [&](int s) {
         if constexpr (HM) {
             const uint32_t n2 = (uint32_t)(c_lo + s * kBdKeys + 32 * kq) * 2;
@@ -469,7 +586,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     };
 
     // per-lane K read base (prefill kernel's): key 32 kq + c32, half h (swapped on keys with bit 3 set)
-    const uint32_t kbase = c32 * 32 + ((h ^ ((c32 >> 3) & 1)) * 16);
+    const uint32_t kbase = kq * 1024 + c32 * 32 + ((h ^ ((c32 >> 3) & 1)) * 16);
     // per-lane V^T gather bases (prefill kernel's, 128-key image):
     // 16-lane group (h, dh), lane gi: key 32 kq + 16 q + 8 e + 4 h + gi / 4
     const int gi = lane & 15, dh = (lane >> 4) & 1;
@@ -509,9 +626,8 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
 #pragma unroll
         for (int j = 0; j < 16; j++) o[db][j] = 0.0f;
     }
-    const float log2e = 1.4426950408889634f;
     const float scale = a.scale;
-    const float slope = xf_slope(a.xf, ik2 * a.rk2 + (p - rq0 * a.R));  // this lane's row's q head's ALiBi slope (1: off)
+    const float slope = xf_slope(a.xf, iq2);  // this lane's row's q head's ALiBi slope (1: off)
 
     FATTN_STAMP(1);
     // Q landed (mask 0, raw 0 and raw 1 may fly on); every wave's Q pieces in LDS
@@ -520,20 +636,8 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
         bd_vm_wait<KT, D, HM>(wave, n0 + n1, n0);
     }
     __syncthreads();
-    // Q^T operands (B of S^T = K.Q^T): dims 16 kk + 8 h .. + 8 of this lane's
-    // row, rounded to f16 like src/utils.h:10
     f16x8 qop[NK];
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const float* qr = (const float*)(smem + C::qOff) + p * D;
-        const f32x4 x0 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h) ^ (p & SW)));
-        const f32x4 x1 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h + 1) ^ (p & SW)));
-        f16x8 hq;
-        hq.s0 = (f16)x0.x; hq.s1 = (f16)x0.y; hq.s2 = (f16)x0.z; hq.s3 = (f16)x0.w;
-        hq.s4 = (f16)x1.x; hq.s5 = (f16)x1.y; hq.s6 = (f16)x1.z; hq.s7 = (f16)x1.w;
-        qop[kk] = hq;
-    }
-    (void)kQInstW;
+    bd_q_operands<D>(smem + C::qOff, p, h, qop);
     FATTN_STAMP(2);
 
     for (int s = 0; s < ntiles; s++) {
@@ -566,13 +670,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
         if constexpr (HM) {
             // (f16, s = 0: the wait above was vmcnt(0); mask 0 went before tile 0)
             if (s > 0) bd_vm_wait<KT, D, HM>(wave, s + 1 < ntiles ? 1 : 0, 0);
-            open = 0;
-            const uint8_t* ms = smem + C::maskOff + wave * C::maskSlot + c32 * 16 + h * 8;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                mh[u] = *(const u32x2*)(ms + u * 512);
-                open |= (mh[u].x ^ 0xFC00FC00u) | (mh[u].y ^ 0xFC00FC00u);
-            }
+            open = bd_mask_read(smem + C::maskOff + wave * C::maskSlot, c32, h, mh);
             if (s + 1 < ntiles) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot has been read
                 mask_issue(s + 1);
@@ -587,96 +685,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
         // a 32 x 32 block that is -inf for every valid row adds nothing (exact skip)
         if (HM && __builtin_amdgcn_ballot_w64(open != 0 && row_ok) == 0) continue;
 
-        // -- S^T = K.Q^T for this wave's 32 keys: the 8 K operands are read
-        // from the image before the MFMA chain (one LDS wait, not eight)
-        f16x8 ka[NK];
-#pragma unroll
-        for (int kk = 0; kk < NK; kk++) ka[kk] = *(const f16x8*)(smem + pofs + kk * (kBdKeys * 32) + kq * 1024 + kbase);
-        __builtin_amdgcn_sched_barrier(0);
-        f32x16 st;
-#pragma unroll
-        for (int j = 0; j < 16; j++) st[j] = 0.0f;
-#pragma unroll
-        for (int kk = 0; kk < NK; kk++) st = mfma32(ka[kk], qop[kk], st);
-
-        // -- u = scale * s + mask (natural units); element j = key 8 (j/4) + 4 h + j%4
-        float u[16];
-#pragma unroll
-        for (int uu = 0; uu < 4; uu++) {
-            if constexpr (HM) {
-                const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
-                u[4 * uu + 0] = fmaf(st[4 * uu + 0], scale, (float)m01.x);
-                u[4 * uu + 1] = fmaf(st[4 * uu + 1], scale, (float)m01.y);
-                u[4 * uu + 2] = fmaf(st[4 * uu + 2], scale, (float)m23.x);
-                u[4 * uu + 3] = fmaf(st[4 * uu + 3], scale, (float)m23.y);
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; r++) u[4 * uu + r] = st[4 * uu + r] * scale;
-            }
-        }
-        // max_bias / logit_softcap (wave-uniform, a kernel argument; off: the
-        // fma above stands): the scores again through xf_score
-        if (a.xf.live) {
-#pragma unroll
-            for (int uu = 0; uu < 4; uu++) {
-                float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if constexpr (HM) {
-                    const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
-                    mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++) u[4 * uu + r] = xf_score(a.xf, scale, st[4 * uu + r], mv[r], slope);
-            }
-        }
-        float tmax = kNegInf;
-#pragma unroll
-        for (int j = 0; j < 16; j++) tmax = fmaxf(tmax, u[j]);
-        tmax = xor32_pair(tmax, true) * log2e;
-        // deferred max (cdna_hip_programming.md T13): the reference max moves
-        // only when the row's block max passes it by more than 2^8 in p
-        if (__builtin_amdgcn_ballot_w64(tmax > m_run + kDeferLog2)) {
-            const float m_new = fmaxf(m_run, tmax);
-            const float alpha = (m_new == kNegInf) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
-            l2 *= alpha;
-#pragma unroll
-            for (int db = 0; db < NDB; db++) o[db] *= alpha;
-            m_run = m_new;
-        }
-        const float nm = (m_run == kNegInf) ? 0.0f : -m_run;
-        f16x8 pb[2];
-        {
-            float pv[16];
-#pragma unroll
-            for (int j = 0; j < 16; j++) pv[j] = __builtin_amdgcn_exp2f(fmaf(u[j], log2e, nm));
-#pragma unroll
-            for (int j = 0; j < 16; j += 2) l2 += f32x2{pv[j], pv[j + 1]};
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                f16x8 x;
-                x.s0 = (f16)pv[8 * q]; x.s1 = (f16)pv[8 * q + 1]; x.s2 = (f16)pv[8 * q + 2]; x.s3 = (f16)pv[8 * q + 3];
-                x.s4 = (f16)pv[8 * q + 4]; x.s5 = (f16)pv[8 * q + 5]; x.s6 = (f16)pv[8 * q + 6]; x.s7 = (f16)pv[8 * q + 7];
-                pb[q] = x;
-            }
-        }
-
-        // -- O^T += V^T.P^T: k-step q covers keys 32 kq + 16 q + 8 (i/4) + 4 h + i%4
-        // (i = 0..7); V^T gathered from the image in that order
-#pragma unroll
-        for (int q = 0; q < 2; q++) {
-            typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-            u32x4 va[NDB];
-#pragma unroll
-            for (int db = 0; db < NDB; db++) {
-                const uint32_t off = pofs + db * (kBdKeys * 64) + q * 1024;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + vbase[0] + off));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + vbase[1] + off));
-                const u32x2 a2 = __builtin_bit_cast(u32x2, lo), b2 = __builtin_bit_cast(u32x2, hi);
-                va[db] = u32x4{a2.x, a2.y, b2.x, b2.y};
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int db = 0; db < NDB; db++) o[db] = mfma32(__builtin_bit_cast(f16x8, va[db]), pb[q], o[db]);
-        }
+        bd_tile_step<kBdKeys, D, HM>(a, smem + pofs, kbase, vbase, qop, mh, scale, slope, m_run, l2, o);
 #ifdef FATTN_STAMPS
         if (s < 4) {
             float z = 0.0f;
@@ -691,33 +700,11 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const Spli
     bd_finish<D, 4>(a, smem, o, m_run, l2, kq, p, h, true, tid, lane, wave, qt, ik2, iq3, y, chunk);
 }
 
-// Second launch of a split batched-decode plan: one wave per (tile, packed
-// row) merges the row's chunk partials (merge_row_parts: the fa_reduce LSE
-// merge of src/flash_row_float.h:415-472 in fp32, fixed order) and writes the
-// normalised dst row.
-template <int D, int KIT, bool PLAIN = false, bool F16 = false>  // PLAIN, F16: as fattn_merge_kernel
-__global__ __launch_bounds__(256) void fattn_bd_merge_kernel(const SplitArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int p = blockIdx.x * 4 + (threadIdx.x >> 6);  // packed row of the tile
-    const int y = blockIdx.y, iq3 = blockIdx.z;
-    int qt = 0, ik2 = y;
-    if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
-    }
-    if (p >= min(a.QPT, a.NQ - qt * a.QPT) * a.R) return;
-    const int64_t slot0 = ((int64_t)iq3 * gridDim.y + y) * a.n_chunks * kBdRows + p;  // chunk 0's row
-    const int rq = div_R(a, p);
-    const int riq2 = ik2 * a.rk2 + (p - rq * a.R);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
-    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
-    if constexpr (F16) {
-        merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  kBdRows * D, 2 * kBdRows, sink);
-    } else {
-        merge_row_parts<D, KIT, PLAIN ? 0 : kAuxSc1>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                                    kBdRows * D, 2 * kBdRows, sink);
-    }
-}
+// the second-launch merge of a split batched-decode plan
+// (fattn_chunk_merge_kernel, fattn_tile.h): 64-row tiles of whole head groups
+struct BdMergeGeom : MergeGeomBase {
+    static constexpr int rows = kBdRows;
+    static constexpr bool hsub = false;
+};
 
 }  // namespace fattn

@@ -26,7 +26,7 @@
 //  * dequantisation h(q * d) with one f16 rounding (src/utils.h:10-11), images
 //    and operand reads exactly as fattn_bd.h / fattn_pf.h (64-key images);
 //  * epilogue: bd_finish over the two key halves (whole-row stores; partials
-//    merged by fattn_bd_merge_kernel when the KV is split).
+//    merged by the merge launch, fattn_chunk_merge_kernel over BdMergeGeom, when the KV is split).
 //
 // LDS (D = 128, Q8_0): [0, 64 KiB) two image pairs (K [8 dim slices][64 keys]
 // [32 B], V [4 dim blocks][64 keys][64 B]), then nRaw = 4 raw tiles [K rows |
@@ -105,18 +105,10 @@ constexpr bool kBdpNT = false;
 // this wave's raw instructions of the tile at key n0 (BdpCfg::owner)
 template <int KT, int D>
 __device__ __forceinline__ void bdp_issue(const StepSrc& rs, int n0, uint32_t lds, int wave, int lane) {
-#ifdef FATTN_MQ_NOMEM
-    return;  // diagnostic build only
-#endif
     using C = BdpCfg<KT, D>;
 #pragma unroll
     for (int j = 0; j < C::T; j++) {
-        if (C::owner(j) != wave) continue;  // wave-uniform
-        const bool is_v = j >= C::NI;
-        const int i = is_v ? j - C::NI : j;
-        const int byte = i * 1024 + lane * 16;
-        if (C::kvRaw % 1024 == 0 || byte < C::kvRaw)  // pieces past the tile's bytes idle (the instruction counts)
-            dma<16, kBdpNT>(is_v ? rs.v : rs.k, lds + (is_v ? C::kvRaw : 0) + i * 1024, (uint32_t)n0 * C::rowB + byte);
+        if (C::owner(j) == wave) raw_tile_dma<C, kBdpNT>(rs, n0, lds, j, lane);  // wave-uniform
     }
 }
 
@@ -143,6 +135,10 @@ __host__ __device__ constexpr int bdp_vswz(int key) { return (key >> 2) & 3; }
 __host__ __device__ constexpr int bdp_kswz(int key) { return ((key >> 2) ^ (key >> 3)) & 1; }
 __host__ __device__ constexpr int bdp_vswz(int key) { return (key >> 1) & 3; }
 #endif
+struct BdpSwz {
+    static __host__ __device__ constexpr int k(int key) { return bdp_kswz(key); }
+    static __host__ __device__ constexpr int v(int key) { return bdp_vswz(key); }
+};
 struct BdpRaw {
     HalfRaw k[kBdpHpw], v[kBdpHpw];
 };
@@ -162,24 +158,11 @@ __device__ __forceinline__ BdpRaw bdp_dequant_load(const uint8_t* raw, int bw, i
 }
 template <int KT, int D>
 __device__ __forceinline__ void bdp_dequant_store(const BdpRaw& r, uint8_t* k16, uint8_t* v16, int bw, int lane) {
-#ifdef FATTN_MQ_NODEQ
-    return;  // diagnostic build only
-#endif
-    const int sk = bdp_kswz(lane), sv = bdp_vswz(lane);
 #pragma unroll
     for (int i = 0; i < (D / 16 + 3) / 4; i++) {
         const int hb = bw + 4 * i;
         if (hb >= D / 16) break;  // wave-uniform
-        const int b = hb >> 1, h = hb & 1;
-        u32x4 ck[2], cv[2];
-        dequant_half_cvt<KT>(r.k[i], h, ck);
-        dequant_half_cvt<KT>(r.v[i], h, cv);
-        uint8_t* kd = k16 + hb * (kBdpKeys * 32) + lane * 32;
-        *(u32x4*)(kd + sk * 16) = ck[0];
-        *(u32x4*)(kd + (sk ^ 1) * 16) = ck[1];
-        uint8_t* vd = v16 + b * (kBdpKeys * 64) + lane * 64;
-        *(u32x4*)(vd + ((2 * h) ^ sv) * 16) = cv[0];
-        *(u32x4*)(vd + ((2 * h + 1) ^ sv) * 16) = cv[1];
+        image_store_half<KT, kBdpKeys, BdpSwz>(r.k[i], r.v[i], k16, v16, lane, hb >> 1, hb & 1);
     }
 }
 template <int KT, int D>
@@ -228,7 +211,6 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     constexpr int NDB = D / 32;  // 32-dim blocks of O^T
     constexpr int NM = HM ? C::NM : 0;
     constexpr float kNegInf = -__builtin_inff();
-    constexpr float kDeferLog2 = 8.0f;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -243,60 +225,29 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     int chunk, y, iq3;
     tile_coords(a, chunk, y, iq3);
     if (a.merge_launch == 2 && tid == 0) arrival_begin(a, (int64_t)iq3 * gridDim.y + y);
-    int qt = 0, ik2 = y, ik3 = iq3;
-    if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
-    }
-    if (a.rk3 != 1) ik3 = iq3 / a.rk3;
+    int qt, hs, ik2, ik3;  // (hs = 0: whole head groups)
+    tile_decode<false>(a, y, iq3, qt, hs, ik2, ik3);
     const int p = kBdRowsW * rg + c32;  // compute waves: this lane's packed row
     const int rq0 = div_R(a, p);
-    const int iq1 = qt * a.QPT + rq0;
+    const int iq1 = qt * a.QPT + rq0, iq2 = ik2 * a.rk2 + (p - rq0 * a.R);
     const bool row_ok = rq0 < a.QPT && iq1 < a.NQ;  // (R not a power of two: rows past QPT * R are none)
 
     const int c_lo = chunk * a.chunk_len;
     const int c_hi = min(a.N, c_lo + a.chunk_len);
     const int ntiles = c_hi > c_lo ? (c_hi - c_lo + kBdpKeys - 1) / kBdpKeys : 0;
 
-    StepSrc rs;
-    rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
-    rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3);
     const uint32_t lds0 = lds_addr(smem);
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % C::nRaw) * C::rawBytes; };
     auto raw_ptr = [&](int s) { return smem + C::rawOff + (s % C::nRaw) * C::rawBytes; };
 
-    // ---- Q: 64 f32 rows -> LDS (pair 1's place) by D / 4 1-KiB DMA
-    // instructions, D / 32 per wave; 16-B chunk g = 64 j + lane of the image is
-    // chunk c = g % CPR of row g / CPR (CPR = D / 4 chunks a row), holding the
-    // row's chunk c ^ (row & SW) (fattn_bd.h's layout; SW = swz_mask(CPR): 31,
-    // 15 and 7 at D = 128, 64, 96)
-    constexpr int CPR = D / 4;
-    constexpr int SW = swz_mask(CPR);
-    {
-        const i32x4 qs = make_srd(a.q + (int64_t)iq3 * a.q_nb3, a.q_span);
-        constexpr int kQInst = kBdRows * D * 4 / 1024;
-        static_assert(kQInst % kBdWaves == 0, "");
-#pragma unroll
-        for (int i = 0; i < kQInst / kBdWaves; i++) {
-            const int j = wave + kBdWaves * i;
-            const int g = kWave * j + lane;
-            const int pr = g / CPR, cc = g % CPR;
-            const int rq = div_R(a, pr);
-            const int q1 = qt * a.QPT + rq, q2 = ik2 * a.rk2 + (pr - rq * a.R);
-            const uint32_t off = rq < a.QPT && q1 < a.NQ ? (uint32_t)q1 * (uint32_t)a.q_nb1 + (uint32_t)q2 * (uint32_t)a.q_nb2 +
-                                                 ((cc ^ (pr & SW)) * 16)
-                                           : a.q_span;
-            dma<16>(qs, lds0 + C::qOff + j * 1024, off);
-        }
-    }
+    // ---- Q: 64 f32 rows -> LDS (pair 1's place)
+    bd_stage_q<D>(a, lds0 + C::qOff, qt, ik2, iq3, wave, lane);
 
     // ---- compute waves' mask blocks: rows 32 rg + c32, keys 32 kh .. + 32 of a
     // tile, slot (wave, s & 1); DMA instruction i, lane l: octet 2 i + (l >> 5)
     const uint32_t mslot0 = lds0 + C::maskOff + (wave & 3) * 2 * C::maskSlot;
-    uint32_t mrow_l;
-    // (head planes: the row of this packed row's own q head's plane)
-    mrow_l = row_ok ? (uint32_t)iq1 * (uint32_t)a.m_nb1 + mask_head_off(a, ik2 * a.rk2 + (p - rq0 * a.R)) : a.m_span_h;
+    const uint32_t mrow_l = bd_mask_row(a, row_ok, iq1, iq2);  // (head planes: this packed row's own q head's)
     auto mask_issue = [&](int s) {
         if constexpr (HM) {
             const uint32_t n2 = (uint32_t)(c_lo + s * kBdpKeys + 32 * kh) * 2;
@@ -323,16 +274,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
     __syncthreads();  // Q and raw 0 complete in LDS
     f16x8 qop[NK];
     if (compute) {
-#pragma unroll
-        for (int kk = 0; kk < NK; kk++) {
-            const float* qr = (const float*)(smem + C::qOff) + p * D;
-            const f32x4 x0 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h) ^ (p & SW)));
-            const f32x4 x1 = *(const f32x4*)(qr + 4 * ((4 * kk + 2 * h + 1) ^ (p & SW)));
-            f16x8 hq;
-            hq.s0 = (f16)x0.x; hq.s1 = (f16)x0.y; hq.s2 = (f16)x0.z; hq.s3 = (f16)x0.w;
-            hq.s4 = (f16)x1.x; hq.s5 = (f16)x1.y; hq.s6 = (f16)x1.z; hq.s7 = (f16)x1.w;
-            qop[kk] = hq;
-        }
+        bd_q_operands<D>(smem + C::qOff, p, h, qop);
         // this wave's pieces of raw 1 landed (the build waves dequantise it
         // after the loop's first barrier)
         if (ntiles > 1) bdp_compute_wait<KT, D, NM>(npro - 2, 0);
@@ -355,9 +297,8 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
 #pragma unroll
         for (int j = 0; j < 16; j++) o[db][j] = 0.0f;
     }
-    const float log2e = 1.4426950408889634f;
     const float scale = a.scale;
-    const float slope = xf_slope(a.xf, ik2 * a.rk2 + (p - rq0 * a.R));  // this lane's row's q head's ALiBi slope (1: off)
+    const float slope = xf_slope(a.xf, iq2);  // this lane's row's q head's ALiBi slope (1: off)
     // per-lane K read base (key 32 kh + c32, half h; halves swapped per
     // bdp_kswz) and V^T gather bases (fattn_bd.h's gather, 64-key images,
     // chunks swizzled per bdp_vswz: keys 32 kh + 16 q + row, the first two
@@ -417,13 +358,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
         u32x2 mh[4];
         uint32_t open = 1;  // any key not at -inf (f16 0xFC00)
         if constexpr (HM) {
-            open = 0;
-            const uint8_t* ms = smem + C::maskOff + (wave & 3) * 2 * C::maskSlot + (s & 1) * C::maskSlot + c32 * 16 + h * 8;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                mh[u] = *(const u32x2*)(ms + u * 512);
-                open |= (mh[u].x ^ 0xFC00FC00u) | (mh[u].y ^ 0xFC00FC00u);
-            }
+            open = bd_mask_read(smem + C::maskOff + (wave & 3) * 2 * C::maskSlot + (s & 1) * C::maskSlot, c32, h, mh);
 #ifndef FATTN_BDP_MASK_LATE
             if (s + 2 < ntiles) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot has been read
@@ -434,94 +369,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const Spl
         // this wave's 32 keys past the chunk, or -inf for every valid row: nothing to add (exact)
         const bool live = c_lo + s * kBdpKeys + 32 * kh < c_hi &&
                           (!HM || __builtin_amdgcn_ballot_w64(open != 0 && row_ok) != 0);
-        if (live) {
-            f16x8 ka[NK];
-#pragma unroll
-            for (int kk = 0; kk < NK; kk++) ka[kk] = *(const f16x8*)(smem + pofs + kk * (kBdpKeys * 32) + kbase);
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 st;
-#pragma unroll
-            for (int j = 0; j < 16; j++) st[j] = 0.0f;
-#pragma unroll
-            for (int kk = 0; kk < NK; kk++) st = mfma32(ka[kk], qop[kk], st);
-
-            // u = scale * s + mask (natural units); element j = key 8 (j/4) + 4 h + j%4
-            float u[16];
-#pragma unroll
-            for (int uu = 0; uu < 4; uu++) {
-                if constexpr (HM) {
-                    const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
-                    u[4 * uu + 0] = fmaf(st[4 * uu + 0], scale, (float)m01.x);
-                    u[4 * uu + 1] = fmaf(st[4 * uu + 1], scale, (float)m01.y);
-                    u[4 * uu + 2] = fmaf(st[4 * uu + 2], scale, (float)m23.x);
-                    u[4 * uu + 3] = fmaf(st[4 * uu + 3], scale, (float)m23.y);
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) u[4 * uu + r] = st[4 * uu + r] * scale;
-                }
-            }
-            // max_bias / logit_softcap (wave-uniform, a kernel argument; off:
-            // the fma above stands): the scores again through xf_score
-            if (a.xf.live) {
-#pragma unroll
-                for (int uu = 0; uu < 4; uu++) {
-                    float mv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                    if constexpr (HM) {
-                        const f16x2 m01 = as_h2(mh[uu].x), m23 = as_h2(mh[uu].y);
-                        mv[0] = (float)m01.x; mv[1] = (float)m01.y; mv[2] = (float)m23.x; mv[3] = (float)m23.y;
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; r++) u[4 * uu + r] = xf_score(a.xf, scale, st[4 * uu + r], mv[r], slope);
-                }
-            }
-            float tmax = kNegInf;
-#pragma unroll
-            for (int j = 0; j < 16; j++) tmax = fmaxf(tmax, u[j]);
-            tmax = xor32_pair(tmax, true) * log2e;
-            // deferred max (cdna_hip_programming.md T13), the whole previous
-            // tile's P.V already accumulated
-            if (__builtin_amdgcn_ballot_w64(tmax > m_run + kDeferLog2)) {
-                const float m_new = fmaxf(m_run, tmax);
-                const float alpha = (m_new == kNegInf) ? 1.0f : __builtin_amdgcn_exp2f(m_run - m_new);
-                l2 *= alpha;
-#pragma unroll
-                for (int db = 0; db < NDB; db++) o[db] *= alpha;
-                m_run = m_new;
-            }
-            const float nm = (m_run == kNegInf) ? 0.0f : -m_run;
-            f16x8 pb[2];
-            {
-                float pv[16];
-#pragma unroll
-                for (int j = 0; j < 16; j++) pv[j] = __builtin_amdgcn_exp2f(fmaf(u[j], log2e, nm));
-#pragma unroll
-                for (int j = 0; j < 16; j += 2) l2 += f32x2{pv[j], pv[j + 1]};
-#pragma unroll
-                for (int q = 0; q < 2; q++) {
-                    f16x8 x;
-                    x.s0 = (f16)pv[8 * q]; x.s1 = (f16)pv[8 * q + 1]; x.s2 = (f16)pv[8 * q + 2]; x.s3 = (f16)pv[8 * q + 3];
-                    x.s4 = (f16)pv[8 * q + 4]; x.s5 = (f16)pv[8 * q + 5]; x.s6 = (f16)pv[8 * q + 6]; x.s7 = (f16)pv[8 * q + 7];
-                    pb[q] = x;
-                }
-            }
-            // O^T += V^T.P^T: k-step q covers keys 32 kh + 16 q + 8 (i/4) + 4 h + i%4
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-                u32x4 va[NDB];
-#pragma unroll
-                for (int db = 0; db < NDB; db++) {
-                    const uint32_t off = pofs + db * (kBdpKeys * 64) + q * 1024;
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + vbase[0] + off));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(smem + vbase[1] + off));
-                    const u32x2 a2 = __builtin_bit_cast(u32x2, lo), b2 = __builtin_bit_cast(u32x2, hi);
-                    va[db] = u32x4{a2.x, a2.y, b2.x, b2.y};
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int db = 0; db < NDB; db++) o[db] = mfma32(__builtin_bit_cast(f16x8, va[db]), pb[q], o[db]);
-            }
-        }
+        if (live) bd_tile_step<kBdpKeys, D, HM>(a, smem + pofs, kbase, vbase, qop, mh, scale, slope, m_run, l2, o);
 #ifdef FATTN_BDP_MASK_LATE
         // diagnostic build only (A/B): mask s + 2 issued after tile s's compute
         // (config 5: 24.6-25.2 vs 24.7-25.4 us, neutral, profiles/r04_j)

@@ -139,46 +139,35 @@ int launch_kernel(const void* kern, const Plan& pl, hipStream_t st, const Events
     return FATTN_OK;
 }
 
-// The second-launch merge kernels of the three split-KV kernels, as template
-// arguments of launch_chunk_merge.  The multi-query merge has no plain-load form.
-struct SplitMerge {
-    static constexpr bool has_plain = true;
-    template <int D, int KIT, bool PLAIN, bool F16>
-    static constexpr auto kernel() { return fattn_merge_kernel<D, KIT, PLAIN, F16>; }
-};
-struct BdMerge {
-    static constexpr bool has_plain = true;
-    template <int D, int KIT, bool PLAIN, bool F16>
-    static constexpr auto kernel() { return fattn_bd_merge_kernel<D, KIT, PLAIN, F16>; }
-};
-template <int SUBS>  // 16-row subtiles per tile
-struct MqMerge {
-    static constexpr bool has_plain = false;
-    template <int D, int KIT, bool PLAIN, bool F16>
-    static constexpr auto kernel() { return fattn_mq_merge_kernel<D, KIT, SUBS, F16>; }
-};
-
-// Merge the chunk partials in a second launch, one wave per packed row, with
-// as few load slots per lane (KIT) as the chunk count allows (the slots past
-// it still cost issue cycles); f16 partials (16-B loads of 8 dims, merge_ppr_h
-// parts per lane row; not at D = 64), else sc1 or plain loads of f32 ones.
-template <typename Family, int D>
+// Merge the chunk partials in a second launch (fattn_chunk_merge_kernel over the
+// kernel family's Geom), one wave per packed row, with as few load slots per
+// lane (KIT) as the chunk count allows (the slots past it still cost issue
+// cycles); f16 partials (16-B loads of 8 dims, merge_ppr_h parts per lane row;
+// not at D = 64), else sc1 or plain loads of f32 ones -- of these forms, the
+// ones the Geom has.
+template <typename Geom, int D>
 void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
     auto pick = [&](int parts_per_row, auto plain, auto f16) {
         constexpr bool PLAIN = decltype(plain)::value, F16 = decltype(f16)::value;
         const int need = (pl.a.n_chunks + parts_per_row - 1) / parts_per_row;
-        if (need <= 2) hipLaunchKernelGGL((Family::template kernel<D, 2, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
-        else if (need <= 4) hipLaunchKernelGGL((Family::template kernel<D, 4, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
-        else if (need <= 8) hipLaunchKernelGGL((Family::template kernel<D, 8, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
-        else hipLaunchKernelGGL((Family::template kernel<D, 16, PLAIN, F16>()), grid, dim3(256), 0, st, pl.a);
+        auto go = [&](auto kit) {
+            hipLaunchKernelGGL((fattn_chunk_merge_kernel<Geom, D, decltype(kit)::value, PLAIN, F16>), grid, dim3(256), 0, st, pl.a);
+        };
+        if constexpr (Geom::min_kit <= 2) {
+            if (need <= 2) return go(std::integral_constant<int, 2>());
+        }
+        if (need <= 4) go(std::integral_constant<int, 4>());
+        else if (need <= 8) go(std::integral_constant<int, 8>());
+        else go(std::integral_constant<int, 16>());
     };
-    if constexpr (D != 64) {
+    constexpr int ppr = merge_ppr<merge_span(D)>();
+    if constexpr (Geom::f16 && D != 64) {
         if (pl.a.part_f16) return pick(merge_ppr_h<D>(), std::false_type(), std::true_type());
     }
-    if constexpr (Family::has_plain) {
-        if (pl.merge_plain) return pick(merge_ppr<D>(), std::true_type(), std::false_type());
+    if constexpr (Geom::plain) {
+        if (!Geom::sc1 || pl.merge_plain) return pick(ppr, std::true_type(), std::false_type());
     }
-    pick(merge_ppr<D>(), std::false_type(), std::false_type());
+    if constexpr (Geom::sc1) pick(ppr, std::false_type(), std::false_type());
 }
 
 template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
@@ -210,7 +199,7 @@ int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
                 // query row: one workgroup per tile, not four)
                 const int qrows = pl.a.QPT < pl.a.NQ ? pl.a.QPT : pl.a.NQ;
                 const int rows = qrows * pl.a.R < kRows ? qrows * pl.a.R : kRows;
-                launch_chunk_merge<SplitMerge, D>(dim3((unsigned)((rows + 3) / 4), pl.grid.y, pl.grid.z), pl, st);
+                launch_chunk_merge<SplitMergeGeom, D>(dim3((unsigned)((rows + 3) / 4), pl.grid.y, pl.grid.z), pl, st);
             }
         }
     });
@@ -265,7 +254,7 @@ int launch_mq_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             // the chunk partials of every 16-row subtile (4 per 64-row tile,
             // 16 per 256-row tile) merge in a second launch
             constexpr int SUBS = NW == 8 ? 16 : 4;
-            launch_chunk_merge<MqMerge<SUBS>, D>(dim3(kRows / 4, pl.grid.y * SUBS, pl.grid.z), pl, st);
+            launch_chunk_merge<MqMergeGeom<SUBS>, D>(dim3(kRows / 4, pl.grid.y * SUBS, pl.grid.z), pl, st);
         }
     });
 }
@@ -348,7 +337,7 @@ int launch_bd_hm(const Plan& pl, hipStream_t st, const Events& ev) {
     if (kern == nullptr) return FATTN_ERR_UNSUPPORTED_TYPE;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(kBdWaves * kWave), pl.lds, st, pl.a);
-        if (pl.a.merge_launch == 1) launch_chunk_merge<BdMerge, D>(dim3(kBdRows / 4, pl.grid.y, pl.grid.z), pl, st);
+        if (pl.a.merge_launch == 1) launch_chunk_merge<BdMergeGeom, D>(dim3(kBdRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
 }
 
@@ -450,7 +439,6 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
 
 // the MLA kernels (instantiated in fattn_launch_mla.hip)
 int launch_mla(const Plan& pl, hipStream_t st, const Events& ev);
-void launch_mla_merge(const Plan& pl, hipStream_t st);
 // ... over a Q8_0 / Q4_0 cache (instantiated in fattn_launch_mla_q.hip)
 int launch_mla_q(const Plan& pl, hipStream_t st, const Events& ev);
 

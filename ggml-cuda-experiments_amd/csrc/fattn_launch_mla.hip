@@ -16,19 +16,11 @@ int launch_mla_form(const Plan& pl, hipStream_t st, const Events& ev) {
     ma.raw16 = 0;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(kMlaWaves * kWave), pl.lds, st, ma);
-        if (pl.a.merge_launch == 1) launch_mla_merge(pl, st);
+        if (pl.a.merge_launch == 1) launch_chunk_merge<MlaMergeGeom, kMlaDV>(dim3(kMlaRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
 }
 
 }  // namespace
-
-// one wave per packed row; as few load slots per lane as the chunks need
-void launch_mla_merge(const Plan& pl, hipStream_t st) {
-    const dim3 grid(kMlaRows / 4, pl.grid.y, pl.grid.z);
-    if (pl.a.n_chunks <= 4) hipLaunchKernelGGL(fattn_mla_merge_kernel<4>, grid, dim3(256), 0, st, pl.a);
-    else if (pl.a.n_chunks <= 8) hipLaunchKernelGGL(fattn_mla_merge_kernel<8>, grid, dim3(256), 0, st, pl.a);
-    else hipLaunchKernelGGL(fattn_mla_merge_kernel<16>, grid, dim3(256), 0, st, pl.a);
-}
 
 int launch_mla(const Plan& pl, hipStream_t st, const Events& ev) {
     if (pl.kt != FATTN_TYPE_F16) return launch_mla_q(pl, st, ev);

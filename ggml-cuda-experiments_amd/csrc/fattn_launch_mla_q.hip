@@ -18,7 +18,7 @@ int launch_mla_q_form(const Plan& pl, hipStream_t st, const Events& ev) {
     ma.raw16 = SOLO && pl.mla_raw16;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
         hipLaunchKernelGGL(kern, pl.grid, dim3(kMlaWaves * kWave), pl.lds, st, ma);
-        if (pl.a.merge_launch == 1) launch_mla_merge(pl, st);
+        if (pl.a.merge_launch == 1) launch_chunk_merge<MlaMergeGeom, kMlaDV>(dim3(kMlaRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
 }
 

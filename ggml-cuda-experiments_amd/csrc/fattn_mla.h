@@ -41,7 +41,8 @@
 // (H = 16 decode) wave 0 computes and waves 1 - 3 load and convert (SOLO).
 #pragma once
 
-#include "fattn_split.h"
+#include "fattn_split.h"  // v_operand_f16
+#include "fattn_tile.h"
 
 namespace fattn {
 
@@ -226,16 +227,6 @@ __device__ __forceinline__ void mla_wait_tiles(int pending) {
     else wait_vmcnt_c<N>();
 }
 
-// the tile decode shared by the kernel and its merge: y -> (query tile, head subgroup, kv head)
-__device__ __forceinline__ void mla_tile_of(const SplitArgs& a, int y, int& qt, int& hs, int& ik2) {
-    qt = 0, hs = 0, ik2 = y;
-    if (a.n_qt != 1 || a.n_hsub != 1) {
-        qt = y % a.n_qt;
-        hs = (y / a.n_qt) % a.n_hsub;
-        ik2 = y / (a.n_qt * a.n_hsub);
-    }
-}
-
 // SOLO (quantised cache only; the launcher's choice): no tile of the launch has
 // more than one wave's 16 rows (H = 16 decode), so wave 0 computes and waves
 // 1 - 3 load and convert -- the conversion leaves the computing wave's chain.
@@ -277,9 +268,8 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
         iq3 = pr / yh;
         y = yy % a.n_qt + a.n_qt * (((lin >> 3) & 1) + 2 * (yy / a.n_qt));
     }
-    int qt, hs, ik2;
-    mla_tile_of(a, y, qt, hs, ik2);
-    const int ik3 = a.rk3 == 1 ? iq3 : iq3 / a.rk3;
+    int qt, hs, ik2, ik3;
+    tile_decode<true>(a, y, iq3, qt, hs, ik2, ik3);
     const int nvalid = tile_rows(a, qt, hs);       // the tile's rows: a prefix of its 64
     const bool active = wave * kRows < nvalid;     // (wave-uniform) this wave has rows to compute
 
@@ -294,10 +284,7 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     const int c_hi = min(a.N, c_lo + a.chunk_len);
     const int ntiles = (c_hi - c_lo + kStep - 1) / kStep;
 
-    StepSrc rs;
-    rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
-    rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, VOWN ? a.v_span : 0);
-    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3, VOWN ? a.v_span : 0);
 
     // ---- Q^T operands (B of S^T = K.Q^T), rounded to f16 like src/utils.h:10;
     // k-step b of lane group g holds the dims of chunk mla_kchunk(b, g)
@@ -637,28 +624,16 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     if (g == 0) *(f32x2*)(a.ws_ml + 2 * slot) = f32x2{m_run, l_tot};
 }
 
-// Second launch of a split plan: one wave per packed row merges the row's chunk
-// partials (merge_row_parts: the fa_reduce LSE merge in fp32, fixed order) and
-// writes the normalised dst row -- 512 columns as two halves of 256, the widest
-// row one wave of merge_row_parts covers; each half reduces the (m, l) pairs
-// anew.  Plain loads: the kernel boundary made the partials visible.
-template <int KIT>
-__global__ __launch_bounds__(256) void fattn_mla_merge_kernel(const SplitArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int tm = blockIdx.x * 4 + (threadIdx.x >> 6);  // packed row of the tile
-    const int y = blockIdx.y, iq3 = blockIdx.z;
-    int qt, hs, ik2;
-    mla_tile_of(a, y, qt, hs, ik2);
-    if (tm >= tile_rows(a, qt, hs)) return;
-    const int64_t slot0 = ((int64_t)iq3 * gridDim.y + y) * a.n_chunks * kMlaRows + tm;  // chunk 0's row tm
-    const int rq = div_R(a, tm);
-    const int riq2 = ik2 * a.rk2 + hs * a.R + (tm - rq * a.R);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * kMlaDV;
-    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };
-#pragma unroll
-    for (int half = 0; half < 2; half++)
-        merge_row_parts<256, KIT, 0>(a.ws_o + slot0 * kMlaDV + 256 * half, a.ws_ml + 2 * slot0, a.n_chunks,
-                                     out + 256 * half, lane, kMlaRows * kMlaDV, 2 * kMlaRows, sink);
-}
+// the second-launch merge of a split plan (fattn_chunk_merge_kernel,
+// fattn_tile.h, at D = kMlaDV: two 256-column parts per row): 64-row tiles with
+// head subgroups, f32 partials read with plain loads (the kernel boundary made
+// them visible), at least 4 load slots per lane
+struct MlaMergeGeom : MergeGeomBase {
+    static constexpr int rows = kMlaRows;
+    static constexpr bool hsub = true;
+    static constexpr bool sc1 = false;
+    static constexpr bool f16 = false;
+    static constexpr int min_kit = 4;
+};
 
 }  // namespace fattn

@@ -34,7 +34,8 @@
 // kernel's last-arriver merge, one 16-row subtile per column group.
 #pragma once
 
-#include "fattn_split.h"
+#include "fattn_split.h"  // the K / V operands, combine_tile
+#include "fattn_tile.h"
 
 namespace fattn {
 
@@ -230,12 +231,8 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
     const int chunk = blockIdx.x;
     const int y = blockIdx.y;
     const int iq3 = blockIdx.z;
-    int qt = 0, ik2 = y, ik3 = iq3;
-    if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
-    }
-    if (a.rk3 != 1) ik3 = iq3 / a.rk3;
+    int qt, hs, ik2, ik3;  // (hs = 0: whole head groups)
+    tile_decode<false>(a, y, iq3, qt, hs, ik2, ik3);
 
     // this lane's columns: packed row p = RPW * wave + 16 * gi + i16 -> (query row, q head)
     int mq[NG], iq1[NG], iq2[NG];
@@ -254,10 +251,7 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
     const int c_hi = min(a.N, c_lo + a.chunk_len);
     const int ntiles = c_hi > c_lo ? (c_hi - c_lo) / kStep : 0;
 
-    StepSrc rs;
-    rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
-    rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3);
     const int mrow0 = qt * a.QPT;
     auto raw = [&](int s) { return smem + (s % C::nRaw) * C::rawBytes; };
     auto k16_of = [&](int s) { return smem + C::imgOff + (s & 1) * 2 * C::img; };
@@ -454,7 +448,7 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
 
     // ---- several chunks: publish each column group's 16 rows as subtile
     // (tile, 4*NG) in the decode kernel's partial layout.  merge_launch: the
-    // subtiles' chunk partials merge in fattn_mq_merge_kernel (the kernel
+    // subtiles' chunk partials merge in the merge launch (the kernel
     // boundary orders the stores before its loads); otherwise the last
     // workgroup of the tile merges them (same hand-off as fattn_split_kernel)
     constexpr int SUBS = NW * NG;
@@ -513,37 +507,16 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
     }
 }
 
-// Second launch of a split multi-query plan (SplitArgs::merge_launch): one
-// wave per packed row of a 16-row subtile merges the row's chunk partials
-// (merge_row_parts: the fa_reduce LSE merge of src/flash_row_float.h:415-472
-// in fp32, fixed order) and writes the normalised dst row.  grid.y runs over
-// (tile, subtile) pairs, y' = tile_y * SUBS + sub, so the partial slots are
-// the multi-query kernel's ((tile * SUBS + sub) * chunks + chunk) * 16 + row.
-template <int D, int KIT, int SUBS, bool F16 = false>  // F16: the f16 partials of SplitArgs::part_f16
-__global__ __launch_bounds__(256) void fattn_mq_merge_kernel(const SplitArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int tm = blockIdx.x * 4 + (threadIdx.x >> 6);  // row of the subtile
-    const int ys = blockIdx.y, iq3 = blockIdx.z;
-    const int y = ys / SUBS, sub = ys % SUBS;
-    int qt = 0, ik2 = y;  // the multi-query kernel's tile decode
-    if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
-    }
-    const int p = kRows * sub + tm;  // packed row of the tile
-    if (p >= min(a.QPT, a.NQ - qt * a.QPT) * a.R) return;
-    const int64_t slot0 = ((int64_t)iq3 * gridDim.y + ys) * a.n_chunks * kRows + tm;  // chunk 0's row
-    const int rq = div_R(a, p);
-    const int riq2 = ik2 * a.rk2 + (p - rq * a.R);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
-    auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
-    if constexpr (F16) {
-        merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  kRows * D, 2 * kRows, sink);
-    } else {
-        merge_row_parts<D, KIT>(a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane, kRows * D, 2 * kRows,
-                                sink);
-    }
-}
+// the second-launch merge of a split multi-query plan (fattn_chunk_merge_kernel,
+// fattn_tile.h): tiles of whole head groups whose partials sit per 16-row
+// subtile, slot ((tile * SUBS + sub) * chunks + chunk) * 16 + row, so grid.y
+// runs over (tile, subtile) pairs.  No plain-load form.
+template <int SUBS>  // 16-row subtiles per tile
+struct MqMergeGeom : MergeGeomBase {
+    static constexpr int rows = kRows;
+    static constexpr bool hsub = false;
+    static constexpr int subs = SUBS;
+    static constexpr bool plain = false;
+};
 
 }  // namespace fattn

@@ -40,6 +40,7 @@
 
 #include "fattn_mq.h"
 #include "fattn_quant.h"
+#include "fattn_tile.h"
 
 namespace fattn {
 
@@ -85,19 +86,56 @@ struct PfCfg {
     static_assert(ldsBytes <= 163840, "");
 };
 
-template <int KT, int D>
-__device__ __forceinline__ void pf_issue(const StepSrc& rs, int n0, uint32_t lds, int wave, int lane) {
+// ---- raw tiles and f16 images, shared with the batched-decode kernels
+// (fattn_bd.h, fattn_bdp.h).  C: the kernel's Cfg (rowB, kvRaw, NI).
+
+// Instruction j of the 2 NI that copy the raw tile at key n0 -- its K rows (j <
+// NI), then its V rows, as they lie in HBM -- to `lds`: 1 KiB, 16 B per lane.
+// Pieces past the tile's bytes stay idle (the instruction still counts).  Which
+// wave issues which j is the calling kernel's loop.  NT: dma's non-temporal policy.
+template <typename C, bool NT>
+__device__ __forceinline__ void raw_tile_dma(const StepSrc& rs, int n0, uint32_t lds, int j, int lane) {
 #ifdef FATTN_MQ_NOMEM
     return;  // diagnostic build only
 #endif
-    using C = PfCfg<KT, D>;
-    for (int j = wave; j < 2 * C::NI; j += kPfWaves) {  // wave-uniform
-        const bool is_v = j >= C::NI;
-        const int i = is_v ? j - C::NI : j;
-        const int byte = i * 1024 + lane * 16;
-        if (C::kvRaw % 1024 == 0 || byte < C::kvRaw)
-            dma<16>(is_v ? rs.v : rs.k, lds + (is_v ? C::kvRaw : 0) + i * 1024, (uint32_t)n0 * C::rowB + byte);
-    }
+    const bool is_v = j >= C::NI;
+    const int i = is_v ? j - C::NI : j;
+    const int byte = i * 1024 + lane * 16;
+    if (C::kvRaw % 1024 == 0 || byte < C::kvRaw)
+        dma<16, NT>(is_v ? rs.v : rs.k, lds + (is_v ? C::kvRaw : 0) + i * 1024, (uint32_t)n0 * C::rowB + byte);
+}
+
+// Half h of ggml block b of key `key`, K's and V's, converted -- h(q * d), one
+// f16 rounding (src/utils.h:10-11) -- into the images of a tile of KEYS keys:
+//   K image [D / 16 dim slices][KEYS keys][32 B]: slice 2 b + h, the 16-B halves swapped where Swz::k(key)
+//   V image [D / 32 dim blocks][KEYS keys][64 B]: block b, chunk c (2 h, 2 h + 1) at c ^ Swz::v(key)
+struct PfSwz {  // halves swapped on keys with bit 3 set; chunk c of key r at c ^ ((r >> 2) & 3)
+    static __host__ __device__ constexpr int k(int key) { return (key >> 3) & 1; }
+    static __host__ __device__ constexpr int v(int key) { return (key >> 2) & 3; }
+};
+template <int KT, int KEYS, typename Swz>
+__device__ __forceinline__ void image_store_half(const HalfRaw& rk, const HalfRaw& rv, uint8_t* k16, uint8_t* v16,
+                                                 int key, int b, int h) {
+#ifdef FATTN_MQ_NODEQ
+    return;  // diagnostic build only
+#endif
+    u32x4 ck[2], cv[2];
+    dequant_half_cvt<KT>(rk, h, ck);
+    dequant_half_cvt<KT>(rv, h, cv);
+    uint8_t* kd = k16 + (2 * b + h) * (KEYS * 32) + key * 32;
+    const int sk = Swz::k(key), sv = Swz::v(key);
+    *(u32x4*)(kd + sk * 16) = ck[0];
+    *(u32x4*)(kd + (sk ^ 1) * 16) = ck[1];
+    uint8_t* vd = v16 + b * (KEYS * 64) + key * 64;
+    *(u32x4*)(vd + ((2 * h) ^ sv) * 16) = cv[0];
+    *(u32x4*)(vd + ((2 * h + 1) ^ sv) * 16) = cv[1];
+}
+
+// instructions j = 0 .. 2*NI-1 go to wave j % 8
+template <int KT, int D>
+__device__ __forceinline__ void pf_issue(const StepSrc& rs, int n0, uint32_t lds, int wave, int lane) {
+    for (int j = wave; j < 2 * PfCfg<KT, D>::NI; j += kPfWaves)  // wave-uniform
+        raw_tile_dma<PfCfg<KT, D>, false>(rs, n0, lds, j, lane);
 }
 
 // f16 K/V: this lane's source offsets (tile-relative; + n0 * nb1 per tile) of
@@ -192,22 +230,9 @@ __device__ __forceinline__ PfRaw pf_dequant_load(const uint8_t* rb, int wave, in
 }
 template <int KT, int D>
 __device__ __forceinline__ void pf_dequant_store(const PfRaw& r, uint8_t* k16, uint8_t* v16, int wave, int lane) {
-#ifdef FATTN_MQ_NODEQ
-    return;  // diagnostic build only
-#endif
     const int b = wave >> 1, h = wave & 1;
     if (b >= D / QK) return;  // wave-uniform
-    u32x4 ck[2], cv[2];
-    dequant_half_cvt<KT>(r.k, h, ck);
-    dequant_half_cvt<KT>(r.v, h, cv);
-    uint8_t* kd = k16 + wave * (kPfKeys * 32) + lane * 32;
-    const int sk = (lane >> 3) & 1;
-    *(u32x4*)(kd + sk * 16) = ck[0];
-    *(u32x4*)(kd + (sk ^ 1) * 16) = ck[1];
-    uint8_t* vd = v16 + b * (kPfKeys * 64) + lane * 64;
-    const int sv = (lane >> 2) & 3;
-    *(u32x4*)(vd + ((2 * h) ^ sv) * 16) = cv[0];
-    *(u32x4*)(vd + ((2 * h + 1) ^ sv) * 16) = cv[1];
+    image_store_half<KT, kPfKeys, PfSwz>(r.k, r.v, k16, v16, lane, b, h);
 }
 
 template <int KT, int D>
@@ -265,19 +290,15 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
     // (the query tiles of a few heads share their K/V stream in one L2)
     if ((a.pf_stagger & 4) && gridDim.y % 8 == 0) y = (y & 7) * (gridDim.y >> 3) + (y >> 3);
     const int iq3 = blockIdx.z;
-    int qt = 0, ik2 = y, ik3 = iq3;
     if (a.pf_flags) {
         // masked: query tiles may see different KV ranges (causal: tile qt sees
         // 4 qt + 4 of them), so the longest go first -- the last query tile of
         // every head, then the one before, ... (longest-first dispatch)
         const int nh = gridDim.y / a.n_qt;
-        qt = a.n_qt - 1 - y / nh;
-        ik2 = y % nh;
-    } else if (a.n_qt != 1) {
-        qt = y % a.n_qt;
-        ik2 = y / a.n_qt;
+        y = a.n_qt - 1 - y / nh + a.n_qt * (y % nh);
     }
-    if (a.rk3 != 1) ik3 = iq3 / a.rk3;
+    int qt, hs, ik2, ik3;  // (hs = 0: whole head groups)
+    tile_decode<false>(a, y, iq3, qt, hs, ik2, ik3);
     auto row_of = [&](int p, int& iq1, int& iq2) {  // packed row -> (query row, q head)
         const int mq = div_R(a, p);
         iq1 = qt * a.QPT + mq;
@@ -322,10 +343,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
         }
     }
 
-    StepSrc rs;
-    rs.k = make_srd(a.k + (int64_t)ik2 * a.k_nb2 + (int64_t)ik3 * a.k_nb3, a.k_span);
-    rs.v = make_srd(a.v + (int64_t)ik2 * a.v_nb2 + (int64_t)ik3 * a.v_nb3, a.v_span);
-    rs.m = make_srd(mask_seq_base(a, iq3), HM ? a.m_span_h : 0);
+    const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3);
     const uint32_t lds0 = lds_addr(smem);
     constexpr int kNRaw = C::nRaw ? C::nRaw : 1;
     auto raw_lds = [&](int s) { return lds0 + C::rawOff + (s % kNRaw) * C::rawBytes; };

@@ -5,7 +5,7 @@ hipcc does not model the memory operations inside an `asm volatile` statement:
 the VGPR destination of an asm VMEM load counts as written at `;;#ASMEND`, so
 the compiler may read, copy, spill or reuse that register before the data has
 landed -- silently wrong results.  The product keeps exactly one kind of such
-load (ggml-cuda-experiments_amd/csrc/fattn_split.h `ld_buf_untracked<TAG>`:
+load (ggml-cuda-experiments_amd/csrc/fattn_tile.h `ld_buf_untracked<TAG>`:
 the split kernel's Q and mask-word prefetch, left untracked so that waiting for
 it does not drain the LDS-DMA issued behind it); every other hand-off load is a
 compiler-tracked builtin.  Each untracked load carries the asm comment
