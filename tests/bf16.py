@@ -10,7 +10,7 @@ Rounding (ggml_compute_fp32_to_bf16), on the f32 bits u:
 round to nearest even on the 16 dropped bits; subnormals are kept, a value past
 the largest finite bf16 becomes inf.  bf16 -> f32 is exact: bits << 16.
 
-The frozen oracle (oracle/) knows F16 / Q8_0 / Q4_0 only.  reference_pair()
+The frozen oracle (oracle/) knows F16 / Q8_0 / Q4_0 only.  kv_types.reference_pair()
 builds each in-range problem twice over the same logical tensors: `gpu`, whose
 K / V are bf16 rows, and `ref`, whose K / V are F16 rows of the SAME values --
 K / V are bf16 roundings of U[-1, 1] with |x| < 2^-14 set to 0, so every value
@@ -29,9 +29,8 @@ from typing import Optional
 import numpy as np
 
 import op_params as op
-import views
 from oracle import oracle as orc
-from problems import Problem, make_problem
+from problems import LAYOUTS, Problem, place_rows
 
 TYPE_BF16 = 30
 F = np.float32
@@ -82,54 +81,16 @@ def cache_values(x: np.ndarray) -> np.ndarray:
     set to 0 (exact in f16 as well)."""
     y = round_bf16(x)
     y[np.abs(y) < F(2.0 ** -14)] = F(0.0)
+    assert np.array_equal(orc.f16_bits_to_f32(orc.f32_to_f16_bits(y)), y)
     return y
-
-
-def _place(rows: np.ndarray, layout: str):
-    """rows [Skv][Hkv][N][rb] -> (flat bytes, nb) in problems.make_problem's layouts (2-byte elements)."""
-    Skv, Hkv, N, rb = rows.shape
-    if layout == "head":
-        return np.ascontiguousarray(rows).reshape(-1), (2, rb, rb * N, rb * N * Hkv)
-    if layout == "pos":
-        return np.ascontiguousarray(rows.transpose(0, 2, 1, 3)).reshape(-1), (2, rb * Hkv, rb, rb * N * Hkv)
-    if layout == "padded":
-        pad = rb + 8
-        buf = np.zeros((Skv, Hkv, N, pad), dtype=np.uint8)
-        buf[..., :rb] = rows
-        return buf.reshape(-1), (2, pad, pad * N, pad * N * Hkv)
-    raise ValueError(layout)
 
 
 def over_cache(base: Problem, k: np.ndarray, v: np.ndarray, layout: str = "head", **repl) -> Problem:
     """`base` with K / V replaced by bf16 rows of k / v (f32 [Skv][Hkv][N][D], already bf16 values)."""
     assert np.array_equal(round_bf16(k), k, equal_nan=True) and np.array_equal(round_bf16(v), v, equal_nan=True)
-    (kb, knb), (vb, vnb) = _place(encode_rows(k), layout), _place(encode_rows(v), layout)
+    (kb, knb), (vb, vnb) = place_rows(encode_rows(k), 2, *LAYOUTS[layout]), place_rows(encode_rows(v), 2, *LAYOUTS[layout])
     return dataclasses.replace(base, kv_type=TYPE_BF16, v_type=TYPE_BF16, layout=layout, k_bytes=kb, v_bytes=vb,
                                k_nb=knb, v_nb=vnb, k_f32=k, v_f32=v, **repl)
-
-
-def reference_pair(layout: str = "head", **kw):
-    """(gpu, ref): problems.make_problem(**kw) over a BF16 cache of the in-range
-    values in `layout`, and the same problem over F16 rows of the same values
-    (head layout) for the frozen oracle."""
-    base = make_problem(kv_type="f16", layout="head", **kw)
-    k, v = cache_values(base.k_f32), cache_values(base.v_f32)
-    hk, hv = orc.f32_to_f16_bits(k), orc.f32_to_f16_bits(v)
-    assert np.array_equal(orc.f16_bits_to_f32(hk), k) and np.array_equal(orc.f16_bits_to_f32(hv), v)
-    D = base.D
-    f16_rows = lambda h: _place(h.view(np.uint8).reshape(h.shape[:3] + (D * 2,)), "head")
-    (kr, krnb), (vr, vrnb) = f16_rows(hk), f16_rows(hv)
-    ref = dataclasses.replace(base, k_bytes=kr, v_bytes=vr, k_nb=krnb, v_nb=vrnb, k_f32=k, v_f32=v)
-    return over_cache(base, k, v, layout), ref
-
-
-def swap_kv(vp, gpu: Problem):
-    """A views.ViewProblem (or a subclass: mask planes, op params, sinks) built
-    over the F16 reference problem, with K / V replaced by the bf16 rows of `gpu`."""
-    pad = np.full(views.GUARD, views.KV_POISON, dtype=np.uint8)
-    k = views.Buf(np.concatenate([gpu.k_bytes, pad]), 0, gpu.kv_type, gpu.kv_ne, gpu.k_nb)
-    v = views.Buf(np.concatenate([gpu.v_bytes, pad]), 0, gpu.v_type, gpu.kv_ne, gpu.v_nb)
-    return dataclasses.replace(vp, base=gpu, k=k, v=v)
 
 
 # ------------------------------------------------------------------ float64 reference

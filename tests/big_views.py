@@ -353,7 +353,8 @@ def logical(case: Case):
         return from_problem(p), p.oracle()
     if case.kind == "bf16":
         import bf16
-        gpu, _ = bf16.reference_pair(**kw)
+        import kv_types
+        gpu, _ = kv_types.reference_pair("bf16", **kw)
         return from_problem(gpu), bf16.reference_f64(gpu)
     if case.kind == "ext":
         import kv_types

@@ -29,12 +29,15 @@ operands to f16 anyway.
 from __future__ import annotations
 
 import dataclasses
+import functools
+from typing import Callable
 
 import numpy as np
 
-import views
+import bf16
+from gpu_util import check_bars
 from oracle import oracle as orc
-from problems import Problem, make_problem, row_bytes  # noqa: F401 (row_bytes: this module's users take it from here)
+from problems import LAYOUTS, make_problem, place_rows, row_bytes
 
 F = np.float32
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
@@ -141,46 +144,77 @@ def edge_blocks() -> np.ndarray:
     return b
 
 
-def _place(rows: np.ndarray, typ: int, layout: str):
-    """rows [Skv][Hkv][N][rb] -> (flat bytes, nb) in problems.make_problem's layouts."""
-    Skv, Hkv, N, rb = rows.shape
-    eb = 2 if typ == orc.TYPE_F16 else BLOCK_BYTES[typ]
-    if layout == "head":
-        return np.ascontiguousarray(rows).reshape(-1), (eb, rb, rb * N, rb * N * Hkv)
-    if layout == "pos":
-        return np.ascontiguousarray(rows.transpose(0, 2, 1, 3)).reshape(-1), (eb, rb * Hkv, rb, rb * N * Hkv)
-    if layout == "padded":
-        pad = rb + 8
-        buf = np.zeros((Skv, Hkv, N, pad), dtype=np.uint8)
-        buf[..., :rb] = rows
-        return buf.reshape(-1), (eb, pad, pad * N, pad * N * Hkv)
-    raise ValueError(layout)
+# ------------------------------------------------------------------ the cache types of the GPU suite
+
+@dataclasses.dataclass(frozen=True)
+class KvType:
+    """A cache type the frozen oracle does not know, as tests/test_gpu_kv_types.py needs it."""
+    name: str
+    typ: int
+    eb: int                  # nb[0]: the bytes of an element or block
+    values: Callable         # U[-1, 1] f32 data -> the f32 values handed to encode (identity; BF16: its in-range values)
+    encode: Callable         # f32 [..., D] -> row bytes u8 [..., row_bytes]
+    decode: Callable         # (row bytes u8 [..., row_bytes], D) -> f32 [..., D], what a kernel reads
+    conv_extra: Callable     # (x f32 [64][128]) -> two more rows of conversion input: the type's edge cases
+    line: str                # the figure line of a case
+    f64: bool                # checked against bf16.reference_f64 as well as against the oracle
+
+
+def _bf16_extra(x):
+    return np.concatenate([bf16.edge_values().reshape(1, 128), (x[:1] * F(2.0 ** 100)).astype(F)])   # (far outside f16's range)
+
+
+def _quant(name, typ):
+    return KvType(name, typ, BLOCK_BYTES[typ], lambda x: x, lambda x: quantize(x, typ), lambda rows, D: dequantize(rows, typ, D),
+                  lambda x: edge_blocks().reshape(2, 128), "KVT " + name + " {tag} rel={rel:.3e} elem={elem:.3f} | {desc}", False)
+
+
+KV_TYPES = {n: _quant(n, t) for n, t in TYPES.items()}
+KV_TYPES["bf16"] = KvType("bf16", bf16.TYPE_BF16, 2, bf16.cache_values, bf16.encode_rows,
+                          lambda rows, D: bf16.bf16_bits_to_f32(np.ascontiguousarray(rows).view("<u2")), _bf16_extra,
+                          "BF16 {tag} vs {what} rel={rel:.3e} elem={elem:.4f} | {desc}", True)
+
+
+def conv_input(t: KvType) -> np.ndarray:
+    """f32 [66][128]: 64 rows of U[-3, 3] and the type's two edge rows."""
+    rng = np.random.default_rng(11)
+    x = (3.0 * (1.0 - 2.0 * rng.random((64, 128), dtype=F))).astype(F)
+    return np.concatenate([x, t.conv_extra(x)], axis=0)
 
 
 def reference_pair(kv_type: str, layout: str = "head", **kw):
     """(gpu, ref): problems.make_problem(**kw) over a cache of kv_type in `layout`,
-    and the same problem over F16 views of the f16-rounded dequantised blocks
-    (head layout) for the frozen oracle."""
-    typ = TYPES[kv_type]
+    and the same problem over F16 rows (head layout) holding the f16 rounding of
+    what a kernel reads from that cache, for the frozen oracle.  Both carry the
+    encoded values as k_f32 / v_f32."""
+    t = KV_TYPES[kv_type]
     base = make_problem(kv_type="f16", layout="head", **kw)
     D = base.D
-    out = {}
-    for name, x in (("k", base.k_f32), ("v", base.v_f32)):
-        blocks = quantize(x, typ)                                    # [Skv][Hkv][N][rb]
-        h16 = orc.f32_to_f16_bits(dequantize(blocks, typ, D))        # [Skv][Hkv][N][D] u16
-        out[name] = (_place(blocks, typ, layout), _place(h16.view(np.uint8).reshape(h16.shape[:3] + (D * 2,)), orc.TYPE_F16, "head"))
-    (kb, knb), (kr, krnb) = out["k"]
-    (vb, vnb), (vr, vrnb) = out["v"]
-    gpu = dataclasses.replace(base, kv_type=typ, v_type=typ, layout=layout, k_bytes=kb, v_bytes=vb, k_nb=knb, v_nb=vnb)
-    ref = dataclasses.replace(base, k_bytes=kr, v_bytes=vr, k_nb=krnb, v_nb=vrnb)
-    return gpu, ref
+    g, r = {}, {}
+    for n, x in (("k", base.k_f32), ("v", base.v_f32)):
+        x = t.values(x)
+        rows = t.encode(x)                                           # [Skv][Hkv][N][rb]
+        h16 = orc.f32_to_f16_bits(t.decode(rows, D))                 # [Skv][Hkv][N][D] u16
+        (gb, gnb), (rb, rnb) = place_rows(rows, t.eb, *LAYOUTS[layout]), place_rows(h16.view(np.uint8), 2)
+        g.update({n + "_bytes": gb, n + "_nb": gnb, n + "_f32": x})
+        r.update({n + "_bytes": rb, n + "_nb": rnb, n + "_f32": x})
+    return dataclasses.replace(base, kv_type=t.typ, v_type=t.typ, layout=layout, **g), dataclasses.replace(base, **r)
 
 
-def swap_kv(vp, gpu: Problem):
-    """A views.ViewProblem (or a subclass: mask planes, op params, sinks) built
-    over the F16 reference problem, with K / V replaced by the blocks of `gpu`
-    (views.make_view cannot lay out a type the oracle does not know)."""
-    pad = np.full(views.GUARD, views.KV_POISON, dtype=np.uint8)
-    k = views.Buf(np.concatenate([gpu.k_bytes, pad]), 0, gpu.kv_type, gpu.kv_ne, gpu.k_nb)
-    v = views.Buf(np.concatenate([gpu.v_bytes, pad]), 0, gpu.v_type, gpu.kv_ne, gpu.v_nb)
-    return dataclasses.replace(vp, base=gpu, k=k, v=v)
+@functools.lru_cache(maxsize=None)
+def cached_pair(kv_type: str, layout: str = "head", **kw):
+    """(gpu problem, F16 problem, oracle output, float64 output or None), computed once per shape."""
+    gpu, ref = reference_pair(kv_type, layout, **kw)
+    return gpu, ref, ref.oracle(), bf16.reference_f64(gpu) if KV_TYPES[kv_type].f64 else None
+
+
+def check(kv_type: str, tag, desc, got, ref, what="oracle(f16 views)"):
+    """The suite's bars against one reference, the type's figure line printed first; returns the normwise error."""
+    return check_bars(got, ref, lambda rel, elem: KV_TYPES[kv_type].line.format(tag=tag, what=what, rel=rel, elem=elem, desc=desc))[0]
+
+
+def check_both(kv_type: str, tag, desc, got, oracle, f64):
+    """check() against the oracle and, for a type with a float64 reference (f64() -> its output), against that."""
+    check(kv_type, tag, desc, got, oracle)
+    if KV_TYPES[kv_type].f64:
+        return check(kv_type, tag, desc, got, f64() if callable(f64) else f64, "f64")

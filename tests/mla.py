@@ -212,16 +212,10 @@ def logical_q(c: Case, v_form: str) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate([lat, rest] if v_form == "view0" else [rest, lat], axis=-1))
 
 
-def _place(rows_f32: np.ndarray, layout: str):
-    """f32 rows [Skv][Hkv][N][d] -> (poisoned u8 buffer, nb) in `layout`."""
-    Skv, Hkv, N, d = rows_f32.shape
-    rows = orc.f32_to_f16_bits(rows_f32).view(np.uint8).reshape(Skv, Hkv, N, d * 2)
-    rb = d * 2 + (ROW_PAD if layout == "pad" else 0)
-    if layout == "pos":
-        nb = (2, Hkv * rb, rb, N * Hkv * rb)
-    else:
-        nb = (2, rb, N * rb, Hkv * N * rb)
-    return views._scatter(rows, nb, 0, np.array([views.KV_POISON])), nb
+def f16_cache(rows_f32: np.ndarray, layout: str):
+    """f32 rows [Skv][Hkv][N][d] -> (poisoned u8 buffer, nb) of f16 rows in `layout`."""
+    rows = orc.f32_to_f16_bits(rows_f32).view(np.uint8).reshape(rows_f32.shape[:3] + (rows_f32.shape[3] * 2,))
+    return views.place_rows(rows, 2, "pos" if layout == "pos" else "head", ROW_PAD if layout == "pad" else 0, views.KV_POISON)
 
 
 FAKE = {"q": 1 << 20, "k": 2 << 20, "v": 3 << 20, "mask": 4 << 20, "dst": 5 << 20}
@@ -236,8 +230,8 @@ class MlaLaunch:
         self.c, self.layout, self.v_form = c, layout, v_form
         sh = c.shape
         krows, vrows, self.v_off_bytes = cache_rows(c, v_form)
-        self.k_buf, self.k_nb = _place(krows, layout)
-        self.v_buf, self.v_nb = _place(vrows, layout) if vrows is not None else (None, self.k_nb)
+        self.k_buf, self.k_nb = f16_cache(krows, layout)
+        self.v_buf, self.v_nb = f16_cache(vrows, layout) if vrows is not None else (None, self.k_nb)
         self.q = logical_q(c, v_form)
         self.q_ne = (DK, sh.NQ, sh.H, sh.S)
         self.q_nb = (4, sh.H * DK * 4, DK * 4, sh.NQ * sh.H * DK * 4)
@@ -261,63 +255,25 @@ class MlaLaunch:
                                 n_head_total=r.n_head_total, head_first=r.head_first)
 
 
-class MlaGpu:
-    """An MlaLaunch on the GPU: dst between two 4 KiB sentinel bands (pre-filled
-    with NaN), the workspace sized to exactly fattn.workspace_size() with a
-    sentinel tail, zeroed once (or handed in: `ws`, a shared workspace)."""
+def gpu_launch(L, kv_chunk=0, dev="cuda", ws=None, k_tensor=None):
+    """L (an MlaLaunch or a mla_quant.QLaunch) on the GPU: its
+    gpu_util.GuardedLaunch -- dst [S][NQ][H][512] between the sentinel bands, the
+    exactly-sized workspace with its sentinel tail or `ws`, a shared one.
+    k_tensor: a device buffer that already holds the K cache, instead of L's."""
+    import torch
 
-    def __init__(self, c: Case, layout="head", v_form="view128", kv_chunk=0, dev="cuda", ws=None):
-        import torch
+    from gpu_util import GuardedLaunch
+    r, sh = L.c.ref, L.c.shape
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t = {"q": up(L.q.reshape(-1).view(np.uint8)), "k": up(L.k_buf) if k_tensor is None else k_tensor}
+    if L.v_buf is not None:
+        t["v"] = up(L.v_buf)
+    if r.mask is not None:
+        t["mask"] = up(r.mask.data)
+    ptrs = {n: x.data_ptr() for n, x in t.items()}
+    return GuardedLaunch(lambda dst: L.params(dict(ptrs, dst=dst), kv_chunk=kv_chunk), (sh.S, sh.NQ, sh.H, DV), t, dev,
+                         sinks=r.sinks, ws=ws)
 
-        import fattn
-        self.L = L = MlaLaunch(c, layout, v_form)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.t = {"q": up(L.q.reshape(-1).view(np.uint8)), "k": up(L.k_buf)}
-        if L.v_buf is not None:
-            self.t["v"] = up(L.v_buf)
-        if c.ref.mask is not None:
-            self.t["mask"] = up(c.ref.mask.data)
-        self.sinks_t = up(c.ref.sinks) if c.ref.sinks is not None else None
-        g = views.DST_GUARD_BYTES // 4
-        self.dst_all = torch.full((g + L.n_out + g,), views.SENTINEL, dtype=torch.int32, device=dev)
-        self.dst = self.dst_all[g:g + L.n_out].view(torch.float32)
-        ptrs = {n: x.data_ptr() for n, x in self.t.items()}
-        ptrs["dst"] = self.dst.data_ptr()
-        self.p = L.params(ptrs, kv_chunk=kv_chunk)
-        self.ws_bytes = fattn.workspace_size(self.p)
-        if ws is None:
-            ws = torch.full(((self.ws_bytes + 3) // 4 + views.WS_TAIL_BYTES // 4,), views.SENTINEL, dtype=torch.int32,
-                            device=dev)
-            ws.view(torch.uint8)[:self.ws_bytes].zero_()
-        self.ws_all = ws
-        if self.ws_bytes:
-            assert ws.numel() * 4 >= self.ws_bytes
-            self.p.workspace = ws.data_ptr()
-            self.p.workspace_bytes = self.ws_bytes
 
-    def describe(self) -> str:
-        import fattn
-        return fattn.describe(self.p)
-
-    def launch(self):
-        import fattn
-        fattn.flash_attn_ext(self.p, sinks=self.sinks_t)
-
-    def run(self) -> np.ndarray:
-        """The whole dst allocation, f32 [S][NQ][H][512]."""
-        import torch
-        sh = self.L.c.shape
-        self.dst.fill_(float("nan"))
-        self.launch()
-        torch.cuda.synchronize()
-        return self.dst.cpu().numpy().reshape(sh.S, sh.NQ, sh.H, DV)
-
-    def guards_intact(self) -> bool:
-        import torch
-        g = views.DST_GUARD_BYTES // 4
-        d = self.dst_all.cpu().numpy().view(np.uint32)
-        w = self.ws_all.view(torch.uint8)[self.ws_bytes:self.ws_bytes + views.WS_TAIL_BYTES].cpu().numpy()
-        want = np.full(views.WS_TAIL_BYTES // 4 + 1, views.SENTINEL, dtype=np.uint32).view(np.uint8)
-        want = want[self.ws_bytes % 4:][:len(w)]
-        return bool((d[:g] == views.SENTINEL).all() and (d[g + self.L.n_out:] == views.SENTINEL).all()
-                    and np.array_equal(w, want))
+def MlaGpu(c: Case, layout="head", v_form="view128", kv_chunk=0, dev="cuda", ws=None):
+    return gpu_launch(MlaLaunch(c, layout, v_form), kv_chunk, dev, ws)

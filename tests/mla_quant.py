@@ -103,14 +103,6 @@ def cached(sh: Shape, typ: str, mask: str = "none", v_off: int = 64, seed: int =
     return c, ref
 
 
-def place(rows: np.ndarray, nb0: int, layout: str, base: int = 0):
-    """u8 rows [Skv][Hkv][N][rb] -> (poisoned buffer, nb); the view starts `base` bytes in."""
-    Skv, Hkv, N, rb0 = rows.shape
-    rb = rb0 + PAD[layout]
-    nb = (nb0, Hkv * rb, rb, N * Hkv * rb) if layout == "pos" else (nb0, rb, N * rb, Hkv * N * rb)
-    return views._scatter(np.ascontiguousarray(rows), nb, base, np.array([views.KV_POISON])), nb
-
-
 class QLaunch:
     """The fattn params of a QCase: form "quant" (the blocks, V b = v_off / 32
     blocks in) or "f16" (the logical K as f16 rows, V 2 v_off bytes in)."""
@@ -127,7 +119,8 @@ class QLaunch:
             self.type_name, nb0 = "f16", 2
             rows = orc.f32_to_f16_bits(k).view(np.uint8).reshape(sh.Skv, sh.Hkv, sh.N, DK * 2)
             self.v_off_bytes = 2 * c.v_off
-        self.k_buf, self.k_nb = place(rows, nb0, layout, base)
+        self.k_buf, self.k_nb = views.place_rows(rows, nb0, "pos" if layout == "pos" else "head", PAD[layout], views.KV_POISON,
+                                                 off=base)
         self.v_buf, self.v_nb = None, self.k_nb
         self.q = np.ascontiguousarray(c.ref.base.q)
         self.q_ne = (DK, sh.NQ, sh.H, sh.S)
@@ -150,33 +143,7 @@ class QLaunch:
                                 n_head_total=r.n_head_total, head_first=r.head_first)
 
 
-class QGpu(mla.MlaGpu):
-    """mla.MlaGpu over a QLaunch (same dst guard bands, workspace tail and run())."""
-
-    def __init__(self, c: QCase, form="quant", layout="head", base=0, kv_chunk=0, dev="cuda", ws=None, k_tensor=None):
-        """k_tensor: a device buffer that already holds the cache (written on the device), instead of the host-built one."""
-        import torch
-
-        import fattn
-        self.L = L = QLaunch(c, form, layout, base)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        self.t = {"q": up(L.q.reshape(-1).view(np.uint8)), "k": up(L.k_buf) if k_tensor is None else k_tensor}
-        if c.ref.mask is not None:
-            self.t["mask"] = up(c.ref.mask.data)
-        self.sinks_t = up(c.ref.sinks) if c.ref.sinks is not None else None
-        g = views.DST_GUARD_BYTES // 4
-        self.dst_all = torch.full((g + L.n_out + g,), views.SENTINEL, dtype=torch.int32, device=dev)
-        self.dst = self.dst_all[g:g + L.n_out].view(torch.float32)
-        ptrs = {n: x.data_ptr() for n, x in self.t.items()}
-        ptrs["dst"] = self.dst.data_ptr()
-        self.p = L.params(ptrs, kv_chunk=kv_chunk)
-        self.ws_bytes = fattn.workspace_size(self.p)
-        if ws is None:
-            ws = torch.full(((self.ws_bytes + 3) // 4 + views.WS_TAIL_BYTES // 4,), views.SENTINEL, dtype=torch.int32,
-                            device=dev)
-            ws.view(torch.uint8)[:self.ws_bytes].zero_()
-        self.ws_all = ws
-        if self.ws_bytes:
-            assert ws.numel() * 4 >= self.ws_bytes
-            self.p.workspace = ws.data_ptr()
-            self.p.workspace_bytes = self.ws_bytes
+def QGpu(c: QCase, form="quant", layout="head", base=0, kv_chunk=0, dev="cuda", ws=None, k_tensor=None):
+    """mla.gpu_launch over a QLaunch (same dst guard bands, workspace tail and run()).  k_tensor: a device
+    buffer that already holds the cache (written on the device), instead of the host-built one."""
+    return mla.gpu_launch(QLaunch(c, form, layout, base), kv_chunk, dev, ws, k_tensor)

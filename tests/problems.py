@@ -10,6 +10,7 @@ from dataclasses import dataclass, field
 from typing import Optional
 
 import numpy as np
+from numpy.lib.stride_tricks import as_strided
 
 import fattn
 from oracle import oracle as orc
@@ -31,6 +32,48 @@ def encode_rows(x: np.ndarray, typ: int) -> np.ndarray:
     if typ == orc.TYPE_F16:
         return orc.f32_to_f16_bits(x).view(np.uint8).reshape(x.shape[:-1] + (x.shape[-1] * 2,))
     return orc.quantize(x, typ)
+
+
+GUARD = 256          # poison bytes after every poisoned view
+# make_problem's layouts as place_rows' (layout, row_pad); "padded": a row stride
+# larger than the row (forces the dword-granular path)
+LAYOUTS = {"head": ("head", 0), "pos": ("pos", 0), "padded": ("head", 8)}
+
+
+def scatter(rows: np.ndarray, nb, off: int, fill: np.ndarray) -> np.ndarray:
+    """rows [n3][n2][n1][row bytes] written at byte strides (nb3, nb2, nb1) from
+    `off` into a buffer pre-filled with `fill` (a 1-element array: the poison
+    pattern), GUARD bytes of poison after the last element."""
+    n3, n2, n1, rb = rows.shape
+    span = (n3 - 1) * nb[3] + (n2 - 1) * nb[2] + (n1 - 1) * nb[1] + rb
+    total = off + span + GUARD
+    unit = fill.dtype.itemsize
+    total = (total + unit - 1) // unit * unit
+    buf = np.full(total // unit, fill[0], dtype=fill.dtype).view(np.uint8)
+    dstv = as_strided(buf[off:], shape=rows.shape, strides=(nb[3], nb[2], nb[1], 1), writeable=True)
+    dstv[...] = rows
+    return buf
+
+
+def place_rows(rows: np.ndarray, eb: int, layout: str = "head", row_pad: int = 0, fill=None, off: int = 0, n_ctx=None,
+               gap: int = 0):
+    """Cache rows u8 [Skv][Hkv][N][row bytes] laid out as a K or V view: (flat
+    buffer, nb).  eb: nb[0], the bytes of an element or block; layout "head"
+    [Skv][Hkv][n_ctx][row] or "pos" [Skv][n_ctx][Hkv][row]; row_pad: bytes behind
+    every row; n_ctx: the rows the cache has room for (N); gap: bytes between
+    the sequences; the view starts `off` bytes into the buffer.  fill None: the
+    buffer ends with the last sequence and its other bytes are zero; fill (a
+    byte): every byte outside the rows is that poison, GUARD of them at the end."""
+    if layout not in ("head", "pos"):
+        raise ValueError(layout)
+    Skv, Hkv, N, rb = rows.shape
+    rb, n = rb + row_pad, n_ctx or N
+    nb = (eb, Hkv * rb, rb, n * Hkv * rb + gap) if layout == "pos" else (eb, rb, n * rb, Hkv * n * rb + gap)
+    if fill is not None:
+        return scatter(np.ascontiguousarray(rows), nb, off, np.array([fill], dtype=np.uint8)), nb
+    buf = np.zeros(off + Skv * nb[3], dtype=np.uint8)
+    as_strided(buf[off:], shape=rows.shape, strides=(nb[3], nb[2], nb[1], 1), writeable=True)[...] = rows
+    return buf, nb
 
 
 @dataclass
@@ -138,23 +181,8 @@ def make_problem(D=128, NQ=1, H=32, Hkv=None, N=4096, kv_type="q8_0", S=1, Skv=N
     k_rows = encode_rows(k, typ)   # [Skv][Hkv][N][row bytes]
     v_rows = encode_rows(v, vtyp)
 
-    def place(rows, t):
-        rb = row_bytes(t, D)
-        eb = elem_bytes(t)
-        if layout == "head":
-            return np.ascontiguousarray(rows), (eb, rb, rb * N, rb * N * Hkv)
-        if layout == "pos":
-            return np.ascontiguousarray(rows.transpose(0, 2, 1, 3)), (eb, rb * Hkv, rb, rb * N * Hkv)  # [Skv][N][Hkv][rb]
-        if layout == "padded":
-            # rows with a stride larger than the row (forces the dword-granular path)
-            pad = rb + 8
-            buf = np.zeros((Skv, Hkv, N, pad), dtype=np.uint8)
-            buf[..., :rb] = rows
-            return buf, (eb, pad, pad * N, pad * N * Hkv)
-        raise ValueError(layout)
-
-    k_buf, k_nb = place(k_rows, typ)
-    v_buf, v_nb = place(v_rows, vtyp)
+    k_buf, k_nb = place_rows(k_rows, elem_bytes(typ), *LAYOUTS[layout])
+    v_buf, v_nb = place_rows(v_rows, elem_bytes(vtyp), *LAYOUTS[layout])
     if v_trans:
         assert typ == orc.TYPE_F16 and vtyp == orc.TYPE_F16
         vt = orc.f32_to_f16_bits(np.ascontiguousarray(v.transpose(0, 1, 3, 2)))  # [Skv][Hkv][D][N]
@@ -226,3 +254,17 @@ def attn_elem_err(got: np.ndarray, ref: np.ndarray, rtol: float = 2e-3, atol_row
     g, r = got[ok], ref[ok]
     den = rtol * np.abs(r) + atol_row * np.maximum(np.abs(r).max(axis=1, keepdims=True), 1e-30)
     return float((np.abs(g - r) / den).max())
+
+
+def oracle_of_dump(d):
+    """The CPU oracle over the inputs of a bench.py dump (--dump-out: shape, q, k, v, mask)."""
+    D, NQ, H, Hkv, N, typ, world = (int(x) for x in d["shape"])
+    rb = D // 32 * orc.BLOCK_BYTES[typ]
+    kv_nb = (orc.BLOCK_BYTES[typ], rb, rb * N, rb * N * Hkv)  # bench's "head" layout
+    q = np.ascontiguousarray(d["q"], dtype=np.float32)        # [1][NQ][H][D]
+    mask = np.ascontiguousarray(d["mask"])                   # [NQ][Npad] f16 bits
+    rows, npad = mask.shape
+    return orc.flash_attn_ext((q, orc.TYPE_F32, (D, NQ, H, 1), (4, H * D * 4, D * 4, NQ * H * D * 4)),
+                              (d["k"], typ, (D, N, Hkv, 1), kv_nb), (d["v"], typ, (D, N, Hkv, 1), kv_nb),
+                              (mask, orc.TYPE_F16, (npad, rows, 1, 1), (2, npad * 2, npad * rows * 2, npad * rows * 2)),
+                              float(np.float32(1.0 / D ** 0.5)), n_threads=16)

@@ -106,31 +106,22 @@ def reference(sp: SinkProblem, sinks=None, plain: Optional[np.ndarray] = None) -
     return out
 
 
-class SinkGpuView(views.GpuView):
+def SinkGpuView(sp: SinkProblem, dev="cuda", kv_chunk: int = 0):
     """views.GpuView (dst guard bands, exactly-sized workspace and its
-    sentinel) whose run() uploads the problem's sinks and launches
-    fattn.flash_attn_ext(p, sinks=...).  null=True: fattn_ext_sinks(p, NULL)
-    through the C ABI itself."""
+    sentinel) that uploads the problem's sinks and launches
+    fattn.flash_attn_ext(p, sinks=...)."""
+    assert sp.sinks is not None
+    return views.GpuView(sp, dev, kv_chunk, sinks=sp.sinks)
 
-    def __init__(self, sp, dev="cuda", kv_chunk: int = 0, null: bool = False):
-        import torch
-        super().__init__(sp, dev, kv_chunk)
-        sk = getattr(sp, "sinks", None)
-        assert null or sk is not None
-        self.null = null
-        self.sinks_t = None if null else torch.from_numpy(np.ascontiguousarray(sk, dtype=np.float32)).to(dev)
 
-    def run(self) -> np.ndarray:
-        import ctypes as C
+def run_null_sinks(g) -> np.ndarray:
+    """g.run() of a gpu_util.GuardedLaunch with fattn_ext_sinks(p, NULL) through the C ABI itself as the launch."""
+    import ctypes as C
 
-        import fattn
-        import torch
-        b = self.vp.base
-        self.dst.fill_(float("nan"))
-        if self.null:
-            rc = fattn.lib().fattn_ext_sinks(C.byref(self.p), None, torch.cuda.current_stream().cuda_stream)
-            assert rc == 0, rc
-        else:
-            fattn.flash_attn_ext(self.p, sinks=self.sinks_t)
-        torch.cuda.synchronize()
-        return self.dst.cpu().numpy().reshape(b.S, b.NQ, b.H, b.D)
+    import fattn
+    import torch
+    g.dst.fill_(float("nan"))
+    rc = fattn.lib().fattn_ext_sinks(C.byref(g.p), None, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return g.dst.cpu().numpy().reshape(g.out_shape)

@@ -7,6 +7,7 @@ import re
 import pytest
 
 import fattn
+from plans import plan_params as _params
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -59,16 +60,6 @@ def test_strerror_and_sizes():
     assert fattn.row_size(fattn.TYPE_F16, 128) == 256
     assert fattn.row_size(fattn.TYPE_Q8_0, 100) == 0
     assert fattn.lib().fattn_version().startswith(b"fattn-gfx950")
-
-
-def _params(D=128, NQ=1, H=32, Hkv=32, N=4096, kt=fattn.TYPE_Q8_0, kv_chunk=0, ptr=1 << 20, mask=True, vt=None):
-    def view(t):
-        rb = fattn.row_size(t, D)
-        eb = 2 if t == fattn.TYPE_F16 else fattn.BLOCK_BYTES.get(t, 4)
-        return fattn.View(ptr, t, (D, N, Hkv, 1), (eb, rb, rb * N, rb * N * Hkv))
-    q = fattn.View(ptr, fattn.TYPE_F32, (D, NQ, H, 1), (4, H * D * 4, D * 4, NQ * H * D * 4))
-    m = fattn.View(ptr, fattn.TYPE_F16, (N, NQ, 1, 1), (2, N * 2, N * 2 * NQ, N * 2 * NQ)) if mask else None
-    return fattn.ext_params(q, view(kt), view(kt if vt is None else vt), m, ptr, 0.088, kv_chunk=kv_chunk)
 
 
 def test_workspace_size_config3():

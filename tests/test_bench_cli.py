@@ -10,8 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from problems import attn_rel_err
-from test_rehearsal import _oracle_of
+from problems import attn_rel_err, oracle_of_dump as _oracle_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

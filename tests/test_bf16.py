@@ -4,6 +4,7 @@ F16 split plan's grid and workspace), what stays rejected, the numpy rounding
 rule (tests/bf16.py) against known answers written out by hand, and the
 numerical design: the bf16 hi / lo operand pairs are under the project's 1e-3
 bar against float64 where one bf16 operand is over it."""
+import functools
 import json
 import os
 
@@ -12,8 +13,9 @@ import pytest
 
 import bf16
 import fattn
+import kv_types as kt
+from plans import plan_params as abi_params
 from problems import attn_elem_err, attn_rel_err
-from test_abi import _params as abi_params
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "bf16_kat.json")
 BF16, F16 = fattn.TYPE_BF16, fattn.TYPE_F16
@@ -21,17 +23,7 @@ BF16, F16 = fattn.TYPE_BF16, fattn.TYPE_F16
 SHAPES = {"decode": dict(), "batched": dict(NQ=64), "prefill": dict(NQ=4096, H=8, Hkv=8, N=4096)}
 
 
-def _params(D=128, NQ=1, H=32, Hkv=32, N=4096, kt=BF16, kv_chunk=0, ptr=1 << 20, mask=True, vt=None, v_nb=None,
-            dk=None, dv=None):
-    """tests/test_abi.py's _params with 2-byte elements for BF16 rows; v_nb: V's
-    strides; dk / dv: K's / V's row lengths where they differ from D (MLA)."""
-    def view(t, d, nb=None):
-        rb = fattn.row_size(t, d)
-        eb = 2 if t in (F16, BF16) else fattn.BLOCK_BYTES.get(t, 4)
-        return fattn.View(ptr, t, (d, N, Hkv, 1), nb or (eb, rb, rb * N, rb * N * Hkv))
-    q = fattn.View(ptr, fattn.TYPE_F32, (D, NQ, H, 1), (4, H * D * 4, D * 4, NQ * H * D * 4))
-    m = fattn.View(ptr, fattn.TYPE_F16, (N, NQ, 1, 1), (2, N * 2, N * 2 * NQ, N * 2 * NQ)) if mask else None
-    return fattn.ext_params(q, view(kt, dk or D), view(kt if vt is None else vt, dv or D, v_nb), m, ptr, 0.088, kv_chunk=kv_chunk)
+_params = functools.partial(abi_params, kt=BF16)   # (the BF16 cache of the same shapes)
 
 
 def test_constants_and_row_size():
@@ -150,7 +142,7 @@ def test_hi_lo_operands_are_the_design(D):
     """On the seeds of the GPU one-row cases: the emulated kernel with Q and P as
     bf16 hi / lo pairs is under attn_rel_err 1e-3 (and attn_elem_err 1) against
     float64; with one bf16 per operand, or with Q alone split, it is over."""
-    gpu, _ = bf16.reference_pair(D=D, NQ=1, H=4, N=544, mask="random", seed=21 + D)
+    gpu, _ = kt.reference_pair("bf16", D=D, NQ=1, H=4, N=544, mask="random", seed=21 + D)
     ref = bf16.reference_f64(gpu)
     both = bf16.emulate(gpu)
     rel, elem = attn_rel_err(both, ref), attn_elem_err(both, ref)
@@ -164,7 +156,7 @@ def test_hi_lo_operands_are_the_design(D):
 
 
 def test_cache_values_are_exact_in_f16():
-    gpu, ref = bf16.reference_pair(D=64, NQ=1, H=2, N=96, mask="none", seed=1)
+    gpu, ref = kt.reference_pair("bf16", D=64, NQ=1, H=2, N=96, mask="none", seed=1)
     assert np.array_equal(gpu.k_f32, ref.k_f32)
     assert np.array_equal(gpu.k_f32.astype(np.float16).astype(np.float32), gpu.k_f32)
     assert np.array_equal(bf16.bf16_bits_to_f32(gpu.k_bytes.view("<u2")).reshape(gpu.k_f32.shape), gpu.k_f32)

@@ -15,7 +15,7 @@ import pytest
 
 import fattn
 from fattn.shard import assemble_heads, head_views, shard_heads
-from gpu_util import run_gpu, upload, views
+from gpu_util import capture, run_gpu, upload, views
 from oracle import oracle as orc
 from problems import attn_elem_err, attn_rel_err, make_problem
 
@@ -469,13 +469,7 @@ def _replay_new_inputs(dev, shape, n_iter=12):
     t = upload(probs[0], dev)
     att = fattn.Attention(*views(probs[0], t), t["dst"], probs[0].scale)
     assert int(att.describe().split("grid(")[1].split(",")[0]) > 1, att.describe()
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        att(s.cuda_stream)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        att(s.cuda_stream)
+    g = capture(att)
     noise_src = torch.randn(1 << 25, device=dev)
     noise_dst = torch.empty_like(noise_src)
     side = torch.cuda.Stream()

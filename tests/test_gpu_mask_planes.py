@@ -1,7 +1,7 @@
 """GPU: mask planes (mask ne[2] / ne[3], include/fattn.h) on every plan.
 
 Each case takes one plan at its smallest shape (the rows of
-tests/test_gpu_views.py's table, one type per distinct kernel body), gives the
+tests/plans.py's table, one type per distinct kernel body), gives the
 mask (ne2, ne3) planes laid out as a poisoned view (tests/mask_planes.py) and
 
   (a) asserts fattn_describe names the intended kernel and the plane counts,
@@ -10,74 +10,25 @@ mask (ne2, ne3) planes laid out as a poisoned view (tests/mask_planes.py) and
       suite's bounds -- NaN positions must coincide, so one poisoned gap or pad
       column leaking into an output element fails the case,
   (c) checks dst's guard bands and the sentinel behind the exactly-sized
-      workspace (views.GpuView).
+      workspace (gpu_util.GuardedLaunch).
 
 The planes differ in where they turn -inf (N, N // 5 + 5, N // 2 + 3) and every
 case runs with the full-length plane first and with the shortest first: a step
 skip or a live-block table taken from another plane drops live keys in one
 order or fetches dead ones -- and reads another plane's values -- in the other.
 """
-from dataclasses import dataclass
-
 import numpy as np
 import pytest
 
 import fattn
 import mask_planes as mp
 import views
-from problems import attn_elem_err, attn_rel_err, make_problem
+from gpu_util import check_bars
+from plans import BD, BDP, PF1, PF4, PLANE_SPECS as SPECS, Spec
+from problems import make_problem
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-3
 
-
-@dataclass(frozen=True)
-class Spec:
-    plan: str
-    kernel: str               # what describe() must name
-    D: int
-    kt: str
-    shape: tuple              # (NQ, H, Hkv, N)
-    opts: tuple = ()
-    kv_chunk: int = 0
-    tag: str = ""
-
-    @property
-    def id(self):
-        NQ, H, Hkv, N = self.shape
-        return f"{self.plan}{self.tag}-D{self.D}-{self.kt}-q{NQ}h{H}kv{Hkv}n{N}"
-
-    @property
-    def rk2(self):
-        return self.shape[1] // self.shape[2]
-
-
-MQ = ((fattn.OPT_MQ_MIN_ROWS, 32), (fattn.OPT_BD, 1))
-BD, BDP = ((fattn.OPT_BD, 2),), ((fattn.OPT_BD, 3),)
-PF1 = ((fattn.OPT_PF, 2), (fattn.OPT_PF_FORM, 1))
-PF4 = ((fattn.OPT_PF, 2),)
-STAGED = "kv_stage_f16<q8_0> + pf_mask_flags] + "
-
-SPECS = [
-    Spec("split_row", "fattn_split_kernel<", 128, "q8_0", (1, 4, 4, 256)),
-    Spec("split_row", "fattn_split_kernel<", 128, "f16", (1, 4, 4, 256)),
-    Spec("split_row_tail", "fattn_split_kernel<", 128, "q8_0", (1, 4, 4, 200)),
-    Spec("split_chunks", "fattn_split_kernel<", 128, "q8_0", (2, 8, 4, 1500), kv_chunk=256),
-    Spec("split_gqa_merge", "fattn_split_kernel<", 128, "q8_0", (3, 8, 2, 800), kv_chunk=256),
-    Spec("split_d80", "fattn_split_kernel<", 80, "f16", (9, 8, 2, 300)),
-    Spec("mq", "fattn_mq_kernel<", 128, "q8_0", (40, 16, 4, 320), MQ),
-    Spec("mq", "fattn_mq_kernel<q8_0,D256,4waves", 256, "q8_0", (50, 2, 2, 320), MQ),
-    Spec("bd", "fattn_bd_kernel<", 128, "f16", (40, 2, 2, 800), BD),
-    Spec("bd", "fattn_bd_kernel<", 128, "q8_0", (40, 2, 2, 800), BD),
-    Spec("bdp", "fattn_bdp_kernel<", 64, "q8_0", (64, 2, 2, 320), BDP),
-    Spec("bdp", "fattn_bdp_kernel<", 128, "q8_0", (64, 2, 2, 320), BDP),
-    Spec("pf", "fattn_pf_kernel<f16,D128", 128, "f16", (300, 2, 2, 384), PF1),
-    Spec("pf", STAGED + "fattn_pf_kernel<f16,D128", 128, "q8_0", (300, 2, 2, 384), PF1, tag="_staged"),
-    Spec("pf", "fattn_pf_kernel<q8_0,D128", 128, "q8_0", (300, 2, 2, 384), PF1 + ((fattn.OPT_PF_STAGE, 1),),
-         tag="_inkernel"),
-    Spec("pf4", "fattn_pf4_kernel(lean)<f16,D128", 128, "f16", (300, 2, 2, 384), PF4),
-    Spec("pf4", STAGED + "fattn_pf4_kernel(lean)<f16,D128", 128, "q8_0", (300, 2, 2, 384), PF4, tag="_staged"),
-]
 BY_ID = {s.id: s for s in SPECS}
 # the same plans with two q heads per kv head: the rows a 64- / 256-row tile
 # packs alternate between two heads, so between two head planes
@@ -130,11 +81,7 @@ def _run(spec, pp, dev, want_kernel=True, gran4=False):
 def _check(tag, spec, pp, d, got):
     ref = pp.oracle()
     assert not np.isnan(ref).any()                        # (position 0 is visible in every plane)
-    e_or, e_el = attn_rel_err(got, ref), attn_elem_err(got, ref)
-    line = f"PLANES {spec.id} {tag}: gpu->oracle {e_or:.3e} elem {e_el:.3f} | {d.split(' grid(')[0]}"
-    print(line)
-    assert e_or <= RTOL, line
-    assert e_el <= 1.0, line
+    check_bars(got, ref, lambda e_or, e_el: f"PLANES {spec.id} {tag}: gpu->oracle {e_or:.3e} elem {e_el:.3f} | {d.split(' grid(')[0]}")
 
 
 # ------------------------------------------------------------------ sequence planes
@@ -286,9 +233,7 @@ def test_prefill_ranges_follow_the_plane(dev, spec, order):
     assert not np.isnan(got).any()
     ref = pp.oracle()
     assert np.isnan(ref[bi]).all() and not np.isnan(ref[ci]).any()                 # (the quirk, as documented above)
-    e_or, e_el = attn_rel_err(got[ci], ref[ci]), attn_elem_err(got[ci], ref[ci])
-    print(f"PLANES {spec.id} {order} causal sequence: gpu->oracle {e_or:.3e} elem {e_el:.3f}")
-    assert e_or <= RTOL and e_el <= 1.0, (e_or, e_el)
+    check_bars(got[ci], ref[ci], lambda e_or, e_el: f"PLANES {spec.id} {order} causal sequence: gpu->oracle {e_or:.3e} elem {e_el:.3f}")
     # ---- (2)
     causal, band = _range_planes(p, keep0=True)
     pl[ci], pl[bi] = causal, band

@@ -12,21 +12,17 @@ rows x 16 heads over two tiles), two row tiles per kv head (128 heads), several
 chunks with a one-tile last chunk (416 keys in chunks of 128), N no multiple of
 32 (173), and a prefill-sized n_q (96 rows x 16 heads = 24 tiles).
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import mla
 import op_params as op
+from gpu_util import WS_TAIL_BYTES, graph_replay, run_kernel_test
 from mla import Shape
 from problems import attn_elem_err, attn_rel_err, make_problem
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
 RTOL = 1e-3
 
 DECODE = Shape(16, 1, 1, 160)
@@ -34,7 +30,7 @@ CHUNKED = Shape(16, 1, 1, 416)       # kv_chunk = 128: 4 chunks, the last of one
 ROWS5 = Shape(16, 1, 5, 224)
 
 
-def check(g: mla.MlaGpu, ref: np.ndarray, tag: str, plan: str = ""):
+def check(g, ref: np.ndarray, tag: str, plan: str = ""):
     d = g.describe()
     assert "fattn_mla_kernel" in d and plan in d, d
     got = g.run()
@@ -157,7 +153,7 @@ def test_shared_workspace_after_d128_decode(dev):
     probe = mla.MlaGpu(c, kv_chunk=128, dev=dev)
     assert g128.ws_bytes > 0 and probe.ws_bytes > 0
     n = max(g128.ws_bytes, probe.ws_bytes)
-    ws = torch.full(((n + 3) // 4 + views.WS_TAIL_BYTES // 4,), -1, dtype=torch.int32, device=dev)   # 0xFF bytes
+    ws = torch.full(((n + 3) // 4 + WS_TAIL_BYTES // 4,), -1, dtype=torch.int32, device=dev)   # 0xFF bytes
     rc = fattn.lib().fattn_workspace_init(ws.data_ptr(), n, torch.cuda.current_stream().cuda_stream)
     assert rc == 0
     g128.p.workspace, g128.p.workspace_bytes = ws.data_ptr(), n
@@ -172,23 +168,9 @@ def test_shared_workspace_after_d128_decode(dev):
 
 
 def test_graph_capture_replays_identically(dev):
-    import torch
     c, ref = mla.cached(CHUNKED, "random")
     g = mla.MlaGpu(c, kv_chunk=128, dev=dev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        g.launch()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=s):
-        g.launch()
-    outs = []
-    for _ in range(2):
-        g.dst.fill_(float("nan"))
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-        outs.append(g.dst.cpu().numpy().copy())
+    _, outs = graph_replay(g.launch, g.dst)
     assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
     assert attn_rel_err(outs[0].reshape(ref.shape), ref) <= RTOL
     assert g.guards_intact()
@@ -196,8 +178,7 @@ def test_graph_capture_replays_identically(dev):
 
 @pytest.mark.parametrize("v_off", [0, 64])
 def test_kernel_test_harness(dev, v_off):
-    r = subprocess.run([HARNESS, "--mla", "--v-off", str(v_off), "--heads", "16", "--kv-size", "416", "--n-q", "2",
-                        "--iters", "3"], capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--mla", "--v-off", v_off, "--heads", "16", "--kv-size", "416", "--n-q", "2", "--iters", "3"])
     print(r.stdout[-600:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "PASS" in r.stdout

@@ -21,22 +21,18 @@ or a base at +4); and solo with whole tiles in 16-B pieces (contiguous rows, 16-
 aligned base: the decode and chunked cases, whose N = 173 / 416 also run the
 dword pieces of a part-filled last tile).
 """
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import mla
 import mla_quant as mq
 import op_params as op
+from gpu_util import WS_TAIL_BYTES, graph_replay, run_kernel_test
 from mla import DK, Shape
 from problems import attn_elem_err, attn_rel_err, make_problem
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
 RTOL = 1e-3
 TYPS = ("q8_0", "q4_0")
 
@@ -196,7 +192,7 @@ def test_shared_workspace_after_d128_decode(dev, typ):
     probe = mq.QGpu(c, kv_chunk=128, dev=dev)
     assert g128.ws_bytes > 0 and probe.ws_bytes > 0
     n = max(g128.ws_bytes, probe.ws_bytes)
-    ws = torch.full(((n + 3) // 4 + views.WS_TAIL_BYTES // 4,), -1, dtype=torch.int32, device=dev)   # 0xFF bytes
+    ws = torch.full(((n + 3) // 4 + WS_TAIL_BYTES // 4,), -1, dtype=torch.int32, device=dev)   # 0xFF bytes
     assert fattn.lib().fattn_workspace_init(ws.data_ptr(), n, torch.cuda.current_stream().cuda_stream) == 0
     g128.p.workspace, g128.p.workspace_bytes = ws.data_ptr(), n
     g = mq.QGpu(c, kv_chunk=128, dev=dev, ws=ws)
@@ -212,23 +208,9 @@ def test_shared_workspace_after_d128_decode(dev, typ):
 
 @pytest.mark.parametrize("typ", TYPS)
 def test_graph_capture_replays_identically(dev, typ):
-    import torch
     c, ref = mq.cached(CHUNKED, typ, "random")
     g = mq.QGpu(c, kv_chunk=128, dev=dev)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        g.launch()
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=s):
-        g.launch()
-    outs = []
-    for _ in range(2):
-        g.dst.fill_(float("nan"))
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-        outs.append(g.dst.cpu().numpy().copy())
+    _, outs = graph_replay(g.launch, g.dst)
     assert np.array_equal(bits(outs[0]), bits(outs[1]))
     assert attn_rel_err(outs[0].reshape(ref.shape), ref) <= RTOL
     assert np.array_equal(bits(outs[0].reshape(ref.shape)), bits(mq.QGpu(c, "f16", kv_chunk=128, dev=dev).run()))
@@ -273,8 +255,7 @@ def test_set_rows_then_attention(dev):
 @pytest.mark.parametrize("typ", TYPS)
 @pytest.mark.parametrize("v_off", [0, 64])
 def test_kernel_test_harness(dev, typ, v_off):
-    r = subprocess.run([HARNESS, "--mla", "--kv-type", typ, "--v-off", str(v_off), "--heads", "16", "--kv-size", "416", "--n-q", "2",
-                        "--iters", "3"], capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--mla", "--kv-type", typ, "--v-off", v_off, "--heads", "16", "--kv-size", "416", "--n-q", "2", "--iters", "3"])
     print(r.stdout[-600:])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "PASS" in r.stdout

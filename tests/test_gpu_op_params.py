@@ -1,7 +1,6 @@
 """GPU: ggml's max_bias (ALiBi) and logit_softcap on every plan.
 
-One case per plan at its smallest shape -- the rows of
-tests/test_gpu_mask_planes.py's table with the same forcing options, plus one
+One case per plan at its smallest shape -- tests/plans.py's table, with one
 dword-path (gran4) split case and one mixed K / V pair -- each under
 
   alibi      max_bias 8 over the integer distance mask (-inf past the causal
@@ -12,139 +11,40 @@ dword-path (gran4) split case and one mixed K / V pair -- each under
   both       scale 1.0, cap 4, max_bias 8, distance mask (one spec per kernel)
 
 against the reference assembled from the frozen oracle's primitives
-(tests/op_params.py), at the suite's own bound: attn_rel_err <= 1e-3 and
-attn_elem_err <= 1, NaN positions coinciding.  Before a launch the case asserts
+(tests/op_params.py; tests/op_cases.py computes each once), at the suite's own
+bound: attn_rel_err <= 1e-3 and attn_elem_err <= 1, NaN positions coinciding.  Before a launch the case asserts
 on the CPU that the parameters move the reference by >= 5e-2 (50 x the bound):
 a kernel that ignored them could not pass.  Launches go through views.GpuView
 (dst guard bands, the exactly-sized workspace's sentinel).  Every case prints
 one OPPARAMS line with its errors.
 """
-from dataclasses import dataclass
-
 import numpy as np
 import pytest
 
-import fattn
 import mask_planes as mp
 import op_params as op
 import views
 from fattn import shard
-from problems import attn_elem_err, attn_rel_err, make_problem
+from gpu_util import check_bars
+from op_cases import launch as _launch, plane as _plane, premultiplied_oracle, problem as _problem, reference as _reference
+from plans import BD, FAMILIES, IDENT, OP_BY_ID as BY_ID, OP_SPECS as SPECS, PF1, SHARD, Spec
+from problems import attn_rel_err, make_problem
 
 pytestmark = pytest.mark.gpu
-RTOL = 1e-3
 MOVES = 5e-2
 
-
-@dataclass(frozen=True)
-class Spec:
-    plan: str
-    kernel: str               # what describe() must name with the parameters live
-    D: int
-    kt: str
-    shape: tuple              # (NQ, H, Hkv, N)
-    opts: tuple = ()
-    kv_chunk: int = 0
-    tag: str = ""
-    vt: str = ""              # V type when it differs from K's
-    variants: tuple = ()
-
-    @property
-    def id(self):
-        NQ, H, Hkv, N = self.shape
-        return f"{self.plan}{self.tag}-D{self.D}-{self.kt}-q{NQ}h{H}kv{Hkv}n{N}"
-
-
-MQ = ((fattn.OPT_MQ_MIN_ROWS, 32), (fattn.OPT_BD, 1))
-BD, BDP = ((fattn.OPT_BD, 2),), ((fattn.OPT_BD, 3),)
-PF1 = ((fattn.OPT_PF, 2), (fattn.OPT_PF_FORM, 1))
-PF4 = ((fattn.OPT_PF, 2),)
-STAGED = "kv_stage_f16<q8_0> + pf_mask_flags] + "
-
-SPECS = [
-    Spec("split_row", "fattn_split_kernel<", 128, "q8_0", (1, 4, 4, 256)),
-    Spec("split_row", "fattn_split_kernel<", 128, "f16", (1, 4, 4, 256)),
-    Spec("split_row_tail", "fattn_split_kernel<", 128, "q8_0", (1, 4, 4, 200)),
-    Spec("split_chunks", "fattn_split_kernel<", 128, "q8_0", (2, 8, 4, 1500), kv_chunk=256),
-    Spec("split_gqa_merge", "fattn_split_kernel<", 128, "q8_0", (3, 8, 2, 800), kv_chunk=256),
-    Spec("split_d80", "fattn_split_kernel<", 80, "f16", (9, 8, 2, 300)),
-    Spec("mq", "fattn_mq_kernel<", 128, "q8_0", (40, 16, 4, 320), MQ),
-    Spec("mq", "fattn_mq_kernel<q8_0,D256,4waves", 256, "q8_0", (50, 2, 2, 320), MQ),
-    Spec("bd", "fattn_bd_kernel<", 128, "f16", (40, 2, 2, 800), BD),
-    Spec("bd", "fattn_bd_kernel<", 128, "q8_0", (40, 2, 2, 800), BD),
-    Spec("bdp", "fattn_bdp_kernel<", 64, "q8_0", (64, 2, 2, 320), BDP),
-    Spec("bdp", "fattn_bdp_kernel<", 128, "q8_0", (64, 2, 2, 320), BDP),
-    Spec("pf", "fattn_pf_kernel<f16,D128", 128, "f16", (300, 2, 2, 384), PF1),
-    Spec("pf", STAGED + "fattn_pf_kernel<f16,D128", 128, "q8_0", (300, 2, 2, 384), PF1, tag="_staged"),
-    Spec("pf", "fattn_pf_kernel<q8_0,D128", 128, "q8_0", (300, 2, 2, 384), PF1 + ((fattn.OPT_PF_STAGE, 1),),
-         tag="_inkernel"),
-    # the shape and options that take fattn_pf4_kernel(lean) with both parameters off
-    Spec("pf4shape", "fattn_pf_kernel<f16,D128", 128, "f16", (300, 2, 2, 384), PF4),
-    Spec("split_gran4", ",gran4,", 128, "q8_0", (1, 4, 4, 256), variants=("kv_offset4",)),
-    Spec("split_mixed", "fattn_split_kernel<q8_0,f16,D128", 128, "q8_0", (1, 4, 4, 256), vt="f16"),
-]
-BY_ID = {s.id: s for s in SPECS}
 # irrational slopes (H = 12: n2 = 8, heads 8 .. 11 from the formula's second branch), three q heads per kv head
 GQA12 = [
     Spec("split_gqa_merge", "fattn_split_kernel<", 128, "q8_0", (3, 12, 4, 800), kv_chunk=256, tag="_h12"),
     Spec("bd", "fattn_bd_kernel<", 128, "f16", (40, 12, 4, 800), BD, tag="_h12"),
     Spec("pf", "fattn_pf_kernel<f16,D128", 128, "f16", (90, 12, 4, 384), PF1, tag="_h12"),   # (two 85-query tiles)
 ]
-FAMILIES = [BY_ID[i] for i in ("split_gqa_merge-D128-q8_0-q3h8kv2n800", "mq-D128-q8_0-q40h16kv4n320",
-                               "bd-D128-q8_0-q40h2kv2n800", "bdp-D128-q8_0-q64h2kv2n320",
-                               "pf_staged-D128-q8_0-q300h2kv2n384")]
 EXACT_H = (1, 2, 4, 8, 6)     # head counts whose slopes at max_bias 8 are all powers of two
-
-_cache = {}
-
-
-def _problem(spec, scale=None):
-    key = ("p", spec.id, scale)
-    if key not in _cache:
-        NQ, H, Hkv, N = spec.shape
-        _cache[key] = make_problem(D=spec.D, NQ=NQ, H=H, Hkv=Hkv, N=N, kv_type=spec.kt, v_type=spec.vt or None,
-                                   mask="none", seed=500 + len(_cache), scale=scale)
-    return _cache[key]
-
-
-def _plane(spec, kind):
-    NQ, _, _, N = spec.shape
-    if kind == "none":
-        return None
-    key = ("m", kind, NQ, N)
-    if key not in _cache:
-        _cache[key] = op.distance_mask(NQ, N) if kind == "distance" else op.random_mask(NQ, N)
-    return _cache[key]
-
-
-def _reference(spec, scale, kind, **kw):
-    """The assembled reference of (spec, scale, mask kind, parameters), computed once."""
-    key = ("r", spec.id, scale, kind, tuple(sorted(kw.items())))
-    if key not in _cache:
-        _cache[key] = op.one_plane(_problem(spec, scale), _plane(spec, kind), spec.variants, **kw).reference()
-    return _cache[key]
-
-
-def _launch(spec, vp, dev, nomask=False, kernel=None):
-    """vp under spec's options through views.GpuView: (describe, output)."""
-    with fattn.options(dict(spec.opts)):
-        g = views.GpuView(vp, dev, spec.kv_chunk)
-        d = g.describe()
-        want = spec.kernel if kernel is None else kernel
-        if nomask:
-            want = want.replace(" + pf_mask_flags", "")
-        assert want in d, d
-        got = g.run()
-    assert g.guards_intact(), d
-    return d, got
 
 
 def _check(tag, spec, d, got, ref, what="assembled"):
-    e_or, e_el = attn_rel_err(got, ref), attn_elem_err(got, ref)
-    line = f"OPPARAMS {spec.id} {tag}: gpu->{what} {e_or:.3e} elem {e_el:.3f} | {d.split(' grid(')[0]}{d[d.index(' ws '):]}"
-    print(line)
-    assert e_or <= RTOL, line
-    assert e_el <= 1.0, line
+    check_bars(got, ref, lambda e_or, e_el: f"OPPARAMS {spec.id} {tag}: gpu->{what} {e_or:.3e} elem {e_el:.3f} | "
+                                            f"{d.split(' grid(')[0]}{d[d.index(' ws '):]}")
 
 
 def _case(spec, dev, tag, scale, kind, **kw):
@@ -171,10 +71,7 @@ def test_alibi(dev, spec):
     d, got = _case(spec, dev, "alibi", None, "distance", max_bias=8.0)
     if spec.shape[1] in EXACT_H:
         # slope * mask exact in f16: the frozen oracle over H pre-multiplied head planes
-        key = ("pre", spec.id)
-        if key not in _cache:
-            _cache[key] = op.premultiplied_planes(_problem(spec), _plane(spec, "distance"), 8.0).oracle()
-        _check("alibi", spec, d, got, _cache[key], what="oracle(premultiplied planes)")
+        _check("alibi", spec, d, got, premultiplied_oracle(spec), what="oracle(premultiplied planes)")
 
 
 @pytest.mark.parametrize("spec", GQA12, ids=[s.id for s in GQA12])
@@ -218,9 +115,6 @@ def test_head_planes_under_max_bias(dev, spec):
     _check(f"planes x alibi (moves {moved:.2g})", spec, d, got, ref)
 
 
-SHARD = Spec("shard", "fattn_split_kernel<", 128, "q8_0", (2, 8, 4, 512))
-
-
 @pytest.mark.parametrize("world", [2, 4])
 def test_head_shards_take_the_global_slopes(dev, world):
     """H = 8, Hkv = 4 over 2 and 4 ranks, every rank's slice launched on this
@@ -244,10 +138,6 @@ def test_head_shards_take_the_global_slopes(dev, world):
         wrong.append(op.one_plane(sub, dist, max_bias=8.0).reference())
     assert attn_rel_err(np.concatenate(wrong, axis=2), full) > MOVES
     _check(f"world {world}", SHARD, d, np.concatenate(parts, axis=2), full)
-
-
-IDENT = [BY_ID[i] for i in ("split_row-D128-q8_0-q1h4kv4n256", "mq-D128-q8_0-q40h16kv4n320", "bd-D128-f16-q40h2kv2n800",
-                            "pf4shape-D128-f16-q300h2kv2n384")]
 
 
 @pytest.mark.parametrize("spec", IDENT, ids=[s.id for s in IDENT])

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 import fattn
-from gpu_util import run_gpu, upload, views
+from gpu_util import graph_replay, run_gpu, upload, views
 from oracle import oracle as orc
 from problems import attn_elem_err, attn_rel_err, make_problem
 
@@ -1140,21 +1140,11 @@ def test_ext_f16_launch_positional(dev):
 
 def test_graph_capture(dev):
     """The launch path allocates nothing and does not sync: capturable into a HIP graph."""
-    import torch
     p = make_problem(D=128, NQ=1, H=32, N=4096, kv_type="q8_0", seed=13)
     t = upload(p, dev)
     att = fattn.Attention(*views(p, t), t["dst"], p.scale)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        att(s.cuda_stream)
-    torch.cuda.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        att(s.cuda_stream)
-    t["dst"].fill_(float("nan"))
-    g.replay()
-    torch.cuda.synchronize()
-    assert attn_rel_err(t["dst"].cpu().numpy(), p.oracle()) <= RTOL
+    _, (out,) = graph_replay(att, t["dst"], replays=1)
+    assert attn_rel_err(out, p.oracle()) <= RTOL
 
 
 @pytest.mark.parametrize("hkv", [8, 32], ids=["gqa4-workgroup-merge", "mha-wave-merge"])

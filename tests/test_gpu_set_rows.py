@@ -6,15 +6,13 @@ allocation (at least one slot's bytes of guard around every plane) and the
 WHOLE allocation is compared: a missing bounds check, a truncated index or a
 store past a row shows as changed guard bytes or a changed slot."""
 import functools
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import fattn
 import set_rows as sr
-from gpu_util import upload, views as gpu_views
+from gpu_util import capture, run_kernel_test, upload, views as gpu_views
 from oracle import oracle as orc
 from problems import Problem, attn_elem_err, attn_rel_err
 
@@ -190,15 +188,9 @@ def test_graph_replay_reads_new_slots(dev, name):
     sv = fattn.View(d_src.data_ptr(), fattn.TYPE_F32, (ne0, nr, ne2, 1), sr.place_src(a)[2])
     iv = fattn.View(d_idx.data_ptr(), fattn.TYPE_I64, (nr, 1, 1, 1), (8, 8 * nr, 8 * nr, 8 * nr))
     dv = fattn.View(d_cache.data_ptr() + off, typ, (ne0, n_slots, ne2, 1), nb)
-    s = torch.cuda.Stream()
-    with torch.cuda.stream(s):
-        fattn.set_rows(sv, iv, dv, s.cuda_stream)
-    torch.cuda.synchronize()
+    g = capture(lambda stream: fattn.set_rows(sv, iv, dv, stream))
     want = sr.set_rows_ref(cache, a, ia, typ, n_slots, off, nb)
-    _assert_same(d_cache.cpu().numpy(), want, "eager")
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=s):
-        fattn.set_rows(sv, iv, dv, s.cuda_stream)
+    _assert_same(d_cache.cpu().numpy(), want, "eager")       # (capturing launched nothing: the eager launch's rows)
     d_src.copy_(_dev(b, dev))
     d_idx.copy_(_dev(ib.reshape(-1), dev))
     torch.cuda.synchronize()
@@ -270,10 +262,6 @@ def test_end_to_end_decode(dev, name):
 def test_harness_set_rows():
     """kernel_test --set-rows --kv-type q5_1: the caches written by fattn_set_rows
     through a seeded slot permutation; its own max-diff check."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = os.path.join(root, "ggml-cuda-experiments_amd", "bin", "kernel_test")
-    if not os.path.exists(exe):
-        pytest.fail(f"{exe} not built (make harness)")
-    r = subprocess.run([exe, "--iters", "3", "--set-rows", "--kv-type", "q5_1"], capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--iters", "3", "--set-rows", "--kv-type", "q5_1"])
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS" in r.stdout

@@ -4,7 +4,7 @@ plan and at every site that normalises into dst.
 The sink enters once per output row, in the epilogue (include/fattn.h,
 DESIGN.md section 12); a miss at one of the sites is silent wrong output, so
 
-  every plan   the rows of tests/test_gpu_op_params.py's table with their
+  every plan   the rows of tests/plans.py's OP_SPECS with their
                forcing options, under a random mask and no mask (the pf rows
                also under the causal distance mask)
   every site   SITES maps each normalising site to the case that reaches it and
@@ -25,8 +25,8 @@ sinks there are none).  Sinks are ln N + linspace(-2, 3, H) under a fixed
 non-monotonic permutation of the heads; before a launch the case asserts on
 the CPU that they move the reference of EVERY head by >= 5e-2 (MOVES), so a
 kernel that ignored them, or took another head's, could not pass.  Launches go
-through sinks.SinkGpuView (views.GpuView's dst guard bands and workspace
-sentinel).  Every case prints one SINKS line with its errors
+through sinks.SinkGpuView (gpu_util.GuardedLaunch's dst guard bands and
+workspace sentinel).  Every case prints one SINKS line with its errors
 (profiles/sinks/errors.txt).  No case runs under FATTN_OPT_MERGE_IN_KERNEL
 (it may return OK with NaN rows by its own documentation, and waits on other
 workgroups); it takes sinks through merge_row_parts like the merge kernels.
@@ -37,14 +37,17 @@ import numpy as np
 import pytest
 
 import fattn
+import op_cases as t
 import op_params as op
 import sinks as sk
-import test_gpu_op_params as t
+import views
 from fattn import shard
-from problems import attn_elem_err, attn_rel_err, make_problem
-from test_gpu_op_params import BD, BY_ID, FAMILIES, IDENT, MOVES, MQ, RTOL, SHARD, SPECS, Spec
+from gpu_util import check_bars
+from plans import BD, FAMILIES, IDENT, MQ, OP_BY_ID as BY_ID, OP_SPECS as SPECS, SHARD, Spec
+from problems import attn_rel_err, make_problem
 
 pytestmark = pytest.mark.gpu
+MOVES = 5e-2
 
 _cache = {}
 
@@ -62,18 +65,18 @@ def off_kernel(spec):
 
 
 def _op(spec, kind, scale=None, **kw):
-    plane = kind if isinstance(kind, np.ndarray) else t._plane(spec, kind)
-    return op.one_plane(t._problem(spec, scale), plane, spec.variants, **kw)
+    plane = kind if isinstance(kind, np.ndarray) else t.plane(spec, kind)
+    return op.one_plane(t.problem(spec, scale), plane, spec.variants, **kw)
 
 
 def _plain(spec, kind, scale=None, **kw):
-    """op_params.reference without sinks: the cache of tests/test_gpu_op_params.py (computed once per session)."""
+    """op_params.reference without sinks: the cache of tests/op_cases.py (computed once per session)."""
     if isinstance(kind, np.ndarray):
         key = ("plain", spec.id, scale, kind.tobytes(), tuple(sorted(kw.items())))
         if key not in _cache:
             _cache[key] = _op(spec, kind, scale, **kw).reference()
         return _cache[key]
-    return t._reference(spec, scale, kind, **kw)
+    return t.reference(spec, scale, kind, **kw)
 
 
 def _ref(spec, kind, sinks, scale=None, **kw):
@@ -92,26 +95,23 @@ def moves_every_head(ref, plain):
 
 def _launch(spec, sp, dev, want, absent=(), null=False):
     with fattn.options(dict(spec.opts)):
-        g = sk.SinkGpuView(sp, dev, spec.kv_chunk, null=null)
+        g = views.GpuView(sp, dev, spec.kv_chunk) if null else sk.SinkGpuView(sp, dev, spec.kv_chunk)
         d = g.describe()
         for w in (want,) if isinstance(want, str) else want:
             assert w in d, (w, d)
         for w in absent:
             assert w not in d, (w, d)
         assert "sink" not in d, d
-        got = g.run()
+        got = sk.run_null_sinks(g) if null else g.run()
     assert g.guards_intact(), d
     return d, got
 
 
 def _check(tag, spec, d, got, ref):
     assert not np.isnan(ref).any()
-    e_or, e_el = attn_rel_err(got, ref), attn_elem_err(got, ref)
-    line = f"SINKS {spec.id} {tag}: gpu->factor-form {e_or:.3e} elem {e_el:.3f} | {d.split(' grid(')[0]}{d[d.index(' ws '):]}"
-    print(line)
-    assert not np.isnan(got).any(), line
-    assert e_or <= RTOL, line
-    assert e_el <= 1.0, line
+    check_bars(got, ref, lambda e_or, e_el: f"SINKS {spec.id} {tag}: gpu->factor-form {e_or:.3e} elem {e_el:.3f} | "
+                                            f"{d.split(' grid(')[0]}{d[d.index(' ws '):]}")
+    assert not np.isnan(got).any(), (spec.id, tag)
 
 
 def _kernel_for(spec, kind, live=False):
@@ -248,7 +248,7 @@ def test_null_sinks_is_fattn_ext(dev, spec):
     """fattn_ext_sinks(p, NULL) and fattn_ext(p): the same bits."""
     for kind in ("random", "none"):
         o = _op(spec, kind)
-        d0, out0 = t._launch(spec, o, dev, nomask=kind == "none", kernel=off_kernel(spec))
+        d0, out0 = t.launch(spec, o, dev, nomask=kind == "none", kernel=off_kernel(spec))
         d1, out1 = _launch(spec, o, dev, _kernel_for(spec, kind), null=True)
         assert d1 == d0
         assert np.array_equal(out1.view(np.uint32), out0.view(np.uint32)), (spec.id, kind)
@@ -285,7 +285,7 @@ def test_fully_masked_rows_are_zero(dev, spec):
     d, got = _launch(spec, sk.with_sinks(o, s), dev, off_kernel(spec))
     assert (got[:, 0] == 0.0).all(), got[:, 0]
     _check("row 0 masked", spec, d, got, ref)
-    d0, got0 = t._launch(spec, o, dev, kernel=off_kernel(spec))
+    d0, got0 = t.launch(spec, o, dev, kernel=off_kernel(spec))
     assert d0 == d
     assert np.isnan(got0[:, 0]).all() and not np.isnan(got0[:, 1:]).any()
 
@@ -335,8 +335,8 @@ def test_head_shards_take_their_slice(dev, world):
     with sink_slice: assembled, the unsharded reference.  The unsliced
     sinks[:H_slice] would be wrong by more than MOVES (CPU)."""
     NQ, H, Hkv, N = SHARD.shape
-    p = t._problem(SHARD)
-    m = t._plane(SHARD, "random")
+    p = t.problem(SHARD)
+    m = t.plane(SHARD, "random")
     s = sink_values(H, N)
     full = _ref(SHARD, "random", s)
     assert moves_every_head(full, _plain(SHARD, "random")) >= MOVES

@@ -30,7 +30,7 @@ import fattn
 import op_params as op
 import sinks as sk
 import views
-from gpu_util import upload
+from gpu_util import check_bars, upload
 from gpu_util import views as tensor_views
 from problems import attn_elem_err, attn_rel_err, make_problem
 
@@ -113,10 +113,7 @@ def _launch(prob, opts, want, chunks, dev, seed=71, launches=1):
 
 
 def _check(tag, d, got, ref):
-    e_or, e_el = attn_rel_err(got, ref), attn_elem_err(got, ref)
-    print(f"COLPACK {tag}: rel {e_or:.3e} elem {e_el:.3f} | {d.split(' lds ')[0]}")
-    assert e_or <= RTOL, (tag, e_or, d)
-    assert e_el <= 1.0, (tag, e_el, d)
+    check_bars(got, ref, lambda e_or, e_el: f"COLPACK {tag}: rel {e_or:.3e} elem {e_el:.3f} | {d.split(' lds ')[0]}")
 
 
 @pytest.mark.parametrize("prob,opts,want,chunks", _cases())

@@ -18,13 +18,12 @@ the tensors are addressed (tests/views.py) or the scale, then
 Scale cases also compare with the float64 reference (views.exact_f64) at the
 same 1e-3 and print both distances (the table of DESIGN.md section 5).
 """
-from dataclasses import dataclass
-
 import numpy as np
 import pytest
 
 import fattn
 import views
+from plans import Spec
 from problems import attn_elem_err, attn_rel_err, make_problem
 
 pytestmark = pytest.mark.gpu
@@ -33,33 +32,6 @@ RTOL = 1e-3
 QUANT = ("q8_0", "q4_0")
 ALL3 = ("f16", "q8_0", "q4_0")
 Q_ALL = ("q_headmajor", "q_rowpad", "q_offset")
-
-
-@dataclass(frozen=True)
-class Spec:
-    plan: str                 # row of the plan table
-    kernel: str               # what describe() must name on a 16-B-aligned view
-    D: int
-    kt: str
-    shape: tuple              # (NQ, H, Hkv, N)
-    opts: tuple = ()          # ((option, value), ...)
-    kv_chunk: int = 0
-    mask: str = "random"
-    tag: str = ""             # distinguishes two specs of one plan / D / type
-
-    @property
-    def id(self):
-        NQ, H, Hkv, N = self.shape
-        return f"{self.plan}{self.tag}-D{self.D}-{self.kt}-q{NQ}h{H}kv{Hkv}n{N}"
-
-    @property
-    def row(self):
-        return self.plan + (f"_d{self.D}" if (self.plan, self.D) in (("mq", 256), ("pf", 80)) else "") + \
-            ("_maskbody" if self.mask != "random" else "")
-
-    @property
-    def family(self):
-        return self.plan.split("_")[0]      # split | mq | bd | bdp | pf | pf4
 
 
 def _specs():

@@ -9,19 +9,13 @@ the same srand(1) inputs -- which pins the harness's CPU reference
 GPU: both of its branches run and pass their own max-diff check.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
-GOLDEN = os.path.join(ROOT, "tests", "golden")
+from gpu_util import run_kernel_test
 
-
-def _need_bin():
-    if not os.path.exists(BIN):
-        pytest.fail(f"{BIN} not built (make harness)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 @pytest.mark.parametrize("fixture,args", [
@@ -29,9 +23,8 @@ def _need_bin():
     ("kernel_test_default.npz", []),
 ])
 def test_cpu_only_matches_reference_bitexact(tmp_path, fixture, args):
-    _need_bin()
     out = tmp_path / "out.bin"
-    r = subprocess.run([BIN, "--cpu-only", "--dump", str(out)] + args, capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--cpu-only", "--dump", out] + args)
     assert r.returncode == 0, r.stderr
     got = np.fromfile(out, dtype=np.float32)
     ref = np.load(os.path.join(GOLDEN, fixture))["out"]
@@ -59,8 +52,7 @@ def test_cpu_only_matches_reference_bitexact(tmp_path, fixture, args):
     ["--config", "5", "--ngpu", "1"],                      # the --ngpu path (RCCL not needed at 1)
 ], ids=lambda a: "_".join(a) or "default")
 def test_harness_runs_on_gpu(dev, args):
-    _need_bin()
-    r = subprocess.run([BIN, "--iters", "3"] + args, capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--iters", "3"] + args)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "PASS" in r.stdout
 
@@ -71,18 +63,17 @@ def test_cpu_only_config_presets_and_n_q(tmp_path):
     writes three finite, distinct query rows (the rand() stream then fills Q,
     K, V and the mask rows in kernel_test.h's order, so K differs from the
     n_q = 1 run's)."""
-    _need_bin()
     out = tmp_path / "c1.bin"
-    r = subprocess.run([BIN, "--config", "1", "--dump", str(out)], capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--config", "1", "--dump", out])
     assert r.returncode == 0, r.stderr
     ref = np.load(os.path.join(GOLDEN, "kernel_test_cfg1.npz"))["out"]
     assert np.array_equal(np.fromfile(out, dtype=np.float32).view(np.uint32), ref.view(np.uint32))
-    r = subprocess.run([BIN, "--config", "9"], capture_output=True, text=True, timeout=60)
+    r = run_kernel_test(["--config", "9"], timeout=60)
     assert r.returncode == 2
     a, b = tmp_path / "a.bin", tmp_path / "b.bin"
-    base = [BIN, "--cpu-only", "--heads", "2", "--kv-heads", "1", "--head-dim", "64", "--kv-size", "96", "--mask", "zero"]
-    assert subprocess.run(base + ["--dump", str(a)], capture_output=True, timeout=60).returncode == 0
-    assert subprocess.run(base + ["--n-q", "3", "--dump", str(b)], capture_output=True, timeout=60).returncode == 0
+    base = ["--cpu-only", "--heads", "2", "--kv-heads", "1", "--head-dim", "64", "--kv-size", "96", "--mask", "zero"]
+    assert run_kernel_test(base + ["--dump", a], timeout=60).returncode == 0
+    assert run_kernel_test(base + ["--n-q", "3", "--dump", b], timeout=60).returncode == 0
     one, three = np.fromfile(a, dtype=np.float32), np.fromfile(b, dtype=np.float32)
     assert three.size == 3 * one.size and np.isfinite(three).all()
     rows = three.reshape(3, -1)

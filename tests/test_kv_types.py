@@ -9,7 +9,7 @@ import pytest
 
 import fattn
 import kv_types as kt
-from test_abi import _params
+from plans import plan_params as _params
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kv_types_kat.json")
 NAMES = ("q4_1", "q5_0", "q5_1")

@@ -4,18 +4,13 @@ plan as fattn_describe prints it, the workspace rule, the padded-V reference's
 identity with the oracle's primitives, the harness's CPU path, and the refusals
 that must stay as they were."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import fattn
 import mla
+from gpu_util import run_kernel_test
 from mla import DK, DV, Shape
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
 
 OK, INVALID, TYPE, HEAD_DIM, STRIDE, WORKSPACE, ALIGN = 0, -1, -2, -3, -4, -5, -7
 BASE = 1 << 24
@@ -233,15 +228,14 @@ def test_kernel_test_mla_cpu_only(tmp_path):
     outs = []
     for v_off in (0, 64):
         f = tmp_path / f"mla{v_off}.bin"
-        r = subprocess.run([HARNESS, "--mla", "--v-off", str(v_off), "--cpu-only", "--heads", "4", "--kv-size", "96", "--n-q", "2",
-                            "--dump", str(f)], capture_output=True, text=True, timeout=120)
+        r = run_kernel_test(["--mla", "--v-off", v_off, "--cpu-only", "--heads", "4", "--kv-size", "96", "--n-q", "2", "--dump", f])
         assert r.returncode == 0, r.stdout + r.stderr
         assert "Reference" in r.stdout
         o = np.fromfile(f, dtype=np.float32)
         assert o.shape == (2 * 4 * DV,) and np.isfinite(o).all()
         outs.append(o)
     assert not np.array_equal(outs[0], outs[1])   # another 512 of the 576 columns
-    r = subprocess.run([HARNESS, "--mla", "--v-off", "32", "--cpu-only"], capture_output=True, text=True, timeout=60)
+    r = run_kernel_test(["--mla", "--v-off", "32", "--cpu-only"], timeout=60)
     assert r.returncode == 2
 
 

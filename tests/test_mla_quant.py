@@ -4,19 +4,14 @@ the plan as fattn_describe prints it, the workspace rule against the f16 view
 plan, mla_v_view on quantised views, the test cache's own values and the
 harness's CPU path."""
 import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import fattn
 import mla
 import mla_quant as mq
+from gpu_util import run_kernel_test
 from mla import DK, DV, Shape
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HARNESS = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
 
 OK, INVALID, TYPE, HEAD_DIM, STRIDE, WORKSPACE, ALIGN = 0, -1, -2, -3, -4, -5, -7
 BASE = 1 << 24
@@ -250,8 +245,8 @@ def test_kernel_test_mla_quant_cpu_only(tmp_path, typ):
     outs = {}
     for v_off in (0, 32, 64):
         f = tmp_path / f"mla{v_off}.bin"
-        r = subprocess.run([HARNESS, "--mla", "--kv-type", typ, "--v-off", str(v_off), "--cpu-only", "--heads", "4", "--kv-size", "96",
-                            "--n-q", "2", "--dump", str(f)], capture_output=True, text=True, timeout=120)
+        r = run_kernel_test(["--mla", "--kv-type", typ, "--v-off", v_off, "--cpu-only", "--heads", "4", "--kv-size", "96", "--n-q", "2",
+                             "--dump", f])
         assert r.returncode == 0, r.stdout + r.stderr
         assert "Reference" in r.stdout
         o = np.fromfile(f, dtype=np.float32)
@@ -260,13 +255,12 @@ def test_kernel_test_mla_quant_cpu_only(tmp_path, typ):
     assert not np.array_equal(outs[0], outs[64]) and not np.array_equal(outs[32], outs[64])
     # the quantised cache's values are not the f16 cache's
     f = tmp_path / "mla_f16.bin"
-    r = subprocess.run([HARNESS, "--mla", "--v-off", "64", "--cpu-only", "--heads", "4", "--kv-size", "96", "--n-q", "2", "--dump", str(f)],
-                       capture_output=True, text=True, timeout=120)
+    r = run_kernel_test(["--mla", "--v-off", "64", "--cpu-only", "--heads", "4", "--kv-size", "96", "--n-q", "2", "--dump", f])
     assert r.returncode == 0
     o16 = np.fromfile(f, dtype=np.float32)
     assert not np.array_equal(o16, outs[64])
     assert np.abs(o16 - outs[64]).max() < (0.05 if typ == "q8_0" else 0.5)      # ... but close to them
     # --v-off 32 stays an f16 error, other offsets and types are refused
     for extra in (["--v-off", "32"], ["--kv-type", typ, "--v-off", "16"], ["--kv-type", "q5_0"]):
-        r = subprocess.run([HARNESS, "--mla", "--cpu-only"] + extra, capture_output=True, text=True, timeout=60)
+        r = run_kernel_test(["--mla", "--cpu-only"] + extra, timeout=60)
         assert r.returncode == 2, extra

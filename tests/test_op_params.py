@@ -5,7 +5,6 @@ planning, as in test_views.py), the shard helper and the kernel_test harness."""
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,11 +14,12 @@ import mask_planes as mp
 import op_params as op
 import views
 from fattn import shard
+from gpu_util import run_kernel_test
 from oracle import oracle as orc
+from plans import plan_params as _params
 from problems import attn_rel_err, make_problem
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "ggml-cuda-experiments_amd", "bin", "kernel_test")
 ERR_INVALID_ARG = -1
 
 
@@ -74,17 +74,6 @@ def test_reference_softcap_moves_the_output():
 
 
 # ------------------------------------------------------------------ ABI
-
-def _params(D=128, NQ=1, H=32, Hkv=32, N=4096, kt=fattn.TYPE_Q8_0, ptr=1 << 20, mask=True, **kw):
-    """tests/test_abi.py's _params: fake pointers, host-only planning."""
-    def view(t):
-        rb = fattn.row_size(t, D)
-        eb = 2 if t == fattn.TYPE_F16 else fattn.BLOCK_BYTES.get(t, 4)
-        return fattn.View(ptr, t, (D, N, Hkv, 1), (eb, rb, rb * N, rb * N * Hkv))
-    q = fattn.View(ptr, fattn.TYPE_F32, (D, NQ, H, 1), (4, H * D * 4, D * 4, NQ * H * D * 4))
-    m = fattn.View(ptr, fattn.TYPE_F16, (N, NQ, 1, 1), (2, N * 2, N * 2 * NQ, N * 2 * NQ)) if mask else None
-    return fattn.ext_params(q, view(kt), view(kt), m, ptr, 0.088, **kw)
-
 
 SHAPES = {"config3": dict(), "config5": dict(NQ=64), "prefill": dict(NQ=4096)}
 
@@ -247,15 +236,13 @@ def test_harness_cpu_reference_has_the_parameters(tmp_path):
     magnitude <= cap + |mask| (6e-7) through a softmax over 96 keys -- 1e-5 of
     a row's largest output is two orders above that and four below the
     feature's effect."""
-    if not os.path.exists(BIN):
-        pytest.fail(f"{BIN} not built (make harness)")
     H, Hkv, D, N, NQ = 6, 2, 64, 96, 2
-    base = [BIN, "--cpu-only", "--heads", str(H), "--kv-heads", str(Hkv), "--head-dim", str(D), "--kv-size", str(N),
+    base = ["--cpu-only", "--heads", str(H), "--kv-heads", str(Hkv), "--head-dim", str(D), "--kv-size", str(N),
             "--n-q", str(NQ)]
     outs = {}
     for tag, extra in (("on", ["--max-bias", "8", "--softcap", "4"]), ("off", [])):
         f = tmp_path / f"{tag}.bin"
-        r = subprocess.run(base + extra + ["--dump", str(f)], capture_output=True, text=True, timeout=120)
+        r = run_kernel_test(base + extra + ["--dump", f])
         assert r.returncode == 0, r.stderr
         outs[tag] = np.fromfile(f, dtype=np.float32).reshape(1, NQ, H, D)
     orc.srand(1)

@@ -19,22 +19,9 @@ import numpy as np
 import pytest
 
 from oracle import oracle as orc
-from problems import attn_rel_err
+from problems import attn_rel_err, oracle_of_dump as _oracle_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _oracle_of(d):
-    D, NQ, H, Hkv, N, typ, world = (int(x) for x in d["shape"])
-    rb = D // 32 * orc.BLOCK_BYTES[typ]
-    kv_nb = (orc.BLOCK_BYTES[typ], rb, rb * N, rb * N * Hkv)  # bench's "head" layout
-    q = np.ascontiguousarray(d["q"], dtype=np.float32)        # [1][NQ][H][D]
-    mask = np.ascontiguousarray(d["mask"])                   # [NQ][Npad] f16 bits
-    rows, npad = mask.shape
-    return orc.flash_attn_ext((q, orc.TYPE_F32, (D, NQ, H, 1), (4, H * D * 4, D * 4, NQ * H * D * 4)),
-                              (d["k"], typ, (D, N, Hkv, 1), kv_nb), (d["v"], typ, (D, N, Hkv, 1), kv_nb),
-                              (mask, orc.TYPE_F16, (npad, rows, 1, 1), (2, npad * 2, npad * rows * 2, npad * rows * 2)),
-                              float(np.float32(1.0 / D ** 0.5)), n_threads=16)
 
 
 def _rehearse(tmp_path, mode):

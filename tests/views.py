@@ -32,6 +32,7 @@ tensors.
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 from typing import Optional
 
@@ -39,7 +40,7 @@ import numpy as np
 from numpy.lib.stride_tricks import as_strided
 
 from oracle import oracle as orc
-from problems import Problem, row_bytes
+from problems import GUARD, Problem, place_rows, row_bytes, scatter as _scatter  # noqa: F401 (GUARD: this module's users)
 
 Q_VARIANTS = ("q_headmajor", "q_rowpad", "q_offset")
 MASK_VARIANTS = ("m_wide16", "m_rows", "m_cols", "m_align4", "m_stride4")
@@ -54,7 +55,6 @@ F32_NAN = np.uint32(0x7FC00000)
 F16_NAN = np.uint16(0x7E00)
 KV_POISON = np.uint8(0x7E)
 N_CTX_EXTRA = 96
-GUARD = 256          # poison bytes after every view
 FAKE_BASE = 1 << 20  # host-only planning: the allocation "address"
 
 
@@ -94,21 +94,6 @@ class ViewProblem:
         return fattn.ext_params(vw(self.q, "q"), vw(self.k, "k"), vw(self.v, "v"),
                                 vw(self.mask, "mask") if self.mask is not None else None,
                                 dst_ptr, self.scale, ws_ptr, ws_bytes, kv_chunk)
-
-
-def _scatter(rows: np.ndarray, nb, off: int, fill: np.ndarray) -> np.ndarray:
-    """rows [n3][n2][n1][row bytes] written at byte strides (nb3, nb2, nb1) from
-    `off` into a buffer pre-filled with `fill` (a 1-element array: the poison
-    pattern), GUARD bytes of poison after the last element."""
-    n3, n2, n1, rb = rows.shape
-    span = (n3 - 1) * nb[3] + (n2 - 1) * nb[2] + (n1 - 1) * nb[1] + rb
-    total = off + span + GUARD
-    unit = fill.dtype.itemsize
-    total = (total + unit - 1) // unit * unit
-    buf = np.full(total // unit, fill[0], dtype=fill.dtype).view(np.uint8)
-    dstv = as_strided(buf[off:], shape=rows.shape, strides=(nb[3], nb[2], nb[1], 1), writeable=True)
-    dstv[...] = rows
-    return buf
 
 
 def logical_rows(bytes_: np.ndarray, typ: int, ne, nb) -> np.ndarray:
@@ -175,19 +160,25 @@ def make_view(prob: Problem, *variants: str, scale: Optional[float] = None) -> V
     v_layout = "pos" if ("kv_split_layout" in vs or "kv_pos" in vs) else "head"
     assert not ("kv_split_layout" in vs and "kv_split_layout_r" in vs)
 
-    def place(bytes_, typ, nb_in, layout):
-        rows = logical_rows(bytes_, typ, prob.kv_ne, nb_in)
-        rb = rows.shape[-1]
+    def kv(bytes_, typ, nb_in, layout):
         eb = 2 if typ == orc.TYPE_F16 else orc.BLOCK_BYTES[typ]
-        if layout == "head":
-            nb = (eb, rb, n_ctx * rb, Hkv * n_ctx * rb + gap)
-        else:
-            nb = (eb, Hkv * rb, rb, n_ctx * Hkv * rb + gap)
-        return Buf(_scatter(rows, nb, kv_off, np.array([KV_POISON])), kv_off, typ, prob.kv_ne, nb)
+        buf, nb = place_rows(logical_rows(bytes_, typ, prob.kv_ne, nb_in), eb, layout, fill=KV_POISON, off=kv_off,
+                             n_ctx=n_ctx, gap=gap)
+        return Buf(buf, kv_off, typ, prob.kv_ne, nb)
 
-    k = place(prob.k_bytes, prob.kv_type, prob.k_nb, k_layout)
-    v = place(prob.v_bytes, prob.v_type, prob.v_nb, v_layout)
+    k = kv(prob.k_bytes, prob.kv_type, prob.k_nb, k_layout)
+    v = kv(prob.v_bytes, prob.v_type, prob.v_nb, v_layout)
     return ViewProblem(prob, tuple(variants), q, k, v, mask, float(np.float32(prob.scale if scale is None else scale)))
+
+
+def swap_kv(vp: ViewProblem, gpu: Problem):
+    """vp (or a subclass: mask planes, op params, sinks), built over an F16
+    reference problem, with K / V replaced by the cache of `gpu` -- make_view
+    cannot lay out a type the oracle does not know."""
+    pad = np.full(GUARD, KV_POISON, dtype=np.uint8)
+    k = Buf(np.concatenate([gpu.k_bytes, pad]), 0, gpu.kv_type, gpu.kv_ne, gpu.k_nb)
+    v = Buf(np.concatenate([gpu.v_bytes, pad]), 0, gpu.v_type, gpu.kv_ne, gpu.v_nb)
+    return dataclasses.replace(vp, base=gpu, k=k, v=v)
 
 
 # ------------------------------------------------------------------ float64 reference
@@ -232,61 +223,17 @@ def exact_f64(prob: Problem, scale: Optional[float] = None) -> np.ndarray:
 
 # ------------------------------------------------------------------ GPU runner
 
-DST_GUARD_BYTES = 4096
-SENTINEL = 0x5A5AA5A5   # a finite f32 (1.5e16), distinct from the NaN pre-fill
-WS_TAIL_BYTES = 4096
+def GpuView(vp: ViewProblem, dev="cuda", kv_chunk: int = 0, sinks=None):
+    """A ViewProblem on the GPU: its gpu_util.GuardedLaunch (dst guard bands,
+    the exactly-sized workspace and its sentinel tail), output [S][NQ][H][D].
+    sinks: f32 [H], for a launch through fattn_ext_sinks."""
+    import torch
 
-
-class GpuView:
-    """A ViewProblem on the GPU: dst inside a larger tensor with 4 KiB of
-    sentinel before and after it (pre-filled with NaN), the workspace sized to
-    exactly fattn.workspace_size() inside a larger buffer with a sentinel tail
-    and zeroed once."""
-
-    def __init__(self, vp: ViewProblem, dev="cuda", kv_chunk: int = 0):
-        import torch
-
-        import fattn
-        self.vp = vp
-        b = vp.base
-        up = lambda a: torch.from_numpy(a).to(dev)
-        self.t = {"q": up(vp.q.data), "k": up(vp.k.data), "v": up(vp.v.data)}
-        if vp.mask is not None:
-            self.t["mask"] = up(vp.mask.data)
-        ptrs = {n: x.data_ptr() for n, x in self.t.items()}
-        self.n_out = b.S * b.NQ * b.H * b.D
-        g = DST_GUARD_BYTES // 4
-        self.dst_all = torch.full((g + self.n_out + g,), SENTINEL, dtype=torch.int32, device=dev)
-        self.dst = self.dst_all[g:g + self.n_out].view(torch.float32)
-        self.dst.fill_(float("nan"))
-        self.p = vp.params(ptrs, self.dst.data_ptr(), kv_chunk=kv_chunk)
-        self.ws_bytes = fattn.workspace_size(self.p)
-        self.ws_all = torch.full(((self.ws_bytes + 3) // 4 + WS_TAIL_BYTES // 4,), SENTINEL, dtype=torch.int32,
-                                 device=dev)
-        if self.ws_bytes:
-            self.ws_all.view(torch.uint8)[:self.ws_bytes].zero_()
-            self.p.workspace = self.ws_all.data_ptr()
-            self.p.workspace_bytes = self.ws_bytes
-
-    def describe(self) -> str:
-        import fattn
-        return fattn.describe(self.p)
-
-    def run(self) -> np.ndarray:
-        import torch
-
-        import fattn
-        b = self.vp.base
-        self.dst.fill_(float("nan"))
-        fattn.flash_attn_ext(self.p)
-        torch.cuda.synchronize()
-        return self.dst.cpu().numpy().reshape(b.S, b.NQ, b.H, b.D)
-
-    def guards_intact(self) -> bool:
-        """dst's guard bands and the workspace tail still hold the sentinel."""
-        import torch
-        g = DST_GUARD_BYTES // 4
-        d = self.dst_all.cpu().numpy().view(np.uint32)
-        w = self.ws_all.view(torch.uint8)[self.ws_bytes:].cpu().numpy()
-        want = np.full(self.ws_all.numel(), SENTINEL, dtype=np.uint32).view(np.uint8)[self.ws_bytes:]
-        return bool((d[:g] == SENTINEL).all() and (d[g + self.n_out:] == SENTINEL).all() and np.array_equal(w, want))
+    from gpu_util import GuardedLaunch
+    up = lambda a: torch.from_numpy(a).to(dev)
+    t = {"q": up(vp.q.data), "k": up(vp.k.data), "v": up(vp.v.data)}
+    if vp.mask is not None:
+        t["mask"] = up(vp.mask.data)
+    ptrs = {n: x.data_ptr() for n, x in t.items()}
+    b = vp.base
+    return GuardedLaunch(lambda dst: vp.params(ptrs, dst, kv_chunk=kv_chunk), (b.S, b.NQ, b.H, b.D), t, dev, sinks=sinks)
