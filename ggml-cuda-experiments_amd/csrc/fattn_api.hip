@@ -215,15 +215,19 @@ int fattn_describe(const fattn_params* p, char* out, size_t cap) {
 
 namespace {
 
-// The one launch path of fattn_ext / fattn_ext_events / fattn_ext_sinks.  The
-// plan is a function of `p` alone: `sinks` (null: off) only rides along as a
-// kernel argument of the plan's kernels (SplitArgs::sinks)
-int launch_ext(const fattn_params* p, const float* sinks, void* stream, void* ev_begin, void* ev_end) {
+// The one launch path of fattn_ext / fattn_ext_events / fattn_ext_sinks /
+// fattn_ext_lse.  The plan is a function of `p` alone: `sinks` (null: off) only
+// rides along as a kernel argument of the plan's kernels (SplitArgs::sinks), and
+// with `lse` the same plan launches its kernels' instantiations over
+// SplitArgsLse, which also store the rows' log-sum-exp (Plan::lse, with_args)
+int launch_ext(const fattn_params* p, const float* sinks, float* lse, void* stream, void* ev_begin, void* ev_end) {
     Plan pl;
     const int rc = plan_now(p, pl);
     if (rc != FATTN_OK) return rc;
     if ((uintptr_t)sinks % 4) return FATTN_ERR_ALIGNMENT;
+    if ((uintptr_t)lse % 4) return FATTN_ERR_ALIGNMENT;
     pl.a.sinks = sinks;
+    pl.lse = lse;
     if (pl.ws_bytes) {
         if (!p->workspace || p->workspace_bytes < pl.ws_bytes || (uintptr_t)p->workspace % 16) return FATTN_ERR_WORKSPACE;
         uint8_t* w = (uint8_t*)p->workspace;
@@ -260,14 +264,18 @@ dim3 grid256(int64_t units) { return dim3((unsigned)((units + 255) / 256)); }
 
 extern "C" {
 
-int fattn_ext(const fattn_params* p, void* stream) { return launch_ext(p, nullptr, stream, nullptr, nullptr); }
+int fattn_ext(const fattn_params* p, void* stream) { return launch_ext(p, nullptr, nullptr, stream, nullptr, nullptr); }
 
 int fattn_ext_events(const fattn_params* p, void* stream, void* ev_begin, void* ev_end) {
-    return launch_ext(p, nullptr, stream, ev_begin, ev_end);
+    return launch_ext(p, nullptr, nullptr, stream, ev_begin, ev_end);
 }
 
 int fattn_ext_sinks(const fattn_params* p, const float* sinks, void* stream) {
-    return launch_ext(p, sinks, stream, nullptr, nullptr);
+    return launch_ext(p, sinks, nullptr, stream, nullptr, nullptr);
+}
+
+int fattn_ext_lse(const fattn_params* p, const float* sinks, float* lse, void* stream) {
+    return launch_ext(p, sinks, lse, stream, nullptr, nullptr);
 }
 
 int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void* mask, float* dst, float scale,

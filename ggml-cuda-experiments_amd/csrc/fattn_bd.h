@@ -196,8 +196,8 @@ __device__ __forceinline__ void bd_dequant(const uint8_t* raw, uint8_t* k16, uin
 // (r / 8) mod n, one merge_row_parts each: the fa_reduce LSE merge
 // (src/flash_row_float.h:415-472) in fp32, fixed order.  This replaces the
 // second launch (fattn_chunk_merge_kernel) and its kernel boundary.
-template <int D>
-__device__ __forceinline__ void bd_tile_merge(const SplitArgs& a, uint8_t* smem, const float* acc, float M, float L,
+template <int D, typename A>
+__device__ __forceinline__ void bd_tile_merge(const A& a, uint8_t* smem, const float* acc, float M, float L,
                                               int pr, int c0, bool row_valid, int tid, int lane, int wave, int qt,
                                               int ik2, int iq3, int y, int chunk) {
     constexpr int kDpt = kBdRows * D / (kBdWaves * kWave);
@@ -222,13 +222,15 @@ __device__ __forceinline__ void bd_tile_merge(const SplitArgs& a, uint8_t* smem,
         const int64_t s0 = tile * n * kBdRows + r;  // chunk 0's row r
         const int rq = div_R(a, r);
         const int riq2 = ik2 * a.rk2 + (r - rq * a.R);
-        float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
+        const int64_t row = ((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2;
+        float* out = a.dst + row * D;
         if (ok) {
             merge_row_parts<D, 8>(a.ws_o + s0 * D, a.ws_ml + 2 * s0, n, out, lane, kBdRows * D, 2 * kBdRows,
                                   [&]() -> const float* {
                                       const float* sinks = a.sinks;
                                       return sinks ? sinks + riq2 : nullptr;
-                                  });
+                                  },
+                                  lse_at(a, row));
         } else if (lane < D / 4) {
             *(f32x4*)(out + 4 * lane) = f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")};
         }
@@ -249,8 +251,8 @@ struct BdPark {
     static constexpr int ml = NKG * kBdRows * stride * 4;
     static constexpr int bytes = ml + NKG * kBdRows * 8;
 };
-template <int D, int NKG>
-__device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, const f32x16 (&o)[D / 32], float m_run,
+template <int D, int NKG, typename A>
+__device__ __forceinline__ void bd_finish(const A& a, uint8_t* smem, const f32x16 (&o)[D / 32], float m_run,
                                           f32x2 l2, int kq, int p, int h, bool has_state, int tid, int lane, int wave,
                                           int qt, int ik2, int iq3, int y, int chunk) {
     using PK = BdPark<D, NKG>;
@@ -310,22 +312,26 @@ __device__ __forceinline__ void bd_finish(const SplitArgs& a, uint8_t* smem, con
     if (!pr_ok) return;
     if (a.n_chunks == 1) {
         const int q2 = ik2 * a.rk2 + (pr - rq * a.R);
-        float* out = a.dst + (((int64_t)iq3 * a.NQ + q1) * a.H + q2) * D + c0;
+        const int64_t row = ((int64_t)iq3 * a.NQ + q1) * a.H + q2;
+        float* out = a.dst + row * D + c0;
         if (const float* sinks = a.sinks) {  // (wave-uniform; rows differ per thread: one load each)
             bool dead;
             const float inv = sink_inv(M, L, sinks[q2], dead);
 #pragma unroll
             for (int e = 0; e < kDpt; e += 4)
                 *(f32x4*)(out + e) = sink_row(f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]}, inv, dead);
-            return;
+        } else {
+            const float inv = 1.0f / L;  // fully masked row -> NaN like the reference
+#pragma unroll
+            for (int e = 0; e < kDpt; e += 4) {
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = L == 0.0f ? __builtin_nanf("") : acc[e + r] * inv;
+                *(f32x4*)(out + e) = v;
+            }
         }
-        const float inv = 1.0f / L;  // fully masked row -> NaN like the reference
-#pragma unroll
-        for (int e = 0; e < kDpt; e += 4) {
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = L == 0.0f ? __builtin_nanf("") : acc[e + r] * inv;
-            *(f32x4*)(out + e) = v;
+        if (float* const lse = lse_of(a)) {  // (wave-uniform) the row's first thread writes its log-sum-exp
+            if (c0 == 0) lse[row] = row_lse(M, L, a.sinks ? a.sinks[q2] : kNegInf, row_dead(M, L));
         }
         return;
     }
@@ -523,8 +529,8 @@ __device__ __forceinline__ void bd_tile_step(const SplitArgs& a, const uint8_t* 
     }
 }
 
-template <int KT, int D, bool HM>
-__global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const SplitArgs a) {
+template <int KT, int D, bool HM, typename A = SplitArgs>
+__global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bd_kernel(const A a) {
     using C = BdCfg<KT, D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NK = D / 16;   // 16-dim k-steps of S^T = K.Q^T

@@ -203,8 +203,8 @@ __device__ __forceinline__ void bdp_compute_wait(int raws, int masks) {
     }
 }
 
-template <int KT, int D, bool HM>
-__global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const SplitArgs a) {
+template <int KT, int D, bool HM, typename A = SplitArgs>
+__global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const A a) {
     using C = BdpCfg<KT, D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NK = D / 16;   // 16-dim k-steps of S^T = K.Q^T

@@ -411,6 +411,23 @@ __device__ __forceinline__ f32x4 sink_row(f32x4 acc, float inv, bool dead) {
     return dead ? f32x4{0.0f, 0.0f, 0.0f, 0.0f} : acc * inv;
 }
 
+// ---------------------------------------------------------------- row log-sum-exp
+// fattn_ext_lse: the natural-log LSE of a row's final scores from the state
+// (M, L) the row is normalised with, ln2 (M + log2 L); with a raw sink s
+// (-inf: none) the sink is one more term, in sink_inv()'s overflow-safe form:
+// mm = max(M, s'), ln2 (mm + log2(L 2^(M - mm) + 2^(s' - mm))) -- with s =
+// -inf that is L * 1 + 0, the sinkless value bit for bit.  `dead` (sink_inv's:
+// no live key) selects the sink itself -- -inf without one --, never the
+// outcome of -inf + -inf or of a NaN L.  Called once per output row behind a
+// wave-uniform `if (lse_of(a))`, after the row's dst stores (SplitArgsLse, fattn_tile.h).
+__device__ __forceinline__ bool row_dead(float M, float L) { return !(L > 0.0f) || M == -__builtin_inff(); }
+__device__ __forceinline__ float row_lse(float M, float L, float sink, bool dead) {
+    const float s = sink * 1.4426950408889634f;
+    const float mm = fmaxf(M, s);
+    const float t = __builtin_fmaf(L, __builtin_amdgcn_exp2f(M - mm), __builtin_amdgcn_exp2f(s - mm));
+    return dead ? sink : 0.6931471805599453f * (mm + __builtin_amdgcn_logf(t));
+}
+
 __device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
 }

@@ -72,6 +72,8 @@ constexpr bool has_kernel(Kernel kern, int kt, int vt, int D) {
 
 struct Plan {
     SplitArgs a = {};
+    float* lse = nullptr;  // fattn_ext_lse's pointer (launch_ext sets it; no part of the plan): which kernels launch, with_args
+
     Kernel kernel = Kernel::Split;
     int kt = 0, vt = 0;  // vt may be VT_F16T
     int D = 0;           // head dim (Kernel::Mla: K's, 576)
@@ -99,6 +101,25 @@ struct Plan {
     int stage_hkv = 0, stage_skv = 0;
     size_t stage_off = 0, stage_bytes = 0;             // per K (or V): Skv * Hkv * N * D * 2
 };
+
+// Every kernel that normalises into dst exists over SplitArgs and over
+// SplitArgsLse (fattn_tile.h): go(type tag) launches the former, or with
+// pl.lse the latter -- the kernels that also store the rows' log-sum-exp.
+template <typename T>
+struct ArgsTag {
+    using type = T;
+};
+template <typename A>
+A launch_args(const Plan& pl) {
+    A a;
+    static_cast<SplitArgs&>(a) = pl.a;
+    if constexpr (std::is_same<A, SplitArgsLse>::value) a.lse = pl.lse;
+    return a;
+}
+template <typename F>
+auto with_args(const Plan& pl, F&& go) {
+    return pl.lse ? go(ArgsTag<SplitArgsLse>()) : go(ArgsTag<SplitArgs>());
+}
 
 struct Events {
     hipEvent_t begin = nullptr, end = nullptr;
@@ -151,7 +172,12 @@ void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
         constexpr bool PLAIN = decltype(plain)::value, F16 = decltype(f16)::value;
         const int need = (pl.a.n_chunks + parts_per_row - 1) / parts_per_row;
         auto go = [&](auto kit) {
-            hipLaunchKernelGGL((fattn_chunk_merge_kernel<Geom, D, decltype(kit)::value, PLAIN, F16>), grid, dim3(256), 0, st, pl.a);
+            with_args(pl, [&](auto tag) {
+                using A = typename decltype(tag)::type;
+                hipLaunchKernelGGL((fattn_chunk_merge_kernel<Geom, D, decltype(kit)::value, PLAIN, F16, A>), grid, dim3(256), 0, st,
+                                   launch_args<A>(pl));
+                return 0;
+            });
         };
         if constexpr (Geom::min_kit <= 2) {
             if (need <= 2) return go(std::integral_constant<int, 2>());
@@ -170,26 +196,26 @@ void launch_chunk_merge(dim3 grid, const Plan& pl, hipStream_t st) {
     if constexpr (Geom::sc1) pick(ppr, std::false_type(), std::false_type());
 }
 
-template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
-int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
+template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, typename A>
+int launch_split_a(const Plan& pl, hipStream_t st, const Events& ev) {
     if (pl.kernel == Kernel::SplitLd) {
         if constexpr (GRAN == 16 && NWV == 8 && EPI == 2 && split_ld_ok(KT, VT, D)) {
-            auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders>;
+            auto lk = fattn_split_ld_kernel<KT, VT, D, HM, NWV, kSplitLoaders, A>;
             return launch_kernel((const void*)lk, pl, st, ev, [&] {
-                hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, pl.a);
+                hipLaunchKernelGGL(lk, pl.grid, dim3((NWV + kSplitLoaders) * kWave), pl.lds, st, launch_args<A>(pl));
             });
         }
         return FATTN_ERR_INVALID_ARG;
     }
-    void (*kern)(SplitArgs) = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI>;
+    void (*kern)(A) = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI, false, A>;
     // max_bias / logit_softcap live: the bodies with the score transform, which
     // exist for 4 waves (the planner sizes such a launch so: size_split)
     if (pl.a.xf.live) {
-        if constexpr (NWV == 4) kern = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI, true>;
+        if constexpr (NWV == 4) kern = fattn_split_kernel<KT, VT, D, GRAN, HM, NWV, EPI, true, A>;
         else return FATTN_ERR_INVALID_ARG;
     }
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
-        hipLaunchKernelGGL(kern, pl.grid, dim3(NWV * kWave), pl.lds, st, pl.a);
+        hipLaunchKernelGGL(kern, pl.grid, dim3(NWV * kWave), pl.lds, st, launch_args<A>(pl));
         if constexpr (EPI == 0) {
             // multi-row tiles: the chunk partials merge in a second launch --
             // unless they merge in-kernel (2)
@@ -203,6 +229,11 @@ int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
             }
         }
     });
+}
+
+template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI>
+int launch_split_e(const Plan& pl, hipStream_t st, const Events& ev) {
+    return with_args(pl, [&](auto tag) { return launch_split_a<KT, VT, D, GRAN, HM, NWV, EPI, typename decltype(tag)::type>(pl, st, ev); });
 }
 
 // the plan's epilogue (a.wave_merge): 1 only for 4 waves at D = 128
@@ -245,11 +276,11 @@ int launch_gran(const Plan& pl, hipStream_t st, const Events& ev) {
     }
 }
 
-template <int KT, int D, int NW, bool HM>
-int launch_mq_hm(const Plan& pl, hipStream_t st, const Events& ev) {
-    auto kern = fattn_mq_kernel<KT, D, NW, HM>;
+template <int KT, int D, int NW, bool HM, typename A>
+int launch_mq_a(const Plan& pl, hipStream_t st, const Events& ev) {
+    auto kern = fattn_mq_kernel<KT, D, NW, HM, A>;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
-        hipLaunchKernelGGL(kern, pl.grid, dim3(NW * kWave), pl.lds, st, pl.a);
+        hipLaunchKernelGGL(kern, pl.grid, dim3(NW * kWave), pl.lds, st, launch_args<A>(pl));
         if (pl.a.merge_launch) {
             // the chunk partials of every 16-row subtile (4 per 64-row tile,
             // 16 per 256-row tile) merge in a second launch
@@ -257,6 +288,11 @@ int launch_mq_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             launch_chunk_merge<MqMergeGeom<SUBS>, D>(dim3(kRows / 4, pl.grid.y * SUBS, pl.grid.z), pl, st);
         }
     });
+}
+
+template <int KT, int D, int NW, bool HM>
+int launch_mq_hm(const Plan& pl, hipStream_t st, const Events& ev) {
+    return with_args(pl, [&](auto tag) { return launch_mq_a<KT, D, NW, HM, typename decltype(tag)::type>(pl, st, ev); });
 }
 
 template <int KT, int D>
@@ -279,17 +315,17 @@ void launch_prepass(Types, int stage_kt, dim3 grid, hipStream_t st, const PfPrep
 // ... of ExtTypes (instantiated in fattn_launch_kv_ext.hip)
 void launch_prepass_kv_ext(int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa);
 
-template <int KT, int D, bool HM>
-int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
+template <int KT, int D, bool HM, typename A>
+int launch_pf_a(const Plan& pl, hipStream_t st, const Events& ev) {
     // (max_bias / logit_softcap live: the body with the score transform; the
     // planner keeps such launches off the one-wave-per-SIMD bodies)
-    void (*kern)(SplitArgs) = pl.a.xf.live ? fattn_pf_kernel<KT, D, HM, true> : fattn_pf_kernel<KT, D, HM, false>;
+    void (*kern)(A) = pl.a.xf.live ? fattn_pf_kernel<KT, D, HM, true, A> : fattn_pf_kernel<KT, D, HM, false, A>;
     int waves = kPfWaves;
     if constexpr (has_kernel(Kernel::Pf4, KT, KT, D)) {
         if (pl.kernel == Kernel::Pf4) {
-            if (pl.pf4_sched == 4) kern = fattn_pf4_kernel<D, HM, 4>;
-            else if (pl.pf4_sched == 3) kern = fattn_pf4_kernel<D, HM, 3>;
-            else kern = fattn_pf4_kernel<D, HM, 2>;
+            if (pl.pf4_sched == 4) kern = fattn_pf4_kernel<D, HM, 4, A>;
+            else if (pl.pf4_sched == 3) kern = fattn_pf4_kernel<D, HM, 3, A>;
+            else kern = fattn_pf4_kernel<D, HM, 2, A>;
             waves = kPf4Waves;
         }
     }
@@ -318,27 +354,35 @@ int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
             else if (is_kv_ext(pl.stage_kt)) launch_prepass_kv_ext(pl.stage_kt, g, st, pa);
             else launch_prepass(QuantTypes(), pl.stage_kt, g, st, pa);
         }
-        hipLaunchKernelGGL(kern, pl.grid, dim3(waves * kWave), pl.lds, st, pl.a);
+        hipLaunchKernelGGL(kern, pl.grid, dim3(waves * kWave), pl.lds, st, launch_args<A>(pl));
     });
+}
+template <int KT, int D, bool HM>
+int launch_pf_hm(const Plan& pl, hipStream_t st, const Events& ev) {
+    return with_args(pl, [&](auto tag) { return launch_pf_a<KT, D, HM, typename decltype(tag)::type>(pl, st, ev); });
 }
 
 // D = 128: the all-waves form, or the role form for quantised K/V (Kernel::Bdp);
 // D = 64 / 96: the role form only for quantised K/V, the all-waves form's f16
 // image ring for f16
-template <int KT, int D, bool HM>
-int launch_bd_hm(const Plan& pl, hipStream_t st, const Events& ev) {
-    void (*kern)(SplitArgs) = nullptr;
+template <int KT, int D, bool HM, typename A>
+int launch_bd_a(const Plan& pl, hipStream_t st, const Events& ev) {
+    void (*kern)(A) = nullptr;
     if constexpr (has_kernel(Kernel::Bd, KT, KT, D)) {
-        if (pl.kernel == Kernel::Bd) kern = fattn_bd_kernel<KT, D, HM>;
+        if (pl.kernel == Kernel::Bd) kern = fattn_bd_kernel<KT, D, HM, A>;
     }
     if constexpr (has_kernel(Kernel::Bdp, KT, KT, D)) {
-        if (pl.kernel == Kernel::Bdp) kern = fattn_bdp_kernel<KT, D, HM>;
+        if (pl.kernel == Kernel::Bdp) kern = fattn_bdp_kernel<KT, D, HM, A>;
     }
     if (kern == nullptr) return FATTN_ERR_UNSUPPORTED_TYPE;
     return launch_kernel((const void*)kern, pl, st, ev, [&] {
-        hipLaunchKernelGGL(kern, pl.grid, dim3(kBdWaves * kWave), pl.lds, st, pl.a);
+        hipLaunchKernelGGL(kern, pl.grid, dim3(kBdWaves * kWave), pl.lds, st, launch_args<A>(pl));
         if (pl.a.merge_launch == 1) launch_chunk_merge<BdMergeGeom, D>(dim3(kBdRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
+}
+template <int KT, int D, bool HM>
+int launch_bd_hm(const Plan& pl, hipStream_t st, const Events& ev) {
+    return with_args(pl, [&](auto tag) { return launch_bd_a<KT, D, HM, typename decltype(tag)::type>(pl, st, ev); });
 }
 
 template <int KT, int D>

@@ -8,11 +8,11 @@ namespace fattn {
 namespace {
 
 // (one instantiation per kernel: launch_kernel caches the LDS attribute per launch site)
-template <int KT, bool HM, bool SOLO>
-int launch_mla_q_form(const Plan& pl, hipStream_t st, const Events& ev) {
-    auto kern = fattn_mla_kernel<false, HM, KT, SOLO>;
-    MlaArgs ma;
-    ma.a = pl.a;
+template <int KT, bool HM, bool SOLO, typename A>
+int launch_mla_q_a(const Plan& pl, hipStream_t st, const Events& ev) {
+    auto kern = fattn_mla_kernel<false, HM, KT, SOLO, A>;
+    MlaArgsT<A> ma;
+    ma.a = launch_args<A>(pl);
     // V starts b whole blocks into K's rows: 64 b bytes into the image's rows
     ma.v_off = pl.mla_v_off / TypeInfo<KT>::block_bytes * (QK * 2);
     ma.raw16 = SOLO && pl.mla_raw16;
@@ -20,6 +20,10 @@ int launch_mla_q_form(const Plan& pl, hipStream_t st, const Events& ev) {
         hipLaunchKernelGGL(kern, pl.grid, dim3(kMlaWaves * kWave), pl.lds, st, ma);
         if (pl.a.merge_launch == 1) launch_chunk_merge<MlaMergeGeom, kMlaDV>(dim3(kMlaRows / 4, pl.grid.y, pl.grid.z), pl, st);
     });
+}
+template <int KT, bool HM, bool SOLO>
+int launch_mla_q_form(const Plan& pl, hipStream_t st, const Events& ev) {
+    return with_args(pl, [&](auto tag) { return launch_mla_q_a<KT, HM, SOLO, typename decltype(tag)::type>(pl, st, ev); });
 }
 
 template <int KT>

@@ -52,11 +52,13 @@ constexpr int kMlaWaves = 4;
 constexpr int kMlaRows = 64;  // packed rows per workgroup (16 per wave)
 constexpr int kMlaVOffMax = 128;
 
-struct MlaArgs {
-    SplitArgs a;
+template <typename A>
+struct MlaArgsT {
+    A a;  // SplitArgs, or SplitArgsLse: the kernel fattn_ext_lse launches (fattn_tile.h)
     int v_off;  // view form: byte offset of V's row inside K's row (0 .. 128, a multiple of 16); else 0
     int raw16;  // SOLO form of a quantised cache: contiguous rows on a 16-B aligned plane -- whole tiles land in 16-B pieces
 };
+using MlaArgs = MlaArgsT<SplitArgs>;
 
 // KT: the cache's type.  F16: the ring holds f16 tiles as they come from HBM.
 // Q8_0 / Q4_0 (V a view of K only): the ring holds RAW tiles -- 32 rows of 18
@@ -230,12 +232,12 @@ __device__ __forceinline__ void mla_wait_tiles(int pending) {
 // SOLO (quantised cache only; the launcher's choice): no tile of the launch has
 // more than one wave's 16 rows (H = 16 decode), so wave 0 computes and waves
 // 1 - 3 load and convert -- the conversion leaves the computing wave's chain.
-template <bool VOWN, bool HM, int KT = FATTN_TYPE_F16, bool SOLO = false>
-__global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const MlaArgs ma) {
+template <bool VOWN, bool HM, int KT = FATTN_TYPE_F16, bool SOLO = false, typename A = SplitArgs>
+__global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const MlaArgsT<A> ma) {
     using C = MlaCfg<VOWN, KT>;
     constexpr bool QUANT = C::QUANT;
     static_assert(QUANT || !SOLO, "");
-    const SplitArgs& a = ma.a;
+    const A& a = ma.a;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NB = kMlaDK / QK;   // 18 k-steps
     constexpr int NC = kMlaDV / 16;   // 32 column groups
@@ -597,21 +599,28 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
 
     if (a.n_chunks == 1) {
         if (!row_ok) return;
-        float* out = a.dst + (((int64_t)iq3 * a.NQ + iq1) * a.H + iq2) * kMlaDV + 4 * g;
+        const int64_t row = ((int64_t)iq3 * a.NQ + iq1) * a.H + iq2;
+        float* out = a.dst + row * kMlaDV + 4 * g;
+        float sraw = kNegInf;  // (the row's raw sink: a term of its log-sum-exp below)
         if (a.sinks) {  // (wave-uniform; m_run is the row's reference max in log2 units)
             bool dead;
-            const float inv = sink_inv(m_run, l_tot, a.sinks[iq2], dead);
+            sraw = a.sinks[iq2];
+            const float inv = sink_inv(m_run, l_tot, sraw, dead);
 #pragma unroll
             for (int c = 0; c < NC; c++) *(f32x4*)(out + 16 * c) = sink_row(o[c], inv, dead);
-            return;
+        } else {
+            const float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
+#pragma unroll
+            for (int c = 0; c < NC; c++) {
+                f32x4 v;
+#pragma unroll
+                for (int r = 0; r < 4; r++) v[r] = l_tot == 0.0f ? __builtin_nanf("") : o[c][r] * inv;
+                *(f32x4*)(out + 16 * c) = v;
+            }
         }
-        const float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
-#pragma unroll
-        for (int c = 0; c < NC; c++) {
-            f32x4 v;
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = l_tot == 0.0f ? __builtin_nanf("") : o[c][r] * inv;
-            *(f32x4*)(out + 16 * c) = v;
+        // the row's log-sum-exp, behind its dst stores: the O registers are dead here
+        if (float* const lse = lse_of(a)) {  // (wave-uniform)
+            if (g == 0) lse[row] = row_lse(m_run, l_tot, sraw, row_dead(m_run, l_tot));
         }
         return;
     }

@@ -211,8 +211,8 @@ __device__ __forceinline__ void mq_dequant(const uint8_t* rb, int kv_raw, uint8_
     }
 }
 
-template <int KT, int D, int NW, bool HM>
-__global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(const SplitArgs a) {
+template <int KT, int D, int NW, bool HM, typename A = SplitArgs>
+__global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(const A a) {
     constexpr int RPW = NW == 8 ? 32 : 16;  // packed rows per wave
     using C = MQCfg<KT, D, NW, RPW>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -441,6 +441,15 @@ __global__ __launch_bounds__(NW * kWave, NW == 8 ? 1 : 2) void fattn_mq_kernel(c
 #pragma unroll
                 for (int r = 0; r < 4; r++) v[r] = l_tot[gi] == 0.0f ? __builtin_nanf("") : o[gi][c][r] * inv;
                 *(f32x4*)(out + 16 * c) = v;
+            }
+        }
+        // the rows' log-sum-exp, behind every dst store (the O registers are dead here)
+        if (float* const lse = lse_of(a)) {  // (wave-uniform)
+#pragma unroll
+            for (int gi = 0; gi < NG; gi++) {
+                if (!row_ok[gi] || g != 0) continue;
+                lse[((int64_t)iq3 * a.NQ + iq1[gi]) * a.H + iq2[gi]] =
+                    row_lse(m_run[gi], l_tot[gi], sinks ? sinks[iq2[gi]] : kNegInf, row_dead(m_run[gi], l_tot[gi]));
             }
         }
         return;

@@ -261,8 +261,8 @@ __device__ __forceinline__ const uint8_t* pf_flag_table(const SplitArgs& a, int 
 // parameter here, not the other kernels' wave-uniform branch: a branch would
 // cut the tile body's basic block, and with it the sched_group_barrier
 // interleaving of the scores with the S^T chains.
-template <int KT, int D, bool HM, bool XF = false>
-__global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const SplitArgs a) {
+template <int KT, int D, bool HM, bool XF = false, typename A = SplitArgs>
+__global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a) {
     using C = PfCfg<KT, D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NK = C::DI / 16;   // 16-dim k-steps of S^T = K.Q^T
@@ -824,6 +824,12 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const Spli
             const f32x4 v = *(const f32x4*)(park + r * kStride + 4 * c);
             *(f32x4*)(a.dst + (((int64_t)iq3 * a.NQ + q1) * a.H + q2) * D + 4 * c) = v;
         }
+    }
+    // the log-sum-exp of this lane's row (lanes 32 .. 63 hold the same rows), behind the dst stores
+    if (float* const lse = lse_of(a)) {  // (wave-uniform)
+        if (row_ok && h == 0)
+            lse[((int64_t)iq3 * a.NQ + iq1) * a.H + iq2] =
+                row_lse(m_run, l_tot, a.sinks ? a.sinks[iq2] : -__builtin_inff(), row_dead(m_run, l_tot));
     }
 }
 

@@ -190,8 +190,8 @@ __device__ __forceinline__ constexpr int sched_inv(int i) {
 // one (FATTN_OPT_PF_FORM 5, the default).  Same arithmetic, same order per row
 // block: both give the same bits as fattn_pf_kernel.  (Round 5's unpipelined
 // three-phase forms, SCHED 0 / 1, measured 18-33 % slower and were removed.)
-template <int D, bool HM, int SCHED>
-__global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const SplitArgs a) {
+template <int D, bool HM, int SCHED, typename A = SplitArgs>
+__global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A a) {
     using C = Pf4Cfg<D>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NK = D / 16;   // 16-dim k-steps of S^T = K.Q^T
@@ -1236,6 +1236,17 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const Sp
         if (row_of(kPf4RowsW * wave + r, q1, q2)) {
             const f32x4 v = *(const f32x4*)(park + r * kStride + 4 * c);
             *(f32x4*)(a.dst + (((int64_t)iq3 * a.NQ + q1) * a.H + q2) * D + 4 * c) = v;
+        }
+    }
+    // the log-sum-exp of this lane's two rows (lanes 32 .. 63 hold the same rows), behind the dst stores
+    if (float* const lse = lse_of(a)) {  // (wave-uniform)
+#pragma unroll
+        for (int rb = 0; rb < 2; rb++) {
+            const float l_tot = PF4_XOR32(l2[rb].x + l2[rb].y, false);
+            int q1, q2;
+            if (row_of(kPf4RowsW * wave + 32 * rb + c32, q1, q2) && h == 0)
+                lse[((int64_t)iq3 * a.NQ + q1) * a.H + q2] =
+                    row_lse(m_run[rb], l_tot, sinks ? sinks[q2] : -__builtin_inff(), row_dead(m_run[rb], l_tot));
         }
     }
 #ifdef FATTN_STAMPS

@@ -428,8 +428,8 @@ __device__ __forceinline__ f16x8 v_operand_f16(const uint8_t* vb, int c, int g, 
 // ---------------------------------------------------------------- kernel
 
 
-template <int D, int CB = 2>
-__device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, int qt, int hs, int ik2, int iq3,
+template <int D, int CB = 2, typename A>
+__device__ __forceinline__ void combine_tile(const A& a, int64_t tile, int qt, int hs, int ik2, int iq3,
                                              int rv, int row_base, uint8_t* smem);
 
 // One-row tiles (decode with n_q * H / Hkv == 1 per tile), up to 32 parts per
@@ -441,8 +441,8 @@ __device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, i
 // fa_reduce math as combine_tile (src/flash_row_float.h:415-472), fixed order.
 constexpr int kWaveMergeParts = 64;  // parts per tile (one (m, l) pair per lane)
 constexpr int kWaveMergeBatch = 32;  // parts loaded per round trip
-template <int D, bool VQ8, int NW = kSplitWaves, bool CP = false>
-__device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f32x4 (&o)[D / 16], float m_run,
+template <int D, bool VQ8, int NW = kSplitWaves, bool CP = false, typename A>
+__device__ __forceinline__ void wave_merge_epilogue(const A& a, const f32x4 (&o)[D / 16], float m_run,
                                                     float l_tot, int chunk, int wave, int lane, int qt, int hs,
                                                     int ik2, int iq3, int y) {
     static_assert(D == 128, "lane i <-> dims 2i, 2i+1");
@@ -534,7 +534,8 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
     const int rq = div_R(a, 0);
     const int riq1 = qt * a.QPT + rq;
     const int riq2 = ik2 * a.rk2 + hs * a.R;
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D + d4;
+    const int64_t row = ((int64_t)iq3 * a.NQ + riq1) * a.H + riq2;
+    float* out = a.dst + row * D + d4;
     if (const float* sinks = a.sinks) {  // (wave-uniform) the head's sink joins the merged row's denominator
         bool dead;
         const float inv = sink_inv(M, L, sinks[riq2], dead);
@@ -542,6 +543,9 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
     } else {
         const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
         *(f32x4*)out = acc * inv;
+    }
+    if (float* const lse = lse_of(a)) {  // (wave-uniform) the merged row's log-sum-exp, one lane
+        if (lane == 0) lse[row] = row_lse(M, L, a.sinks ? a.sinks[riq2] : kNegInf, row_dead(M, L));
     }
     FATTN_SSTAMP(13);
 }
@@ -554,8 +558,8 @@ __device__ __forceinline__ void wave_merge_epilogue(const SplitArgs& a, const f3
 // workgroup on the tile's arrival word, and the last workgroup's wave 0 merges
 // the chunks (merge_row_parts).  The cross-workgroup hand-off carries one row
 // per workgroup instead of one per wave.
-template <int D, bool VQ8, int NW, bool CP = false>
-__device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o)[D / 16], float m_run, float l_tot,
+template <int D, bool VQ8, int NW, bool CP = false, typename A>
+__device__ __forceinline__ void wg_row_merge(const A& a, const f32x4 (&o)[D / 16], float m_run, float l_tot,
                                              int chunk, int wave, int lane, int qt, int hs, int ik2, int iq3,
                                              int y, uint8_t* smem, int region) {
     constexpr int NB = D / QK;
@@ -635,7 +639,8 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
     }
     const int riq1 = qt * a.QPT;
     const int riq2 = ik2 * a.rk2 + hs * a.R;
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D;
+    const int64_t row = ((int64_t)iq3 * a.NQ + riq1) * a.H + riq2;
+    float* out = a.dst + row * D;
     if (a.n_chunks == 1) {
         if (h == 0) {
             if (const float* sinks = a.sinks) {  // (wave-uniform)
@@ -646,6 +651,9 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
                 const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;
                 *(f32x4*)(out + d4) = acc * inv;
             }
+        }
+        if (float* const lse = lse_of(a)) {  // (wave-uniform)
+            if (lane == 0) lse[row] = row_lse(M, L, a.sinks ? a.sinks[riq2] : kNegInf, row_dead(M, L));
         }
         return;
     }
@@ -677,9 +685,10 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
         const float* sinks = a.sinks;
         return sinks ? sinks + riq2 : nullptr;
     };
-    if (need <= 4) merge_row_parts<D, 4>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
-    else if (need <= 8) merge_row_parts<D, 8>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
-    else merge_row_parts<D>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink);
+    float* lse_row = lse_at(a, row);  // (wave-uniform)
+    if (need <= 4) merge_row_parts<D, 4>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink, lse_row);
+    else if (need <= 8) merge_row_parts<D, 8>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink, lse_row);
+    else merge_row_parts<D>(po_all, pml_all, a.n_chunks, out, lane, D, 2, sink, lse_row);
     FATTN_SSTAMP(13);
 }
 
@@ -693,8 +702,8 @@ __device__ __forceinline__ void wg_row_merge(const SplitArgs& a, const f32x4 (&o
 // merge and one published row per workgroup (wg_row_merge).  `active`: this
 // wave holds a state (waves >= NW must be inactive).  `sync_first`: the images
 // alias step buffers, so wait for every wave before writing them.
-template <int KT, int VT, int D, int NW, int EPI>
-__device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D / 16], float m_run, float l_run,
+template <int KT, int VT, int D, int NW, int EPI, typename A>
+__device__ __forceinline__ void split_epilogue(const A& a, f32x4 (&o)[D / 16], float m_run, float l_run,
                                                float (&corr)[corr_regs<VT, D, col_packed<VT, EPI>()>()], int wave, int lane,
                                                int qt, int hs, int ik2, int iq3, int y, int chunk, uint8_t* smem, int region,
                                                bool active, bool sync_first) {
@@ -790,9 +799,11 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
     // row (Mk = -inf) keeps L = 0, so the select on L == 0 below still finds it.
     // Without sinks ms = -inf leaves M and L as they were, bit for bit
     const float Mk = M;
-    float ms = kNegInf;
-    if (a.n_chunks == 1 && a.sinks != nullptr && tm < rv)  // (wave-uniform but for the row bound)
-        ms = a.sinks[ik2 * a.rk2 + hs * a.R + (tm - div_R(a, tm) * a.R)] * 1.4426950408889634f;
+    float ms = kNegInf, sraw = kNegInf;  // (sraw: the raw sink, the log-sum-exp of a row without a live key)
+    if (a.n_chunks == 1 && a.sinks != nullptr && tm < rv) {  // (wave-uniform but for the row bound)
+        sraw = a.sinks[ik2 * a.rk2 + hs * a.R + (tm - div_R(a, tm) * a.R)];
+        ms = sraw * 1.4426950408889634f;
+    }
     M = fmaxf(M, ms);
     float L = (ms == kNegInf || Mk == kNegInf) ? 0.0f : __builtin_amdgcn_exp2f(ms - M);
     float acc[EPT];
@@ -809,15 +820,17 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
         }
     }
     auto head_of = [&](int r) { return ik2 * a.rk2 + hs * a.R + (r - div_R(a, r) * a.R); };  // q head of packed row r (in-kernel merge)
-    auto dst_row = [&](int r) -> float* {
+    auto dst_idx = [&](int r) -> int64_t {  // packed row r's row of dst (and entry of lse)
         const int rq = div_R(a, r);
         const int riq1 = qt * a.QPT + rq;
         const int riq2 = ik2 * a.rk2 + hs * a.R + (r - rq * a.R);
-        return a.dst + (((int64_t)iq3 * a.NQ + riq1) * a.H + riq2) * D;
+        return ((int64_t)iq3 * a.NQ + riq1) * a.H + riq2;
     };
+    auto dst_row = [&](int r) -> float* { return a.dst + dst_idx(r) * D; };
     if (a.n_chunks == 1) {
         if (tm < rv && dok) {
-            float* out = dst_row(tm) + d0;
+            const int64_t idx = dst_idx(tm);
+            float* out = a.dst + idx * D + d0;
             // L == 0: the row has no live key -- NaN like the reference, zeros with
             // sinks; by selection either way
             const float inv = 1.0f / L;
@@ -831,6 +844,11 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
                 v.z = none ? fill : acc[e + 2] * inv;
                 v.w = none ? fill : acc[e + 3] * inv;
                 *(f32x4*)(out + e) = v;
+            }
+            // the row's log-sum-exp, one thread per row: the sink, where live, is in M and
+            // L already (above); nothing but the pointer is fetched for it
+            if (float* const lse = lse_of(a)) {  // (wave-uniform)
+                if (tj == 0) lse[idx] = !(L > 0.0f) ? sraw : row_lse(M, L, kNegInf, false);
             }
         }
         FATTN_SSTAMP(12);
@@ -893,7 +911,8 @@ __device__ __forceinline__ void split_epilogue(const SplitArgs& a, f32x4 (&o)[D 
                                       [&]() -> const float* {
                                           const float* sinks = a.sinks;
                                           return sinks ? sinks + head_of(r) : nullptr;
-                                      });
+                                      },
+                                      lse_at(a, dst_idx(r)));
             } else if (lane < D / 4) {
                 *(f32x4*)(out + 4 * lane) = f32x4{__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""),
                                                   __builtin_nanf("")};
@@ -1243,9 +1262,9 @@ constexpr int split_waves_per_simd() {
 // steps' dependent LDS -> VALU -> MFMA chains.
 // XF (split_step): instantiated for NWV = 4 only; the planner sizes a launch
 // with max_bias / logit_softcap live for 4 waves (size_split).
-template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false>
+template <int KT, int VT, int D, int GRAN, bool HM, int NWV, int EPI, bool XF = false, typename A = SplitArgs>
 __global__ __launch_bounds__(NWV * kWave, split_bounds_wps(KT, GRAN, D)) void fattn_split_kernel(
-    const SplitArgs a) {
+    const A a) {
     using C = SplitCfg<KT, VT, D>;
     using P = StepPlan<KT, VT, D, GRAN>;
     constexpr int NI = P::NIKV + (HM ? P::NIM : 0);  // VMEM instructions per step
@@ -1498,8 +1517,8 @@ __device__ __forceinline__ void wait_lds_flag(const uint32_t* f) {
     asm volatile("" ::: "memory");
 }
 
-template <int KT, int VT, int D, bool HM, int NWV, int NLD>
-__global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(const SplitArgs a) {
+template <int KT, int VT, int D, bool HM, int NWV, int NLD, typename A = SplitArgs>
+__global__ __launch_bounds__((NWV + NLD) * kWave, 1) void fattn_split_ld_kernel(const A a) {
     using C = SplitCfg<KT, VT, D>;
     using P = StepPlan<KT, VT, D, 16>;
     constexpr int NI = P::NIKV + (HM ? P::NIM : 0);  // VMEM instructions per step
@@ -1655,8 +1674,8 @@ struct SplitMergeGeom : MergeGeomBase {
 // (row_base != 0: the multi-query kernel's 16-row subtiles).  Written for
 // 256 threads; in a 512-thread workgroup the upper half only joins the
 // barriers (its groups, rows and chunks are all out of range).
-template <int D, int CB>
-__device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, int qt, int hs, int ik2, int iq3,
+template <int D, int CB, typename A>
+__device__ __forceinline__ void combine_tile(const A& a, int64_t tile, int qt, int hs, int ik2, int iq3,
                                              int rv, int row_base, uint8_t* smem) {
     constexpr float kNegInf = -__builtin_inff();
     constexpr int EPT = epi_ept<D>();
@@ -1718,6 +1737,14 @@ __device__ __forceinline__ void combine_tile(const SplitArgs& a, int64_t tile, i
                 lr = dead ? -1.0f : inv;
             }
             rowL[mr] = lr;
+            // the row's log-sum-exp: (Mr, Lr) are known here and nowhere below, so this
+            // one store stands before the row's dst stores
+            if (float* const lse = lse_of(a)) {  // (wave-uniform)
+                const int pr = row_base + mr, rq = div_R(a, pr);
+                const int riq2 = ik2 * a.rk2 + hs * a.R + (pr - rq * a.R);
+                lse[((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2] =
+                    row_lse(Mr, Lr, a.sinks ? a.sinks[riq2] : kNegInf, row_dead(Mr, Lr));
+            }
         }
     }
     __syncthreads();

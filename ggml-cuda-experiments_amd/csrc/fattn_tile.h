@@ -90,6 +90,27 @@ struct SplitArgs {
                         // normalise into dst, under a wave-uniform branch outside every tile loop
 };
 
+// fattn_ext_lse: the kernels' arguments with the pointer the rows' log-sum-exp
+// goes to (f32 [S][NQ][H]; row_lse, fattn_common.h).  Every kernel that
+// normalises into dst is a template over its argument type: over SplitArgs it
+// is the kernel of a launch without lse -- lse_of() is a constant null there,
+// so none of the log-sum-exp code exists in it and its argument block, registers
+// and instructions are those it had before there was an lse --, over
+// SplitArgsLse the one fattn_ext_lse launches (launch_args, fattn_launch.h).
+// One lane per output row stores one float after the row's dst stores, behind
+// the row guards of the dst store.
+struct SplitArgsLse : SplitArgs {
+    float* lse;
+};
+__device__ __forceinline__ constexpr float* lse_of(const SplitArgs&) { return nullptr; }
+__device__ __forceinline__ float* lse_of(const SplitArgsLse& a) { return a.lse; }
+// entry `row` of it, or null: off
+template <typename A>
+__device__ __forceinline__ float* lse_at(const A& a, int64_t row) {
+    float* const lse = lse_of(a);
+    return lse ? lse + row : nullptr;
+}
+
 // XOR mask of the 16-B chunk swizzle of an LDS row of `cpr` chunks: the largest
 // power of two dividing cpr, minus one, so that chunk ^ (x & mask) stays a
 // bijection on [0, cpr) (cpr = 16 / 8 for D = 128 / 64 f16 rows; 12 and 10 for
@@ -489,7 +510,8 @@ struct NoSink {
 };
 template <int D, int kIt = 16, int AUX = kAuxSc1, typename SinkOf = NoSink>  // kIt: loads per lane per round trip; AUX: the loads' cache bits
 __device__ __forceinline__ void merge_row_parts(const float* parts_o, const float* parts_ml, int NP, float* out,
-                                                int lane, int ostride = D, int mstride = 2, SinkOf sink_of = SinkOf()) {
+                                                int lane, int ostride = D, int mstride = 2, SinkOf sink_of = SinkOf(),
+                                                float* lse_row = nullptr) {
     constexpr float kNegInf = -__builtin_inff();
     constexpr int LPP = D / 4;              // lanes per part
     constexpr int PPR = merge_ppr<D>();     // D = 80 / 96: 1
@@ -540,14 +562,17 @@ __device__ __forceinline__ void merge_row_parts(const float* parts_o, const floa
         acc.w = xor32_pair(acc.w, false);
     }
     if (h) return;
-    if (const float* sink = sink_of()) {  // (wave-uniform)
+    const float* sink = sink_of();
+    if (sink) {  // (wave-uniform)
         bool dead;
         const float inv = sink_inv(M, L, *sink, dead);
         *(f32x4*)(out + d4) = sink_row(acc, inv, dead);
-        return;
+    } else {
+        const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
+        *(f32x4*)(out + d4) = acc * inv;
     }
-    const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
-    *(f32x4*)(out + d4) = acc * inv;
+    // (wave-uniform) `lse_row`: the row's entry of SplitArgsLse::lse, or null
+    if (lse_row && lane == 0) *lse_row = row_lse(M, L, sink ? *sink : kNegInf, row_dead(M, L));
 }
 
 // f16 chunk partials (SplitArgs::part_f16, second-launch merges): the
@@ -587,7 +612,8 @@ template <int D>
 constexpr int merge_ppr_h() { return 64 % (D / 8) == 0 ? 64 / (D / 8) : 1; }  // (4, 2, 1)
 template <int D, int kIt, typename SinkOf = NoSink>
 __device__ __forceinline__ void merge_row_parts_h(const uint16_t* parts_o, const float* parts_ml, int NP, float* out,
-                                                  int lane, int ostride, int mstride, SinkOf sink_of = SinkOf()) {
+                                                  int lane, int ostride, int mstride, SinkOf sink_of = SinkOf(),
+                                                  float* lse_row = nullptr) {
     constexpr float kNegInf = -__builtin_inff();
     constexpr int LPP = D / 8;
     constexpr int PPR = merge_ppr_h<D>();
@@ -635,16 +661,18 @@ __device__ __forceinline__ void merge_row_parts_h(const uint16_t* parts_o, const
         if constexpr (PPR >= 2) acc[e] = xor32_pair(acc[e], false);
     }
     if (h) return;
-    if (const float* sink = sink_of()) {  // (wave-uniform; L = sum_p w_p l_p is the row's whole sum at reference M)
+    const float* sink = sink_of();
+    if (sink) {  // (wave-uniform; L = sum_p w_p l_p is the row's whole sum at reference M)
         bool dead;
         const float inv = sink_inv(M, L, *sink, dead);
         *(f32x4*)(out + d8) = sink_row(f32x4{acc[0], acc[1], acc[2], acc[3]}, inv, dead);
         *(f32x4*)(out + d8 + 4) = sink_row(f32x4{acc[4], acc[5], acc[6], acc[7]}, inv, dead);
-        return;
+    } else {
+        const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
+        *(f32x4*)(out + d8) = f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
+        *(f32x4*)(out + d8 + 4) = f32x4{acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv};
     }
-    const float inv = L == 0.0f ? __builtin_nanf("") : 1.0f / L;  // L == 0 (row fully masked) -> NaN like the reference
-    *(f32x4*)(out + d8) = f32x4{acc[0] * inv, acc[1] * inv, acc[2] * inv, acc[3] * inv};
-    *(f32x4*)(out + d8 + 4) = f32x4{acc[4] * inv, acc[5] * inv, acc[6] * inv, acc[7] * inv};
+    if (lse_row && lane == 0) *lse_row = row_lse(M, L, sink ? *sink : kNegInf, row_dead(M, L));
 }
 
 // ---------------------------------------------------------------- merge launch
@@ -677,8 +705,8 @@ struct MergeGeomBase {
 // visible).  F16: the f16 partials of SplitArgs::part_f16 (merge_row_parts_h,
 // plain loads).
 constexpr int merge_span(int D) { return D > 256 ? 256 : D; }
-template <typename Geom, int D, int KIT, bool PLAIN, bool F16>
-__global__ __launch_bounds__(256) void fattn_chunk_merge_kernel(const SplitArgs a) {
+template <typename Geom, int D, int KIT, bool PLAIN, bool F16, typename A = SplitArgs>
+__global__ __launch_bounds__(256) void fattn_chunk_merge_kernel(const A a) {
     constexpr int W = merge_span(D);
     static_assert(D % W == 0 && (W == D || !F16), "");
     const int lane = threadIdx.x & 63;
@@ -693,16 +721,18 @@ __global__ __launch_bounds__(256) void fattn_chunk_merge_kernel(const SplitArgs 
     const int64_t slot0 = ((int64_t)iq3 * gridDim.y + ys) * a.n_chunks * Geom::rows + tm;  // chunk 0's row
     const int rq = div_R(a, p);
     const int riq2 = ik2 * a.rk2 + hs * a.R + (p - rq * a.R);
-    float* out = a.dst + (((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2) * D;
+    const int64_t row = ((int64_t)iq3 * a.NQ + qt * a.QPT + rq) * a.H + riq2;  // dst's row, lse's entry
+    float* out = a.dst + row * D;
     auto sink = [&]() -> const float* { return a.sinks ? a.sinks + riq2 : nullptr; };  // (one row, one head per wave)
+    float* lse_row = lse_at(a, row);  // (wave-uniform; a constant null without lse)
     if constexpr (F16) {
         merge_row_parts_h<D, KIT>((const uint16_t*)a.ws_o + slot0 * D, a.ws_ml + 2 * slot0, a.n_chunks, out, lane,
-                                  Geom::rows * D, 2 * Geom::rows, sink);
+                                  Geom::rows * D, 2 * Geom::rows, sink, lse_row);
     } else {
 #pragma unroll
-        for (int c = 0; c < D; c += W)
+        for (int c = 0; c < D; c += W)  // (rows of several spans: the first one writes the row's lse)
             merge_row_parts<W, KIT, PLAIN ? 0 : kAuxSc1>(a.ws_o + slot0 * D + c, a.ws_ml + 2 * slot0, a.n_chunks, out + c,
-                                                        lane, Geom::rows * D, 2 * Geom::rows, sink);
+                                                        lane, Geom::rows * D, 2 * Geom::rows, sink, c == 0 ? lse_row : nullptr);
     }
 }
 

@@ -38,7 +38,7 @@ ERRORS = {
 EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
-    "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows",
+    "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows", "fattn_ext_lse", "fattn_lse_merge",
 )
 OPT_MQ_ROWS_PER_WAVE = 1
 OPT_MQ_DISABLE = 2
@@ -118,6 +118,10 @@ def lib() -> C.CDLL:
         L.fattn_ext.argtypes = [C.POINTER(FattnParams), vp]
         L.fattn_ext_sinks.restype = C.c_int
         L.fattn_ext_sinks.argtypes = [C.POINTER(FattnParams), vp, vp]
+        L.fattn_ext_lse.restype = C.c_int
+        L.fattn_ext_lse.argtypes = [C.POINTER(FattnParams), vp, vp, vp]
+        L.fattn_lse_merge.restype = C.c_int
+        L.fattn_lse_merge.argtypes = [vp, vp, C.c_int32, i64, C.c_int32, i64, i64, vp, C.c_int32, vp, vp, vp]
         L.fattn_ext_events.restype = C.c_int
         L.fattn_ext_events.argtypes = [C.POINTER(FattnParams), vp, vp, vp]
         L.fattn_ext_f16_launch.restype = C.c_int
@@ -267,6 +271,7 @@ def describe(p: FattnParams) -> str:
 
 
 NO_SINKS = object()   # Attention.retarget(sinks=NO_SINKS): back to a launch without sinks
+NO_LSE = object()     # Attention.retarget(lse=NO_LSE): back to a launch that writes no log-sum-exp
 
 
 def _sinks_ptr(sinks, n_head: int) -> Optional[int]:
@@ -285,7 +290,23 @@ def _sinks_ptr(sinks, n_head: int) -> Optional[int]:
     return _tptr(sinks)
 
 
-def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sinks=None):
+def _lse_ptr(lse, n_rows: int) -> Optional[int]:
+    """lse: None, a raw device pointer (taken on trust), or a torch tensor:
+    contiguous float32 on the GPU with exactly n_rows = S * n_q * H values -- a
+    host tensor or a short one would be an illegal or out-of-bounds device write."""
+    if lse is None or isinstance(lse, int):
+        return lse
+    import torch
+    if lse.dtype != torch.float32 or not lse.is_contiguous():
+        raise ValueError("lse: a contiguous float32 tensor, one value per output row [S][n_q][H]")
+    if not lse.is_cuda:
+        raise ValueError("lse: a device tensor (this one is on the host)")
+    if lse.numel() != n_rows:
+        raise ValueError(f"lse: {lse.numel()} values for the launch's {n_rows} output rows (S * n_q * H)")
+    return _tptr(lse)
+
+
+def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sinks=None, lse=None):
     """GGML_OP_FLASH_ATTN_EXT on the GPU (replaces flash_attn_ext_f16, src/flash-llama.h:5-32).
     ev_begin/ev_end: optional raw hipEvent_t handles recorded around the main kernel.
     sinks: ggml's src[4], one raw f32 logit per q head of THIS launch that joins
@@ -293,8 +314,19 @@ def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sink
     or a torch f32 tensor of p.q.ne[2] values (a head shard passes
     shard.HeadShard.sink_slice(sinks)); None is fattn_ext.  The plan, the
     workspace and describe(p) do not depend on it.  There is no events variant:
-    sinks with ev_begin / ev_end raises ValueError."""
-    if sinks is not None:
+    sinks with ev_begin / ev_end raises ValueError.
+    lse: where the rows' natural-log log-sum-exp goes (include/fattn.h,
+    fattn_ext_lse) -- a device pointer or a contiguous torch f32 tensor of exactly
+    S * n_q * H values, dst's layout without its last dim; with sinks the sink is
+    one of its terms.  None writes none.  Like sinks it changes no plan and has no
+    events variant (ValueError)."""
+    if lse is not None:
+        if ev_begin is not None or ev_end is not None:
+            raise ValueError("flash_attn_ext: lse cannot be combined with ev_begin / ev_end")
+        sptr = _sinks_ptr(sinks, int(p.q.ne[2]))
+        lptr = _lse_ptr(lse, int(p.q.ne[1]) * int(p.q.ne[2]) * int(p.q.ne[3]))
+        _check(lib().fattn_ext_lse(C.byref(p), sptr, lptr, _stream(stream)), "fattn_ext_lse")
+    elif sinks is not None:
         if ev_begin is not None or ev_end is not None:
             raise ValueError("flash_attn_ext: sinks cannot be combined with ev_begin / ev_end")
         ptr = _sinks_ptr(sinks, int(p.q.ne[2]))
@@ -303,6 +335,44 @@ def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sink
         _check(lib().fattn_ext(C.byref(p), _stream(stream)), "fattn_ext")
     else:
         _check(lib().fattn_ext_events(C.byref(p), _stream(stream), ev_begin, ev_end), "fattn_ext_events")
+
+
+def lse_merge(outs, lses, dst, sinks=None, lse_out=None, n_head=None, stream=None):
+    """fattn_lse_merge (include/fattn.h): merge P normalised partial outputs of
+    the same rows over disjoint key ranges by their log-sum-exps -- what
+    flash_attn_ext(..., lse=) wrote on each range, e.g. after
+    shard.gather_parts().  outs: f32 [P, ..., dv], lses: f32 [P, ...] (device
+    tensors whose parts are contiguous; the part strides pass through, so a
+    slice of a padded buffer works); dst: contiguous f32 [..., dv], not aliasing
+    outs.  sinks: None, or a contiguous f32 tensor of n_head raw logits that join
+    the merged denominator once (rows are in dst's [S][n_q][H] order: row r is
+    head r % n_head; n_head defaults to sinks.numel()).  lse_out: None or a
+    contiguous f32 tensor of one value per row.  Returns dst."""
+    import torch
+    for name, t in (("outs", outs), ("lses", lses), ("dst", dst)):
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"lse_merge: {name} must be a float32 device tensor")
+    if outs.dim() < 2 or lses.dim() < 1 or outs.shape[0] != lses.shape[0]:
+        raise ValueError("lse_merge: outs is [P, ..., dv] and lses [P, ...] with the same P")
+    P, dv = int(outs.shape[0]), int(outs.shape[-1])
+    n_rows = outs[0].numel() // dv
+    if not outs[0].is_contiguous() or not lses[0].is_contiguous() or not dst.is_contiguous():
+        raise ValueError("lse_merge: every part of outs / lses, and dst, must be contiguous")
+    if lses[0].numel() != n_rows or dst.numel() != n_rows * dv:
+        raise ValueError("lse_merge: lses holds one value per row of outs, dst one part's shape")
+    sptr = None
+    if sinks is not None:
+        if sinks.dtype != torch.float32 or not sinks.is_contiguous() or not sinks.is_cuda:
+            raise ValueError("lse_merge: sinks must be a contiguous float32 device tensor")
+        n_head = int(sinks.numel()) if n_head is None else int(n_head)
+        if sinks.numel() != n_head or n_head < 1:
+            raise ValueError("lse_merge: sinks holds n_head values")
+        sptr = _tptr(sinks)
+    lptr = _lse_ptr(lse_out, n_rows)
+    _check(lib().fattn_lse_merge(_tptr(outs), _tptr(lses), P, n_rows, dv, int(outs.stride(0)) if P > 1 else n_rows * dv,
+                                 int(lses.stride(0)) if P > 1 else n_rows, sptr, int(n_head or 0), _tptr(dst), lptr,
+                                 _stream(stream)), "fattn_lse_merge")
+    return dst
 
 
 # ------------------------------------------------------------------ torch helpers
@@ -391,9 +461,10 @@ class Attention:
 
     def __init__(self, q: View, k: View, v: View, mask: Optional[View], dst, scale: float, kv_chunk: int = 0, *,
                  max_bias: float = 0.0, logit_softcap: float = 0.0, n_head_total: int = 0, head_first: int = 0,
-                 sinks=None):
+                 sinks=None, lse=None):
         import torch
         self.sinks = sinks   # ggml's src[4] (flash_attn_ext): a pointer, a torch f32 tensor (kept alive here) or None
+        self.lse = lse       # where the rows' log-sum-exp goes (flash_attn_ext): a pointer, a torch f32 tensor or None
         self.p = ext_params(q, k, v, mask, _tptr(dst), scale, 0, 0, kv_chunk, max_bias=max_bias,
                             logit_softcap=logit_softcap, n_head_total=n_head_total, head_first=head_first)
         ws = workspace_size(self.p)
@@ -403,10 +474,15 @@ class Attention:
         self.p.workspace_bytes = self.workspace.numel()
         self.dst = dst
 
-    def retarget(self, q=None, k=None, v=None, dst=None, mask=None, sinks=None):
+    def retarget(self, q=None, k=None, v=None, dst=None, mask=None, sinks=None, lse=None):
         """Point the same call at other buffers with identical shapes/strides.
         None keeps what the call has.  sinks: another pointer or tensor of
-        q.ne[2] f32 values, or fattn.NO_SINKS to launch without sinks again."""
+        q.ne[2] f32 values, or fattn.NO_SINKS to launch without sinks again.
+        lse: another pointer or tensor of S * n_q * H f32 values, or fattn.NO_LSE."""
+        if lse is NO_LSE:
+            self.lse = None
+        elif lse is not None:
+            self.lse = lse
         if sinks is NO_SINKS:
             self.sinks = None
         elif sinks is not None:
@@ -426,7 +502,7 @@ class Attention:
         return describe(self.p)
 
     def __call__(self, stream=None, ev_begin=None, ev_end=None):
-        flash_attn_ext(self.p, stream, ev_begin, ev_end, sinks=self.sinks)
+        flash_attn_ext(self.p, stream, ev_begin, ev_end, sinks=self.sinks, lse=self.lse)
         return self.dst
 
 

@@ -125,3 +125,54 @@ def gather_heads(local, group=None, buf=None, out=None):
     perm = tuple(range(1, 1 + nl)) + (1 + nl, 2 + nl, 0, 3 + nl, 4 + nl)
     out.view(*lead, S, NQ, world, Hl, D).copy_(buf.permute(*perm))
     return out
+
+
+# ------------------------------------------------------------------ KV (context) sharding
+# Heads do not split an MLA op (one kv head) or a cache too long for one GPU:
+# there the KEYS split.  Each rank attends to its own contiguous key range
+# and returns (out, lse) -- fattn.flash_attn_ext(..., lse=) -- and one
+# all-gather plus fattn.lse_merge() give the exact result (include/fattn.h,
+# fattn_lse_merge).  Sinks go to the merge, once, never to the shard launches.
+
+def kv_ranges(N: int, world: int, align: int = 32):
+    """[(lo, hi)] * world: contiguous key ranges that partition [0, N), every
+    boundary a multiple of `align`, the last range taking the remainder.  align =
+    32 keeps the 16-byte paths and whole ggml blocks; every range is non-empty,
+    so N must hold at least `world` aligned pieces."""
+    if world <= 0 or align <= 0:
+        raise ValueError(f"kv_ranges: world {world}, align {align}")
+    per = N // world // align * align
+    if per <= 0:
+        raise ValueError(f"kv_ranges: {N} keys do not give {world} ranges of a multiple of {align}")
+    return [(w * per, (w + 1) * per if w + 1 < world else N) for w in range(world)]
+
+
+def kv_views(k, v, mask, lo: int, hi: int):
+    """The FLASH_ATTN_EXT sub-problem over keys [lo, hi), zero-copy: `narrow` on
+    ggml dim 1 of K and V and on dim 0 of the mask (None stays None).  V moves
+    by the same rows as K, so an MLA V that is a view of K (v = k + off, same
+    strides) stays one.  The range that ends at the last key keeps the mask
+    rows' padding past it (rows are read in dword pieces).  lo a multiple of 32
+    keeps every alignment rule of the unsharded views."""
+    N = int(k.ne[1])
+    if not 0 <= lo < hi <= N:
+        raise ValueError(f"kv_views: keys [{lo}, {hi}) of {N}")
+    kk, vv = narrow(k, 1, lo, hi - lo), narrow(v, 1, lo, hi - lo)
+    mm = None
+    if mask is not None:
+        mm = narrow(mask, 0, lo, (int(mask.ne[0]) if hi == N else hi) - lo)
+    return kk, vv, mm
+
+
+def gather_parts(out, lse, group=None):
+    """out: this rank's [..., dv] output over its key range, lse: its [...]
+    log-sum-exps (both contiguous).  Returns ([world, ..., dv], [world, ...]) on
+    every rank by one all_gather_into_tensor each: fattn.lse_merge()'s inputs."""
+    import torch
+    import torch.distributed as dist
+    world = dist.get_world_size(group)
+    outs = torch.empty((world,) + tuple(out.shape), dtype=out.dtype, device=out.device)
+    lses = torch.empty((world,) + tuple(lse.shape), dtype=lse.dtype, device=lse.device)
+    dist.all_gather_into_tensor(outs.view(-1), out.contiguous().view(-1), group=group)
+    dist.all_gather_into_tensor(lses.view(-1), lse.contiguous().view(-1), group=group)
+    return outs, lses

@@ -44,6 +44,11 @@
 //                        gets the raw extra logit BASE + 0.25 * (h % 8) in its softmax
 //                        denominator (the global head index under --ngpu: device g passes
 //                        its own slice); the CPU reference applies the same
+//   --lse                also the rows' log-sum-exp (fattn_ext_lse): the CPU reference computes it
+//                        (with --sinks the sink is one of its terms), the GPU path launches
+//                        fattn_ext_lse and prints `lse max abs err` beside the verification line
+//                        (passes at 1e-4 of max(1, |lse|)); with --cpu-only --dump FILE it goes to FILE.lse.
+//                        One device; the call goes through the fattn_params form
 //   --set-rows           build the K / V caches with fattn_set_rows (GGML_OP_SET_ROWS) from the
 //                        f32 K / V instead of fattn_quantize / the host's f16 rounding: row n
 //                        goes to slot perm[n] of a seeded permutation, and the CPU reference
@@ -147,10 +152,44 @@ void random_fill(std::vector<float>& a) {
 // sinks (null: none): ggml's src[4], one raw logit per head joining (M, S) after
 // the row's last key by ggml's statement; the row is then the plain row times
 // g = vs * S_plain / S -- the factor form, so P keeps the plain row's f16 rounding
+bool dump_floats(const char* path, const std::vector<float>& x) {
+    FILE* f = fopen(path, "wb");
+    if (!f || fwrite(x.data(), sizeof(float), x.size(), f) != x.size()) {
+        fprintf(stderr, "cannot write %s\n", path);
+        return false;
+    }
+    fclose(f);
+    return true;
+}
+
+// --lse: the natural-log log-sum-exp of a row with running max M and sum S =
+// sum exp(score - M); with a sink the sink is one more term, taken at
+// max(M, sink).  A row without a live key (M = -inf): the sink, or -inf
+float row_lse(float M, float S, const float* sink) {
+    if (M == -INFINITY) return sink ? *sink : -INFINITY;
+    if (!sink || *sink == -INFINITY) return M + logf(S);
+    return *sink > M ? *sink + logf(S * expf(M - *sink) + 1.0f) : M + logf(S + expf(*sink - M));
+}
+
+// `lse max abs err` of --lse over rows x heads; the pass mark is on the error relative to max(1, |ref|): 1e-4
+bool lse_check(const std::vector<float>& ref, const std::vector<float>& got, const std::vector<int>& rows, int H) {
+    float worst = 0.0f, worst_abs = 0.0f;
+    for (int r : rows)
+        for (int h = 0; h < H; h++) {
+            const float a = ref[(size_t)r * H + h], b = got[(size_t)r * H + h];
+            float e = fabsf(a - b) / std::max(1.0f, fabsf(a));
+            if (a == b) e = 0.0f;  // (both -inf)
+            worst = std::isnan(e) ? INFINITY : std::max(worst, e);
+            worst_abs = a == b ? worst_abs : std::isnan(e) ? INFINITY : std::max(worst_abs, fabsf(a - b));
+        }
+    printf("lse max abs err %.3g (%.3g of max(1, |lse|), tol 1e-04): %s\n", worst_abs, worst, worst <= 1e-4f ? "PASS" : "FAIL");
+    return worst <= 1e-4f;
+}
+
 void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, const std::vector<float>& v,
                    const std::vector<float>& mask, std::vector<float>& out, int N, int D, int H, int Hkv, float scale,
                    const std::vector<int>& rows, int threads = 1, float max_bias = 0.0f, float softcap = 0.0f,
-                   const std::vector<float>* sinks = nullptr) {
+                   const std::vector<float>* sinks = nullptr, std::vector<float>* lse = nullptr) {
     const int r = H / Hkv;
     int n2 = 1;
     while (n2 * 2 <= H) n2 *= 2;
@@ -206,6 +245,7 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
                     for (int i = 0; i < N; i++) s[i] = 0.0f;
                 }
             }
+            if (lse) (*lse)[(size_t)row * H + h] = row_lse(M, S, sinks ? &(*sinks)[h] : nullptr);
             float* o = out.data() + ((size_t)row * H + h) * D;
             for (int c = 0; c < D; c++) {
                 float acc = 0.0f;
@@ -299,7 +339,8 @@ int parse_type(const std::string& s) {
 constexpr int kMlaDK = 576, kMlaDV = 512;
 
 void cpu_reference_mla(const std::vector<float>& q, const std::vector<float>& kv, const std::vector<float>& mask,
-                       std::vector<float>& out, int N, int H, int NQ, int v_off, float scale, int threads) {
+                       std::vector<float>& out, int N, int H, int NQ, int v_off, float scale, int threads,
+                       std::vector<float>* lse = nullptr) {
     std::vector<float> qh(q.size()), kh(kv.size());
     for (size_t i = 0; i < q.size(); i++) qh[i] = rh(q[i]);
     for (size_t i = 0; i < kv.size(); i++) kh[i] = rh(kv[i]);
@@ -326,6 +367,7 @@ void cpu_reference_mla(const std::vector<float>& q, const std::vector<float>& kv
                 }
             }
             for (int i = 0; i < N; i++) s[i] = rh(expf(s[i] - M) / S);
+            if (lse) (*lse)[(size_t)row * H + h] = row_lse(M, S, nullptr);
             float* o = out.data() + ((size_t)row * H + h) * kMlaDV;
             for (int c = 0; c < kMlaDV; c++) {
                 float acc = 0.0f;
@@ -395,7 +437,7 @@ void dequant_host_q80_q40(int type, const uint8_t* src, float* dst, int D, int64
 // quantised (fattn_quantize; on the host with --cpu-only), the reference takes
 // the blocks dequantised on the host, and V is the view v_off / 32 blocks in.
 int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mask_kind, bool cpu_only, int iters, float tol,
-            const char* dump) {
+            const char* dump, bool use_lse) {
     const bool quant = kv_type == FATTN_TYPE_Q8_0 || kv_type == FATTN_TYPE_Q4_0;
     if (kv_type != FATTN_TYPE_F16 && !quant) {
         fprintf(stderr, "--mla: --kv-type f16|q8_0|q4_0\n");
@@ -437,8 +479,10 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     }
     const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
     std::vector<float> ref((size_t)kMlaDV * H * NQ), got(ref.size());
-    cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads);
+    std::vector<float> lse_ref((size_t)H * NQ), lse_got(lse_ref.size());
+    cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads, use_lse ? &lse_ref : nullptr);
     print_array("Reference", ref.data(), 16);
+    if (use_lse) print_array("Reference LSE", lse_ref.data(), std::min(16, H * NQ));
     if (cpu_only) {
         if (dump) {
             FILE* f = fopen(dump, "wb");
@@ -447,6 +491,7 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
                 return 2;
             }
             fclose(f);
+            if (use_lse && !dump_floats((std::string(dump) + ".lse").c_str(), lse_ref)) return 2;
         }
         return 0;
     }
@@ -462,8 +507,9 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
         for (int i = 0; i < N; i++) mask16[(size_t)r * Np + i] = f2h(mask[(size_t)r * N + i]);
     hipStream_t st;
     HIP_CHECK(hipStreamCreate(&st));
-    float *d_q, *d_out;
+    float *d_q, *d_out, *d_lse = nullptr;
     void *d_kv, *d_mask, *d_ws;
+    if (use_lse) HIP_CHECK(hipMalloc(&d_lse, 4 * lse_got.size()));
     HIP_CHECK(hipMalloc(&d_q, 4 * query.size()));
     HIP_CHECK(hipMalloc(&d_out, 4 * got.size()));
     HIP_CHECK(hipMalloc(&d_kv, blocks.size()));
@@ -489,7 +535,7 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     int rc = fattn_workspace_init(d_ws, ws_bytes, st);
     p.workspace = d_ws;
     p.workspace_bytes = ws_bytes;
-    rc = rc ? rc : fattn_ext(&p, st);
+    rc = rc ? rc : fattn_ext_lse(&p, nullptr, d_lse, st);  // (d_lse null: fattn_ext)
     if (rc) {
         fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
         return 2;
@@ -501,7 +547,7 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     std::vector<float> times;
     for (int it = 0; it < iters; it++) {
         HIP_CHECK(hipEventRecord(start, st));
-        rc = fattn_ext(&p, st);
+        rc = fattn_ext_lse(&p, nullptr, d_lse, st);
         HIP_CHECK(hipEventRecord(stop, st));
         HIP_CHECK(hipEventSynchronize(stop));
         if (rc) {
@@ -540,7 +586,14 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
            head_idx, dim_idx);
     printf("checked %d of %d query rows x %d heads; n_q %d, 1 GPU(s)\n", NQ, NQ, H, NQ);
     printf("normwise rel err %.3g (tol %.1g): %s\n", worst_rel, tol, worst_rel <= tol ? "PASS" : "FAIL");
-    return worst_rel <= tol ? 0 : 1;
+    bool lse_ok = true;
+    if (use_lse) {
+        HIP_CHECK(hipMemcpy(lse_got.data(), d_lse, 4 * lse_got.size(), hipMemcpyDeviceToHost));
+        std::vector<int> all_rows(NQ);
+        for (int r = 0; r < NQ; r++) all_rows[r] = r;
+        lse_ok = lse_check(lse_ref, lse_got, all_rows, H);
+    }
+    return worst_rel <= tol && lse_ok ? 0 : 1;
 }
 
 }  // namespace
@@ -557,7 +610,7 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
 int main(int argc, const char* argv[]) {
     int kv_size = 512, num_warps = 8, head_dim = 128, num_heads = 32, num_kv_heads = 8, iters = 20;
     int kv_type = FATTN_TYPE_F16, n_q = 1, check_rows = 64, ngpu = 1;
-    bool parallel_kv = true, cpu_only = false;
+    bool parallel_kv = true, cpu_only = false, use_lse = false;
     std::string mask_kind = "random";
     const char* dump = nullptr;
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
@@ -591,6 +644,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--softcap") softcap = (float)atof(next());
         else if (a == "--sinks") sink_base = (float)atof(next()), use_sinks = true;
         else if (a == "--mla") mla = true;
+        else if (a == "--lse") use_lse = true;
         else if (a == "--v-off") mla_v_off = atoi(next());
         else if (a == "--mask") {
             mask_kind = next();
@@ -628,12 +682,17 @@ int main(int argc, const char* argv[]) {
         printf("invalid num_warps, should be 2, 4, 8\n");  // kernel_test.h:176-178 (informational)
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
     // (the model family's smallest head count unless --heads says otherwise)
-    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump);
+    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump, use_lse);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)
     if (use_sinks) parallel_kv = false;                  // (nor the sinks: fattn_ext_sinks takes fattn_params)
     if (set_rows) parallel_kv = false;                   // (SET_ROWS writes rows: no transposed V)
+    if (use_lse) parallel_kv = false;                    // (fattn_ext_lse takes fattn_params)
+    if (use_lse && ngpu > 1) {
+        fprintf(stderr, "--lse runs on one device\n");
+        return 2;
+    }
 
     const int D = head_dim, H = num_heads, Hkv = num_kv_heads, N = kv_size, NQ = n_q;
     const float scale = 1.0f / sqrtf((float)D);
@@ -692,9 +751,11 @@ int main(int argc, const char* argv[]) {
     const std::vector<float>* sinks_ref = use_sinks ? &sinks : nullptr;
 
     if (cpu_only) {  // BASELINE config 1: kernel_test.h:50-66 on the host, nothing else
-        std::vector<float> out((size_t)D * H * NQ);
-        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref);
+        std::vector<float> out((size_t)D * H * NQ), lse((size_t)H * NQ);
+        cpu_reference(query, key, value, mask, out, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref,
+                      use_lse ? &lse : nullptr);
         print_array("Reference", out.data(), std::min(16, D * H));
+        if (use_lse) print_array("Reference LSE", lse.data(), std::min(16, H * NQ));
         if (dump) {
             FILE* f = fopen(dump, "wb");
             if (!f || fwrite(out.data(), sizeof(float), out.size(), f) != out.size()) {
@@ -702,6 +763,7 @@ int main(int argc, const char* argv[]) {
                 return 2;
             }
             fclose(f);
+            if (use_lse && !dump_floats((std::string(dump) + ".lse").c_str(), lse)) return 2;
         }
         return 0;
     }
@@ -810,7 +872,9 @@ int main(int argc, const char* argv[]) {
 
     // CPU reference (kernel_test.h:50-66) on the checked rows
     std::vector<float> qkv((size_t)D * H * NQ, 0.0f), qkv_gpu((size_t)D * H * NQ);
-    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref);
+    std::vector<float> lse_ref((size_t)H * NQ), lse_gpu(lse_ref.size());
+    cpu_reference(query, kref, vref, mask, qkv, N, D, H, Hkv, scale, rows, threads, max_bias, softcap, sinks_ref,
+                  use_lse ? &lse_ref : nullptr);
     print_array("Reference", qkv.data(), 16);
 
     // ---- per device: its head shard (kv heads [g Hkv/G, (g+1) Hkv/G) and their
@@ -830,6 +894,7 @@ int main(int argc, const char* argv[]) {
         hipStream_t st;
         float *q, *out, *gather;
         float* sinks;  // this device's heads' sinks (--sinks), or null
+        float* lse;    // [n_q][Hl] log-sum-exps (--lse), or null
         void *k, *v, *mask, *ws;
         size_t ws_bytes;
         fattn_params p;
@@ -855,6 +920,8 @@ int main(int argc, const char* argv[]) {
         HIP_CHECK(hipMemcpyAsync(d.k, kbytes.data() + kvb * g, kvb, hipMemcpyHostToDevice, d.st));
         HIP_CHECK(hipMemcpyAsync(d.v, vbytes.data() + kvb * g, kvb, hipMemcpyHostToDevice, d.st));
         HIP_CHECK(hipMemcpyAsync(d.mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, d.st));
+        d.lse = nullptr;
+        if (use_lse) HIP_CHECK(hipMalloc(&d.lse, sizeof(float) * NQ * Hl));
         d.sinks = nullptr;
         if (use_sinks) {  // the slice of the model's sinks that belongs to this device's q heads
             HIP_CHECK(hipMalloc(&d.sinks, sizeof(float) * Hl));
@@ -908,7 +975,7 @@ int main(int argc, const char* argv[]) {
             int rc;
             if (parallel_kv)
                 rc = fattn_row(d.q, d.k, d.v, d.mask, d.ws, d.ws_bytes, d.out, D, N, H, scale, D * N, r_kv_heads, d.st);
-            else if (NQ == 1 && G == 1 && has_mask && !op_xf && !use_sinks)
+            else if (NQ == 1 && G == 1 && has_mask && !op_xf && !use_sinks && !use_lse)
                 rc = fattn_ext_f16_launch(d.q, d.k, d.v, d.mask, d.out, scale,
                                           D, 1, H, 1,
                                           D, N, Hkv, 1,
@@ -918,7 +985,8 @@ int main(int argc, const char* argv[]) {
                                           D, H, 1, 1,
                                           kv_type, kv_type, d.ws, d.ws_bytes, d.st);
             else
-                rc = use_sinks ? fattn_ext_sinks(&d.p, d.sinks, d.st) : fattn_ext(&d.p, d.st);
+                rc = use_lse ? fattn_ext_lse(&d.p, d.sinks, d.lse, d.st)
+                     : use_sinks ? fattn_ext_sinks(&d.p, d.sinks, d.st) : fattn_ext(&d.p, d.st);
             if (rc) return rc;
         }
         if (G > 1) {
@@ -1007,8 +1075,13 @@ int main(int argc, const char* argv[]) {
            max_diff, row_idx, head_idx, dim_idx);
     printf("checked %zu of %d query rows x %d heads; n_q %d, %d GPU(s)\n", rows.size(), NQ, H, NQ, G);
     printf("normwise rel err %.3g (tol %.1g): %s\n", worst_rel, tol, worst_rel <= tol ? "PASS" : "FAIL");
+    bool lse_ok = true;
+    if (use_lse) {
+        HIP_CHECK(hipMemcpy(lse_gpu.data(), dv[0].lse, 4 * lse_gpu.size(), hipMemcpyDeviceToHost));
+        lse_ok = lse_check(lse_ref, lse_gpu, rows, H);
+    }
     for (int g = 0; g < G; g++) {
         if (G > 1) RCCL_CHECK(ncclCommDestroy(comms[g]));
     }
-    return worst_rel <= tol ? 0 : 1;
+    return worst_rel <= tol && lse_ok ? 0 : 1;
 }

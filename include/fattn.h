@@ -317,6 +317,62 @@ int fattn_ext(const fattn_params* p, void* stream);
  * the chunk merge of a split-KV plan); the tile loops are untouched. */
 int fattn_ext_sinks(const fattn_params* p, const float* sinks, void* stream);
 
+/* fattn_ext_sinks(p, sinks, stream) that also writes the rows' log-sum-exp: the
+ * one number per row that lets a caller combine launches over pieces of one KV
+ * range (KV-sharded decode across GPUs, a prefix cache plus a tail) with
+ * fattn_lse_merge below.
+ *   lse    device pointer to S * n_q * H contiguous f32 values, [S][n_q][H]:
+ *          dst's layout without its last dim (the MLA shape too).  4-byte
+ *          aligned, else FATTN_ERR_ALIGNMENT -- checked beside sinks, after the
+ *          params: invalid params return what fattn_ext returns for them,
+ *          whatever lse is.  NULL: exactly fattn_ext_sinks -- same code path,
+ *          same bits.
+ * Each entry is the natural-log log-sum-exp of the row's FINAL scores -- after
+ * scale, logit_softcap and slope(h) * mask, the scores whose softmax weights V.
+ *   - sinks != NULL: the sink is one of the terms, so lse is the log of the
+ *     denominator dst was divided by and dst * exp(lse) is the unnormalised row
+ *     either way.  A KV-sharded caller passes sinks = NULL to the shard launches
+ *     and gives the sinks to the merge, once.
+ *   - a row whose mask is -inf everywhere: lse = -inf (dst NaN, as without lse)
+ *     without sinks, lse = sinks[h] (dst zeros) with sinks; -inf is written by
+ *     selection, never computed.
+ * dst is bit for bit what the launch without lse writes.  The plan, the grid,
+ * the workspace size and fattn_describe(p) stay functions of p alone; every plan
+ * and every cache type serves it: one lane per output row stores one float in
+ * the epilogue that normalises into dst, behind the row guards of the dst
+ * store.  (Under fattn_debug.h's diagnostic in-kernel chunk merge, a row that
+ * option leaves NaN -- its own documentation -- has an undefined lse.)  No events and
+ * no positional form; fattn_row is unchanged. */
+int fattn_ext_lse(const fattn_params* p, const float* sinks, float* lse, void* stream);
+
+/* The merge of n_parts normalised partial outputs of one set of rows over
+ * disjoint key ranges, by their log-sum-exps (the fa_reduce rule the kernels
+ * use between split-KV chunks, from outside).
+ *   outs  part p at outs + p * out_part_stride floats, f32 [n_rows][dv]
+ *   lses  part p at lses + p * lse_part_stride floats, f32 [n_rows]
+ *         -- what an all-gather of per-rank (dst, lse) yields.  Rows in dst's
+ *         [S][n_q][H] order: row r belongs to head r % n_head.
+ *   sinks NULL, or n_head raw f32 logits indexed like fattn_ext_sinks' (n_head
+ *         is read only then): the sink joins the merged denominator, once.
+ *   dst   f32 [n_rows][dv]; must not alias outs.  lse_out: f32 [n_rows] or NULL.
+ * Per row: M = max_p lse_p, w_p = exp(lse_p - M), L = sum_p w_p,
+ *     dst = sum_p w_p out_p / L,   lse_out = M + ln L.
+ * A part with lse_p = -inf contributes nothing, by selection: its out_p row
+ * (NaN) never reaches the sum.  With a finite sink s, L gains exp(s - M), taken
+ * at max(M, s).  All parts -inf: a NaN row and lse_out = -inf without sinks, a
+ * zero row and lse_out = s with sinks.  n_parts = 1 without sinks copies bit
+ * for bit.
+ * Validated before anything launches: NULL outs / lses / dst, n_parts outside
+ * 1 .. 64, n_rows outside 1 .. 2^31 - 1, n_head < 1 with sinks
+ * FATTN_ERR_INVALID_ARG; dv no multiple of 4 in 4 .. 512
+ * FATTN_ERR_UNSUPPORTED_HEAD_DIM; out_part_stride < n_rows * dv or no multiple
+ * of 4, lse_part_stride < n_rows FATTN_ERR_BAD_STRIDE; outs / dst not 16-byte
+ * aligned, lses / lse_out / sinks not 4-byte aligned FATTN_ERR_ALIGNMENT.
+ * Stream-ordered; allocates nothing, needs no workspace, capturable. */
+int fattn_lse_merge(const float* outs, const float* lses, int32_t n_parts, int64_t n_rows, int32_t dv,
+                    int64_t out_part_stride, int64_t lse_part_stride, const float* sinks, int32_t n_head,
+                    float* dst, float* lse_out, void* stream);
+
 /* flash-llama.h:7-32 argument list (K and V share nb11..nb13, flash-llama.h:123-125;
  * mask rows padded to ne31, nb31 bytes per row; one mask plane -- the list has
  * no ne32 / ne33 -- as for fattn_row below).  The one ne10 is K's and V's row
