@@ -42,7 +42,7 @@ $(LIBDIR)/libfattn_stamps.so: $(STAMP_OBJS)
 	$(HIPCC) $(HIPFLAGS) -shared $(STAMP_OBJS) -o $@
 
 # diagnostic / A-B variant of the library (never the product):
-#   make variant VAR=nr3 VFLAGS=-DFATTN_BDP_MAX_RAW=3  ->  lib/libfattn_nr3.so
+#   make variant VAR=diag_notail VFLAGS=-DFATTN_DIAG_NOTAIL  ->  lib/libfattn_diag_notail.so
 VAR ?= var
 VFLAGS ?=
 VAR_OBJS := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/$(VAR)_%.o,$(CSRC))

@@ -39,10 +39,7 @@ namespace fattn {
 
 constexpr int kBdpKeys = 64;      // keys per tile (two 32-key halves)
 constexpr int kBdpCompute = 4;    // waves 0..3 compute, 4..7 build
-#ifndef FATTN_BDP_MAX_RAW
-#define FATTN_BDP_MAX_RAW 5
-#endif
-constexpr int kBdpMaxRaw = FATTN_BDP_MAX_RAW;  // (diagnostic builds lower it for A/B runs)
+constexpr int kBdpMaxRaw = 5;     // raw tiles in flight, at most (BdpCfg::nRaw)
 
 template <int KT, int D>
 struct BdpCfg {
@@ -66,32 +63,16 @@ struct BdpCfg {
     static constexpr int qOff = pair;                            // Q's f32 rows before the loop (pair 1)
     static constexpr int NI = (kvRaw + 1023) / 1024;             // 1-KiB DMA instructions per K (or V) tile
     // Raw instructions j = 0 .. T - 1 (K then V) of a tile, issued by the build
-    // waves, j -> 4 + j % 4.  (FATTN_BDP_ALL_ISSUE, A/B builds: from 8 of them
-    // on ALL eight waves issue them, j -> wave j % 8, the remainder to the
-    // build waves first -- or one more to every compute wave when more than
-    // four are left -- so the compute waves' counts are equal: their waits sit
-    // right behind the youngest group and must count it exactly.  The issue
-    // of the build waves alone stalls ~1.2 us per tile on config 5 (a full
-    // memory pipeline), but spreading it over all waves made the compute
-    // waves stall as long: 25.1 vs 24.4 us, profiles/r04_e.)  The smallest
-    // per-role count counts the waits (a build wave with one more instruction
-    // also waits for one of a younger group: fattn_pf.h).
+    // waves, j -> 4 + j % 4; the compute waves issue none.  (The issue of the
+    // build waves alone stalls ~1.2 us per tile on config 5 (a full memory
+    // pipeline), but spreading it over all eight waves made the compute waves
+    // stall as long: 25.1 vs 24.4 us, profiles/r04_e.)  The smallest per-role
+    // count counts the waits (a build wave with one more instruction also
+    // waits for one of a younger group: fattn_pf.h).
     static constexpr int T = 2 * NI;
-#ifdef FATTN_BDP_ALL_ISSUE
-    static constexpr bool kAll = T >= 8;  // diagnostic build only (A/B)
-#else
-    static constexpr bool kAll = false;
-#endif
-    static constexpr int kBase = T / 8, kRem = T % 8;
-    static constexpr int owner(int j) {
-        return !kAll ? 4 + j % 4
-               : j < 8 * kBase ? j % 8
-               : kRem <= 4     ? 4 + (j - 8 * kBase)
-               : j - 8 * kBase < 4 ? j - 8 * kBase
-                                   : 4 + (j - 8 * kBase - 4);
-    }
-    static constexpr int R_c = kAll ? kBase + (kRem > 4 ? 1 : 0) : 0;  // per compute wave (exact)
-    static constexpr int R_b = kAll ? kBase : T / 4;                   // per build wave (smallest)
+    static constexpr int owner(int j) { return 4 + j % 4; }
+    static constexpr int R_c = 0;      // raw instructions of a tile per compute wave (exact)
+    static constexpr int R_b = T / 4;  // per build wave (smallest)
     static constexpr int NM = 2;                                 // mask DMA instructions per compute wave and tile
     static_assert(kBdRows * D * 4 <= pair, "Q rows in the second pair's place");
     static_assert(nRaw >= 3, "a compute wave's raw s + 2 is older than its mask s + 1");
@@ -127,14 +108,9 @@ constexpr int kBdpHpw = 2;  // half-blocks per build wave, at most (D <= 128)
 // the compute waves' operand reads conflict-free; fattn_bd.h / fattn_pf.h's
 // swizzles (bit 3; key >> 2) left the writes 2-way conflicted (27 % + 27 % of
 // the modelled excess cycles; round-4 counters: 36 % of LDS-active cycles in
-// conflicts).  FATTN_BDP_OLD_SWZ (A/B builds): the old ones.
-#ifdef FATTN_BDP_OLD_SWZ
-__host__ __device__ constexpr int bdp_kswz(int key) { return (key >> 3) & 1; }
-__host__ __device__ constexpr int bdp_vswz(int key) { return (key >> 2) & 3; }
-#else
+// conflicts; on config 5 the two measured the same, profiles/r05_f).
 __host__ __device__ constexpr int bdp_kswz(int key) { return ((key >> 2) ^ (key >> 3)) & 1; }
 __host__ __device__ constexpr int bdp_vswz(int key) { return (key >> 1) & 3; }
-#endif
 struct BdpSwz {
     static __host__ __device__ constexpr int k(int key) { return bdp_kswz(key); }
     static __host__ __device__ constexpr int v(int key) { return bdp_vswz(key); }
@@ -259,7 +235,7 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const A a
     };
 
     // ---- prologue.  Compute waves: Q | mask 0 | mask 1 | their pieces of raw
-    // 0 .. nRaw - 1.  Build waves: Q | their pieces of raw 0 .. nRaw - 1; after
+    // 0 .. nRaw - 1 (R_c each: none).  Build waves: Q | their pieces of raw 0 .. nRaw - 1; after
     // the barrier that completes raw 0 they dequantise it into pair 0.
     const int npro = min(C::nRaw, ntiles);  // raw tiles of the prologue
     if (compute) {
@@ -326,20 +302,15 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const A a
         __syncthreads();
         if (s < 4) FATTN_STAMP(3 + s);
         // build waves: the raw words of tile s + 1 read first (their latency
-        // runs under the DMA issue below)
+        // runs under the DMA issue below; read after it, config 5 took 27.4-27.8
+        // vs 23.9-25.0 us, profiles/r04_i)
         BdpRaw deq;
-#ifndef FATTN_BDP_READ_LATE
         if (!compute && s + 1 < ntiles) deq = bdp_dequant_load<KT, D>(raw_ptr(s + 1), bw, lane);
-#endif
         // every wave: its pieces of raw s + nRaw into raw s's slot (every build
         // wave read it before this barrier)
         if (s == 2) FATTN_STAMP(14);
         if (s + C::nRaw < ntiles) bdp_issue<KT, D>(rs, c_lo + (s + C::nRaw) * kBdpKeys, raw_lds(s + C::nRaw), wave, lane);
         if (s == 2) FATTN_STAMP(15);
-#ifdef FATTN_BDP_READ_LATE
-        // diagnostic build only (A/B): the raw words read after the DMA issue
-        if (!compute && s + 1 < ntiles) deq = bdp_dequant_load<KT, D>(raw_ptr(s + 1), bw, lane);
-#endif
         if (!compute) {
             // ---- build: raw s + 1 -> pair (s + 1) % 2; then wait for this
             // wave's pieces of raw s + 2 (raw s + 3 .. s + nRaw may fly on)
@@ -353,33 +324,22 @@ __global__ __launch_bounds__(kBdWaves* kWave, 2) void fattn_bdp_kernel(const A a
         }
         // ---- compute tile s.  This lane's mask values (keys 8 u + 4 h + 0..3 of
         // the half) out of slot s & 1 (landed: waited for before the barrier),
-        // then mask s + 2 into that slot
+        // then mask s + 2 into that slot (issued after tile s's compute instead,
+        // config 5 measured the same: 24.6-25.2 vs 24.7-25.4 us, profiles/r04_j)
         const uint32_t pofs = (s & 1) * C::pair;
         u32x2 mh[4];
         uint32_t open = 1;  // any key not at -inf (f16 0xFC00)
         if constexpr (HM) {
             open = bd_mask_read(smem + C::maskOff + (wave & 3) * 2 * C::maskSlot + (s & 1) * C::maskSlot, c32, h, mh);
-#ifndef FATTN_BDP_MASK_LATE
             if (s + 2 < ntiles) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the slot has been read
                 mask_issue(s + 2);
             }
-#endif
         }
         // this wave's 32 keys past the chunk, or -inf for every valid row: nothing to add (exact)
         const bool live = c_lo + s * kBdpKeys + 32 * kh < c_hi &&
                           (!HM || __builtin_amdgcn_ballot_w64(open != 0 && row_ok) != 0);
         if (live) bd_tile_step<kBdpKeys, D, HM>(a, smem + pofs, kbase, vbase, qop, mh, scale, slope, m_run, l2, o);
-#ifdef FATTN_BDP_MASK_LATE
-        // diagnostic build only (A/B): mask s + 2 issued after tile s's compute
-        // (config 5: 24.6-25.2 vs 24.7-25.4 us, neutral, profiles/r04_j)
-        if constexpr (HM) {
-            if (s + 2 < ntiles) {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                mask_issue(s + 2);
-            }
-        }
-#endif
         // before the next barrier: mask s + 1 and this wave's pieces of raw s + 2
         // landed.  Issue order per tile: raw s + nRaw, then mask s + 2, so raw
         // s + 2 (issued with tile s + 2 - nRaw <= s - 1, or in the prologue) is

@@ -213,8 +213,7 @@ __device__ __forceinline__ void pf_vm_wait(int nraw, int nmask) {
 // of row `lane`, for K (into dim slice 2b + h) and V (dim block b, chunks 2h, 2h+1)
 // (D = 64: two blocks, waves 0-3; waves 4-7 -- the prioritised half -- skip it).
 // In two steps (pf_dequant_load: the LDS reads of the raw words;
-// pf_dequant_store: conversion and image writes), so an A/B build can split
-// them around the S^T chains (FATTN_PF_DEQ_EARLY).
+// pf_dequant_store: conversion and image writes), as fattn_bdp.h's.
 struct PfRaw {
     HalfRaw k, v;
 };
@@ -389,22 +388,14 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
     // tile s's mask block is +-0 everywhere (flag 2; wave-uniform)
     auto zero_of = [&](int s) { return s < 256 && ((zb[s >> 6] >> (s & 63)) & 1); };
     // such a tile's mask DMA goes through an offset past the descriptor (no
-    // traffic, the instruction count unchanged).  (FATTN_PF_ZERO_SKIP, A/B
-    // builds, quantised K/V: not issued at all, the counted waits leaving its
-    // group out -- Q8_0 zero mask 446-455 vs 430-453 us, causal 251 vs 245:
-    // slower, profiles/r04_j)
-#ifdef FATTN_PF_ZERO_SKIP
-    constexpr bool kSkipZero = !C::kDirect;  // diagnostic build only
-#else
-    constexpr bool kSkipZero = false;
-#endif
-    auto mask_groups = [&](int s) { return (HM && !(kSkipZero && zero_of(s))) ? 1 : 0; };
+    // traffic, the instruction count unchanged).  (Not issuing it at all, the
+    // counted waits leaving its group out, was slower on quantised K/V: Q8_0 zero
+    // mask 446-455 vs 430-453 us, causal 251 vs 245, profiles/r04_j.)
     auto mask_issue = [&](int s) {
         if constexpr (HM) {
 #ifndef FATTN_MQ_NOMEM
             const uint32_t n2 = (uint32_t)(t0 + s) * kPfKeys * 2;
             const bool zero = zero_of(s);
-            if (kSkipZero && zero) return;
 #pragma unroll
             for (int k = 0; k < C::NIM; k++) {
                 const uint32_t off = (moff[k] == a.m_span_h || zero) ? a.m_span_h : moff[k] + n2;
@@ -448,7 +439,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
         for (int s = 0; s < 3 && s < ntiles; s++) pf_issue<KT, D>(rs, (t0 + s) * kPfKeys, raw_lds(s), wave, lane);
         if (ntiles > 0) mask_issue(0);
         // raw 0 landed (raw 1, 2 and mask 0 may fly on)
-        pf_vm_wait<KT, D>(min(2, ntiles - 1), ntiles > 0 ? mask_groups(0) : 0);
+        pf_vm_wait<KT, D>(min(2, ntiles - 1), ntiles > 0 ? NM : 0);
         __syncthreads();
         if (ntiles > 0) pf_dequant<KT, D>(raw_ptr(0), smem, smem + C::img, wave, lane);
     }
@@ -484,7 +475,7 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
         // quantised: raw s+1 landed (raw s+2 and mask s may fly on);
         // f16: image pair of tile s landed (tile s+1 and mask s may fly on)
         PF_T(7);
-        pf_vm_wait<KT, D>(s + C::ahead - 1 < ntiles ? 1 : 0, C::kDirect ? NM : mask_groups(s));
+        pf_vm_wait<KT, D>(s + C::ahead - 1 < ntiles ? 1 : 0, NM);
         __syncthreads();
         PF_T(0);
         if constexpr (C::kDirect) {
@@ -496,29 +487,17 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
         // (the round-1 phase stagger -- waves 4-7 dequantising after their
         // compute, FATTN_OPT_PF_STAGGER bit 0 -- measured neutral and was
         // removed: it kept the dequantisation's state live across the compute)
-#ifndef FATTN_PF_DEQ_EARLY
         // reads, conversion and image writes of tile s + 1 in one piece before
-        // tile s's compute.  (FATTN_PF_DEQ_EARLY, A/B builds: the raw words read
-        // before the S^T operand reads and converted after the S^T chains --
-        // Q8_0 zero mask 439-452 vs 439-449 us, random mask 458-480 vs 483-486,
-        // Q4_0 432-441 vs 419-434: no net gain for 14 more VGPRs, profiles/r04_i)
+        // tile s's compute.  (Reading the raw words before the S^T operand reads
+        // and converting them after the S^T chains gave no net gain for 14 more
+        // VGPRs: Q8_0 zero mask 439-452 vs 439-449 us, random mask 458-480 vs
+        // 483-486, Q4_0 432-441 vs 419-434, profiles/r04_i.)
         if constexpr (!C::kDirect) {
             if (s + 1 < ntiles)
                 pf_dequant<KT, D>(raw_ptr(s + 1), smem + (P ^ 1) * C::pairBytes,
                                   smem + (P ^ 1) * C::pairBytes + C::img, wave, lane);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        PfRaw deq;
-        const bool deq_next = false;
-#else
-        // diagnostic build only: the raw words of tile s + 1 (this wave's half
-        // block) read now, converted and written after the S^T chains
-        PfRaw deq;
-        const bool deq_next = !C::kDirect && s + 1 < ntiles;  // workgroup-uniform
-        if constexpr (!C::kDirect) {
-            if (deq_next) deq = pf_dequant_load<KT, D>(raw_ptr(s + 1), wave, lane);
-        }
-#endif
         PF_T(2);
         // quantised: raw tile s + 3 is issued during this tile's first S^T chain
         // (an issue that stalls on a full memory queue then waits beside the
@@ -644,13 +623,6 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
         }
         __builtin_amdgcn_sched_barrier(0);
         }  // live, first half
-        // quantised: tile s + 1's images from the raw words read above (the
-        // conversion VALU runs under the tail of the S^T chains)
-        if constexpr (!C::kDirect) {
-            if (deq_next)
-                pf_dequant_store<KT, D>(deq, smem + (P ^ 1) * C::pairBytes, smem + (P ^ 1) * C::pairBytes + C::img, wave,
-                                        lane);
-        }
         // quantised: raw tile s + 3, issued while the S^T chains execute (a
         // skipped tile issues it here too)
         issue_raw();
@@ -764,7 +736,8 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
     // rows in LDS ([32 rows][DI + 4] f32, its own region; every wave is past
     // the loop's last LDS read: one barrier) and stores them back as whole
     // rows, 64 lanes x 16 B = 1 KiB of contiguous row bytes per instruction
-    // (cdna_hip_programming.md T21).
+    // (cdna_hip_programming.md T21; the row-per-lane stores were 2-15 % slower
+    // per launch, profiles/r04_h).
     const float l_tot = xor32_pair(l2.x + l2.y, false);
     // attention sinks (SplitArgs::sinks; wave-uniform branch): this lane's row's
     // head's sink joins the denominator, sink_inv() -- m_run is the row's
@@ -778,23 +751,6 @@ __global__ __launch_bounds__(kPfWaves* kWave, 1) void fattn_pf_kernel(const A a)
         inv = sink_inv(m_run, l_tot, row_ok ? sinks[iq2] : 0.0f, none);
         fill = 0.0f;
     }
-#ifdef FATTN_PF_DIRECT_STORE
-    // diagnostic build only (A/B): the row-per-lane stores from the accumulator layout
-    if (row_ok) {
-        float* out = a.dst + (((int64_t)iq3 * a.NQ + iq1) * a.H + iq2) * D + 4 * h;
-#pragma unroll
-        for (int db = 0; db < NDB; db++) {
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                f32x4 v;
-#pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = none ? fill : o[db][4 * u + r] * inv;
-                if (32 * db + 8 * u + 4 * h < D) *(f32x4*)(out + 32 * db + 8 * u) = v;
-            }
-        }
-    }
-    return;
-#endif
     constexpr int kStride = C::DI + 4;  // floats (+16 B a row: the parking writes are conflict-free)
     static_assert(kPfWaves * kPfRowsW * kStride * 4 <= C::ldsBytes, "");
     __syncthreads();  // every wave is done with the images, raw tiles and mask slots

@@ -20,9 +20,9 @@
 //           tile j-1, rb 1's scores / max of tile j
 //      B_j: O += V_{j-1}^T . P_{j-1}^T for both  || rb 1's decision and
 //           exponentials of tile j, rb 0's scores / max / decision of tile j
-//    (SCHED 3, "balanced", the default; SCHED 2, "pipelined": each phase's
-//    exponentials in one half and its max pieces in the other); one
-//    workgroup barrier per tile, mid-A;
+//    (SCHED 3, "balanced"; SCHED 2, "pipelined": each phase's exponentials
+//    in one half and its max pieces in the other; the default is SCHED 4,
+//    "lean": see the kernel); one workgroup barrier per tile, mid-A;
 //  * HBM -> LDS by LDS-DMA straight into the f16 images (the swizzles of
 //    fattn_pf.h, 16-B granular, so each lane's source offset carries them):
 //    K and V rings of 3 tiles, per-wave mask rings of 2: V j in A_j, K j+3
@@ -63,19 +63,13 @@ struct Pf4Cfg {
 // row-sum add.  Plain C: hipcc places the trans-use wait state after each
 // v_exp_f32 only for instructions it sees; an inline-asm v_add_f32 reading an
 // exponential one instruction after its v_exp read a stale register in some
-// lanes (rows scaled or sign-flipped; FATTN_PF4_ASM_ADD keeps that form for A/B
-// and hazard-checker tests only)
+// lanes (rows scaled or sign-flipped; tests/hip/isa_hazard_probe.hip keeps that
+// form for the hazard checker)
 __device__ __forceinline__ float add_f32(float x, float y) {
-#ifdef FATTN_PF4_ASM_ADD  // diagnostic build only: WRONG results (see above)
-    float r;
-    asm("v_add_f32_e32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
-    return r;
-#else
     // (not contracted with l's rescale multiply into one fma: the 8-wave
     // body rounds the two separately, and the forms must give the same bits)
 #pragma clang fp contract(off)
     return x + y;
-#endif
 }
 // O *= alpha on one accumulator block where it lives (AGPRs), in one asm
 // statement: v_accvgpr_read, v_mul_f32, v_accvgpr_write per element, inside
@@ -118,11 +112,8 @@ __device__ __forceinline__ void scale_acc16(f32x16& o, float alpha) {
 // cannot see (its hazard pass knows only its own MFMAs): the accumulator ->
 // first VALU read (an 8-pass XDL write: 12 states) and Q^T's v_accvgpr_write
 // -> MFMA read, checked on the .s by tools/isa_hazard_check.py (xdl-vgpr).
-#ifndef FATTN_PF4_SAGPR
-#define FATTN_PF4_SVGPR 1
-#else
-#define FATTN_PF4_SVGPR 0
-#endif
+// (The AGPR accumulators, chains started from -m / c, took 3683 vs 3396
+// cycles per Q8_0 tile, profiles/r06_y.)
 __device__ __forceinline__ void mfma_s_first(f32x16& d, const f16x8& k, const f16x8& q) {
     asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=&v"(d) : "v"(k), "a"(q));
 }
@@ -157,21 +148,11 @@ __device__ __forceinline__ void pin_p(f16x8 (&p)[2][2]) {
     p[1][1] = __builtin_bit_cast(f16x8, d);
 }
 
-// diagnostic builds only: without the opaque bases
-#ifdef FATTN_PF4_SHFL
-#define PF4_XOR32(x, mx) ((mx) ? fmaxf((x), __shfl_xor((x), 32)) : (x) + __shfl_xor((x), 32))
-#else
-#define PF4_XOR32(x, mx) xor32_pair((x), (mx))
-#endif
-#ifdef FATTN_PF4_NO_OPAQUE
-#define PF4_OPAQUE_V(x) ((void)0)
-#define PF4_OPAQUE_S(x) ((void)0)
-#define PF4_OPAQUE_V2(x, y) ((void)0)
-#else
-#define PF4_OPAQUE_V(x) asm volatile("" : "+v"(x))
-#define PF4_OPAQUE_S(x) asm volatile("" : "+s"(x))
-#define PF4_OPAQUE_V2(x, y) asm volatile("" : "+v"(x), "+v"(y))
-#endif
+// the opaque bases of the mask, K and V^T reads: an LDS base through an empty
+// volatile asm is a value hipcc cannot fold into the reads or derive again
+__device__ __forceinline__ void opaque_s(uint32_t& x) { asm volatile("" : "+s"(x)); }
+__device__ __forceinline__ void opaque_v(uint32_t& x) { asm volatile("" : "+v"(x)); }
+__device__ __forceinline__ void opaque_v(uint32_t& x, uint32_t& y) { asm volatile("" : "+v"(x), "+v"(y)); }
 
 // the piece q in [0, 16) whose stage of schedule s(q) = C + (A q) / B falls on
 // step i, or -1 (s strictly increasing: A >= B)
@@ -187,8 +168,9 @@ __device__ __forceinline__ constexpr int sched_inv(int i) {
 }
 
 // SCHED 2: the pipelined schedule (FATTN_OPT_PF_FORM 4); SCHED 3: the balanced
-// one (FATTN_OPT_PF_FORM 5, the default).  Same arithmetic, same order per row
-// block: both give the same bits as fattn_pf_kernel.  (Round 5's unpipelined
+// one (FATTN_OPT_PF_FORM 5).  Same arithmetic, same order per row block: both
+// give the same bits as fattn_pf_kernel.  SCHED 4: the lean form
+// (FATTN_OPT_PF_FORM 6, the default; LEAN below).  (Round 5's unpipelined
 // three-phase forms, SCHED 0 / 1, measured 18-33 % slower and were removed.)
 template <int D, bool HM, int SCHED, typename A = SplitArgs>
 __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A a) {
@@ -198,19 +180,18 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
     constexpr int NDB = D / 32;  // 32-dim blocks of O^T
     constexpr float kNegInf = -__builtin_inff();
     constexpr float kDeferLog2 = 8.0f;
-    // SCHED 4 ("lean"): each S^T chain starts from the row's -m / c (m its
-    // running max in log2 units, c = scale * log2(e)) instead of 0, so one
-    // multiply by c turns the accumulator into the exponent argument c s - m:
-    // per score an accumulator read, that multiply, one max, one exponential,
-    // one row-sum add and half a pack -- not the balanced form's separate
-    // scale fma and "x * log2(e) - m" (bodies without mask values: the zero
-    // mask, no mask; a masked body runs the balanced arithmetic -- its extra
-    // fma per score pushed the lean form into scratch); the rescale decisions
-    // move to the phase tails, where the rare
-    // branch also shifts the tile's arguments and the chains' start.  Q^T
-    // stays h(q) (src/utils.h:10): pre-scaling it by c instead (one rounding
-    // more) cost 5e-3 on large scores.  Not bit-identical to the 8-wave body
-    // (the -m / c enters the f32 chain): the oracle's 1e-3 is the bar.
+    // SCHED 4 ("lean"): one fma turns a score's accumulator into the exponent
+    // argument c s - m (m the row's running max in log2 units, c = scale *
+    // log2(e); the chains start from 0, mfma_s_first): per score that fma, one
+    // max, one exponential, one row-sum add and half a pack -- not the balanced
+    // form's separate scale fma and "x * log2(e) - m" (bodies without mask
+    // values: the zero mask, no mask; a masked body runs the balanced
+    // arithmetic -- its extra fma per score pushed the lean form into scratch);
+    // the rescale decisions move to the phase tails, where the rare branch
+    // also shifts the tile's arguments.  Q^T stays h(q) (src/utils.h:10):
+    // pre-scaling it by c instead (one rounding more) cost 5e-3 on large
+    // scores.  Not bit-identical to the 8-wave body (one rounding of c s - m
+    // where it has two): the oracle's 1e-3 is the bar.
     constexpr bool LEAN = SCHED == 4;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -298,7 +279,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
             }
         }
     }
-    if constexpr (LEAN && FATTN_PF4_SVGPR) {
+    if constexpr (LEAN) {
         // (Q^T into AGPRs once, where the lean chains take it as srcB: from
         // VGPRs hipcc copied it there before every MFMA, 64 v_accvgpr_write a tile)
 #pragma unroll
@@ -382,22 +363,13 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
         }
     }
     f32x16 s0[2], s1[2];  // S^T of rb 0 and rb 1 (both computed in A_j), per subtile
-    f32x16 ci[2];         // (SCHED 4) each row block's S^T chain start: -m / c of the row (0 while m = -inf)
-#pragma unroll
-    for (int rb = 0; rb < 2; rb++) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) ci[rb][j] = 0.0f;
-        // (held in AGPRs, where the MFMAs take it as srcC: from VGPRs hipcc
-        // copied it to AGPRs before every chain, 32 v_accvgpr_write a tile)
-        if constexpr (SCHED == 4 && !FATTN_PF4_SVGPR) asm volatile("" : "+a"(ci[rb]));
-    }
 
     // mask values of row block rb for tile s (a +-0 block's slot holds the
     // zeros its empty DMA wrote)
     auto mask_reads = [&](int s, int rb, u32x2 (&mk)[2][4]) {
         if constexpr (HM) {
             uint32_t mb = (uint32_t)(C::mOff + (wave * C::MS + s % C::MS) * C::maskSlot + rb * (32 * 128));
-            PF4_OPAQUE_S(mb);
+            opaque_s(mb);
             const lds_u8* slot = (const lds_u8*)smem + mb;
 #pragma unroll
             for (int t = 0; t < 2; t++) {
@@ -526,7 +498,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
             auto pv2 = [&](int s, const f16x8 (&pa)[2][2], const f16x8 (&pb)[2][2]) {
                 uint32_t b0 = (uint32_t)(C::vOff + (s % C::VS) * C::img) + vbase[0];
                 uint32_t b1 = (uint32_t)(C::vOff + (s % C::VS) * C::img) + vbase[1];
-                PF4_OPAQUE_V2(b0, b1);
+                opaque_v(b0, b1);
                 lds_u8* const img0 = lsm + b0;
                 lds_u8* const img1 = lsm + b1;
                 // every V^T operand of the tile first (64 VGPRs), so that no MFMA
@@ -566,7 +538,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
             // for half of them)
             auto k_base_at = [&](int slot) {
                 uint32_t kb = (uint32_t)(C::kOff + slot * C::img) + kbase;
-                PF4_OPAQUE_V(kb);
+                opaque_v(kb);
                 return kb;
             };
             auto k_base = [&](int s) { return k_base_at(s % C::KS); };
@@ -656,19 +628,13 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 mX[pc][1] = st[t][k + 1];
                 // (an accumulator read staged a step ahead; with the chains in VGPRs
                 // (lean kernels) there is nothing to stage, and the pin made copies)
-                if constexpr (!(LEAN && FATTN_PF4_SVGPR)) asm volatile("" : "+v"(mX[pc][0]), "+v"(mX[pc][1]));
+                if constexpr (!LEAN) asm volatile("" : "+v"(mX[pc][0]), "+v"(mX[pc][1]));
             };
             // (SCHED 4 without mask values: the accumulator times c IS the argument)
             auto m1u = [&](const f32x16 (&st)[2], float (&us)[2][16], float nr, int pc) {
                 const int t = pc >> 3, k = 2 * (pc & 7);
-#if FATTN_PF4_SVGPR
                 us[t][k] = fmaf(st[t][k], a.scale_log2, nr);
                 us[t][k + 1] = fmaf(st[t][k + 1], a.scale_log2, nr);
-#else
-                (void)nr;
-                us[t][k] = st[t][k] * a.scale_log2;
-                us[t][k + 1] = st[t][k + 1] * a.scale_log2;
-#endif
                 asm volatile("" : "+v"(us[t][k]), "+v"(us[t][k + 1]));
             };
             auto m2 = [&](const u32x2 (&mk)[2][4], float (&us)[2][16], int pc) {
@@ -689,9 +655,9 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 asm volatile("" : "+v"(us[t][k0]), "+v"(us[t][k0 + 1]));
             };
             // (SCHED 4) the rescale decision of row block rb at a phase tail: trel is
-            // the tile max relative to the chains' start -m_ref; a rare,
-            // wave-uniform branch applies a new max to the tile's arguments,
-            // l, and the next chains' start (O's factor: rescale_acc, end of B)
+            // the tile max relative to the arguments' reference m_ref; a rare,
+            // wave-uniform branch applies a new max to the tile's arguments and
+            // l (O's factor: rescale_acc, end of B)
             auto lean_decide = [&](int rb, float trel, float (&us)[2][16], float& alpha, bool& resc) {
                 const float mref = m_run[rb] == kNegInf ? 0.0f : m_run[rb];
                 const float tabs = trel + mref;
@@ -709,14 +675,10 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                     }
                     l2[rb] = f32x2{l2[rb].x * alpha, l2[rb].y * alpha};
                     m_run[rb] = m_new;
-                    const float nci = m_new == kNegInf ? 0.0f : -m_new / a.scale_log2;
-                    if constexpr (!FATTN_PF4_SVGPR) {
-#pragma unroll
-                        for (int j = 0; j < 16; j++) ci[rb][j] = nci;
-                        asm volatile("" : "+a"(ci[rb]));
-                    } else {
-                        (void)nci;
-                    }
+                    // (names `a` only so that this closure captures it as it did while the
+                    // chains' start was computed here: without the capture hipcc allocates
+                    // the lean kernels' registers differently, and they are shipped as measured)
+                    (void)a;
                 }
             };
             auto m3 = [&](const float (&us)[2][16], float& tmax, int pc) {
@@ -753,7 +715,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 f16x8 va[2][2][NDB];
                 uint32_t vb0 = (uint32_t)(C::vOff + (((j > 0 ? j : 1) - 1) % C::VS) * C::img) + vbase[0];
                 uint32_t vb1 = (uint32_t)(C::vOff + (((j > 0 ? j : 1) - 1) % C::VS) * C::img) + vbase[1];
-                PF4_OPAQUE_V2(vb0, vb1);
+                opaque_v(vb0, vb1);
                 auto v_read1 = [&](int v) {
                     const int t = v >> 3, q = (v >> 2) & 1, db = v & 3;
                     const uint32_t off = db * (kPfKeys * 64) + t * 2048 + q * 1024;
@@ -791,12 +753,9 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                         if (i >= 24 && !(i & 1)) v_read1((i - 24) >> 1);  // (after the barrier)
                     }
                     // V_j's DMA (into V_{j-3}'s slot, read in B_{j-2}; needed at B_{j+1}):
-                    // the other half of the tile's issue cost beside A's MFMAs
-#ifdef FATTN_PF4_VDMA_LATE
-                    if (i >= 16 && (i & 3) == 1) v_piece(j, (i - 16) >> 2);
-#else
+                    // the other half of the tile's issue cost beside A's MFMAs (in A's
+                    // max steps 17-29 instead it measured within the spread, profiles/r05_k)
                     if (i < 16 && (i & 3) == 1) v_piece(j, i >> 2);
-#endif
                     if constexpr (MM) {
                         if (i == 8) mask_reads(j, 1, mk1);   // (for rb 1's scores, steps 16+)
                         if (i == 14) mask_reads(j, 0, mk0);  // (for B_j: this wave's slot, no barrier needed)
@@ -858,12 +817,12 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                         if (slot0(p) - 1 == i) m1(s0, p);
                     }
                     if (i == 12) {
-                        tred1 = PF4_XOR32(tmax1, true) * cexp;
+                        tred1 = xor32_pair(tmax1, true) * cexp;
                         asm volatile("" : "+v"(tred1));
                     }
                     if (i == 13) {
                         smax_decide(1, tred1, al1, rs1);
-                        tred0 = PF4_XOR32(tmax0, true) * cexp;
+                        tred0 = xor32_pair(tmax0, true) * cexp;
                         asm volatile("" : "+v"(tred0));
                     }
                     if (i == 14) {
@@ -887,11 +846,9 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                     // consumed by then)
                     if (i < 16 && (i & 3) == 1) k_piece(j + 3, i >> 2);  // (K_{j+3} into K_j's slot; V_j went in A_j)
                     if (i >= 16 && (i & 1)) m_piece(j + 2, (i - 16) >> 1, mskip);
-#ifdef FATTN_PF4_KREAD_EARLY
-                    if (i >= 5 && i < 9) k_read1(kbn, 0, i - 5);
-#else
+                    // (K_{j+1}'s first reads in steps 5-8 instead measured within the
+                    // spread, profiles/r05_k)
                     if (i >= 28) k_read1(kbn, 0, i - 28);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 e3(p0n, la0, lb0, 15);  // (piece 15's last stage, after the loop)
@@ -947,7 +904,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 f16x8 va[2][2][NDB];
                 uint32_t vb0 = (uint32_t)(C::vOff + (F ? 0 : rm) * C::img) + vbase[0];
                 uint32_t vb1 = (uint32_t)(C::vOff + (F ? 0 : rm) * C::img) + vbase[1];
-                PF4_OPAQUE_V2(vb0, vb1);
+                opaque_v(vb0, vb1);
                 auto v_read1 = [&](int v) {
                     const int t = v >> 3, q = (v >> 2) & 1, db = v & 3;
                     const uint32_t off = db * (kPfKeys * 64) + t * 2048 + q * 1024;
@@ -999,7 +956,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                             // (the first tile's step 9 reads s1[0] two steps after its
                             // chain's last MFMA with no exponentials between: the
                             // remaining accumulator -> VALU wait states)
-                            if (F && FATTN_PF4_SVGPR && i == 9) asm volatile("s_nop 3" : "+v"(s1[0]));
+                            if (F && i == 9) asm volatile("s_nop 3" : "+v"(s1[0]));
                             if (q1 >= 0) m1u(s1, us1, nr1, q1);
                         } else {
                             if (q2 >= 0) m2(mk1, us1, q2);
@@ -1007,12 +964,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                         }
                     }
                     if (i < 16) {
-                        if constexpr (LN && FATTN_PF4_SVGPR) {
-                            if (kk == 0) mfma_s_first(s1[t], kr[t][kk], qop[1][kk]);
-                            else mfma_s_next(s1[t], kr[t][kk], qop[1][kk]);
-                        } else if constexpr (LN) {
-                            s1[t] = mfma32(kr[t][kk], qop[1][kk], kk == 0 ? ci[1] : s1[t]);
-                        } else if constexpr (LEAN && FATTN_PF4_SVGPR) {
+                        if constexpr (LEAN) {
                             if (kk == 0) mfma_s_first(s1[t], kr[t][kk], qop[1][kk]);
                             else mfma_s_next(s1[t], kr[t][kk], qop[1][kk]);
                         } else {
@@ -1020,12 +972,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                             s1[t] = mfma32(kr[t][kk], qop[1][kk], s1[t]);
                         }
                     } else {
-                        if constexpr (LN && FATTN_PF4_SVGPR) {
-                            if (kk == 0) mfma_s_first(s0[t], kr[t][kk], qop[0][kk]);
-                            else mfma_s_next(s0[t], kr[t][kk], qop[0][kk]);
-                        } else if constexpr (LN) {
-                            s0[t] = mfma32(kr[t][kk], qop[0][kk], kk == 0 ? ci[0] : s0[t]);
-                        } else if constexpr (LEAN && FATTN_PF4_SVGPR) {
+                        if constexpr (LEAN) {
                             if (kk == 0) mfma_s_first(s0[t], kr[t][kk], qop[0][kk]);
                             else mfma_s_next(s0[t], kr[t][kk], qop[0][kk]);
                         } else {
@@ -1046,7 +993,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 }
                 if constexpr (LN) {
                     // rb 1's decision of tile j, at A's tail (its exponentials run in B)
-                    lean_decide(1, PF4_XOR32(tmax1, true), us1, al1, rs1);
+                    lean_decide(1, xor32_pair(tmax1, true), us1, al1, rs1);
                 }
                 if constexpr (kDiagNoValu) asm volatile("" ::"v"(s1[0][0]), "v"(s1[1][0]), "v"(s0[0][0]), "v"(s0[1][0]));
                 PF4_T(1);
@@ -1070,7 +1017,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
 #pragma unroll
                 for (int i = 0; i < 32; i++) {
                     if (i == 0 && !LN) {
-                        tred1 = PF4_XOR32(tmax1, true) * cexp;
+                        tred1 = xor32_pair(tmax1, true) * cexp;
                         asm volatile("" : "+v"(tred1));
                     }
                     if (i == 1 && !LN) {
@@ -1101,7 +1048,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                         }
                     }
                     if (i == 29 && !LN) {
-                        tred0 = PF4_XOR32(tmax0, true) * cexp;
+                        tred0 = xor32_pair(tmax0, true) * cexp;
                         asm volatile("" : "+v"(tred0));
                     }
                     if (i == 30 && !LN) smax_decide(0, tred0, al0, rs0);
@@ -1131,7 +1078,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
                 pin_p(p1n);
                 if constexpr (LN) {
                     // rb 0's decision of tile j, at B's tail (its exponentials run in A_{j+1})
-                    lean_decide(0, PF4_XOR32(tmax0, true), us0, al0, rs0);
+                    lean_decide(0, xor32_pair(tmax0, true), us0, al0, rs0);
                 }
                 pin16(us0[0]);
                 pin16(us0[1]);
@@ -1201,7 +1148,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
     const float* sinks = a.sinks;
 #pragma unroll
     for (int rb = 0; rb < 2; rb++) {
-        const float l_tot = PF4_XOR32(l2[rb].x + l2[rb].y, false);
+        const float l_tot = xor32_pair(l2[rb].x + l2[rb].y, false);
         float inv = 1.0f / l_tot;  // fully masked row -> NaN like the reference
         bool none = l_tot == 0.0f;
         float fill = __builtin_nanf("");
@@ -1242,7 +1189,7 @@ __global__ __launch_bounds__(kPf4Waves* kWave, 1) void fattn_pf4_kernel(const A 
     if (float* const lse = lse_of(a)) {  // (wave-uniform)
 #pragma unroll
         for (int rb = 0; rb < 2; rb++) {
-            const float l_tot = PF4_XOR32(l2[rb].x + l2[rb].y, false);
+            const float l_tot = xor32_pair(l2[rb].x + l2[rb].y, false);
             int q1, q2;
             if (row_of(kPf4RowsW * wave + 32 * rb + c32, q1, q2) && h == 0)
                 lse[((int64_t)iq3 * a.NQ + q1) * a.H + q2] =

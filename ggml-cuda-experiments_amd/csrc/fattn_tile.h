@@ -14,17 +14,13 @@ constexpr int kSplitWaves = 4;
 constexpr int kStep = 32;   // KV positions per wave step (= one PV k-step)
 constexpr int kRows = 16;   // packed query rows per workgroup (MFMA N)
 constexpr int VT_F16T = 100;  // V f16 stored transposed ([D][N], flash_row_float.h:177)
-constexpr int kCntStride = 64;
+constexpr int kCntStride = 64;  // uint32 words between arrival counters (256 B: atomics to one line serialise)
 // deferred max (cdna_hip_programming.md T13): the exponentials' reference max
 // moves only when a score exceeds it by more than 2^3 in p, so p <= 8 (and P*d
 // of a V block stays far inside f16 range)
 constexpr float kRescaleLog2 = 3.0f;
 constexpr float kRescaleNat = kRescaleLog2 * 0.6931471805599453f;
-#ifdef FATTN_DMA_NO_NT
-constexpr bool kDecodeNT = false;  // diagnostic build only
-#else
 constexpr bool kDecodeNT = true;   // decode K/V: read once per launch
-#endif  // uint32 words between arrival counters (256 B: atomics to one line serialise)
 
 struct SplitArgs {
     const uint8_t* q;
@@ -233,8 +229,7 @@ __device__ __forceinline__ u32x4 ld_buf_untracked(const i32x4& srd, uint32_t off
 // decodes read through a stale descriptor word; tools/isa_hazard_check.py
 // audits every asm VMEM instruction for it).  It also covers M0 -> LDS-DMA
 // (1 state).  Not tracked by the compiler's s_waitcnt bookkeeping: every
-// consumer waits with an explicit vmcnt.  (-DFATTN_DMA_M0_SAVE: the round-5
-// save / restore form, padded the same way, for A/B builds.)
+// consumer waits with an explicit vmcnt.
 // NT: non-temporal policy for bytes one CU reads once (the decode KV stream,
 // MI355X_MICROARCH.md 'nt-weights'); never for tiles other workgroups re-read.
 // PAD: the opening s_nop's count -- 4 (5 wait states) unless the caller's
@@ -248,19 +243,9 @@ __device__ __forceinline__ void dma(const i32x4& srd, uint32_t lds_any, uint32_t
     // wave-uniform by construction; readfirstlane keeps it an SGPR operand even
     // where divergent code around the call hides that from the compiler
     const uint32_t lds = __builtin_amdgcn_readfirstlane(lds_any);
-#ifdef FATTN_DMA_M0_SAVE
-    uint32_t keep;
-#define FATTN_DMA_ASM(INSN, MOD)                                                                         \
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 2\n\t" INSN " %1, %2, 0 offen" MOD \
-                 "\n\ts_mov_b32 m0, %0"                                                                \
-                 : "=&s"(keep)                                                                           \
-                 : "v"(off), "s"(srd), "s"(lds)                                                          \
-                 : "memory")
-#else
-#define FATTN_DMA_ASM(INSN, MOD)                                                                     \
+#define FATTN_DMA_ASM(INSN, MOD)                                                                          \
     asm volatile("s_nop %3\n\t" INSN " %0, %1, 0 offen" MOD : : "v"(off), "s"(srd), "{m0}"(lds), "n"(PAD) \
                  : "memory")
-#endif
     if constexpr (BYTES == 16 && NT) FATTN_DMA_ASM("buffer_load_dwordx4", " nt lds");
     else if constexpr (BYTES == 16) FATTN_DMA_ASM("buffer_load_dwordx4", " lds");
     else if constexpr (NT) FATTN_DMA_ASM("buffer_load_dword", " nt lds");

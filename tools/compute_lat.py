@@ -1,8 +1,9 @@
-"""Compute-only latency of the decode step (libfattn_nomem.so: no HBM traffic,
-the kernel computes on whatever LDS holds).  Config 3 shape, forced chunk
-lengths: chunk = 128*k gives k steps per wave."""
+"""Compute-only latency of the decode step (libfattn_diag_nomem.so, built by
+tools/build_diag.sh: no HBM traffic, the kernel computes on whatever LDS
+holds).  Config 3 shape, forced chunk lengths: chunk = 128*k gives k steps per
+wave."""
 import json, os, subprocess, sys
-for lib in ["libfattn_nomem.so", "libfattn_nomem_nopub.so", "libfattn_nomem_notail.so", "libfattn_notail.so"]:
+for lib in ["libfattn_diag_nomem.so", "libfattn_diag_nomem_notail.so", "libfattn_diag_notail.so"]:
     for ch in [128, 512, 2048, 4096]:
         env = dict(os.environ, FATTN_LIB=lib)
         out = subprocess.run([sys.executable, "bench.py", "--steps", "50", "--warmup", "5", "--no-cpu-baseline",
