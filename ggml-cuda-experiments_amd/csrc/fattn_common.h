@@ -84,6 +84,7 @@ using ExtTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;
 using SplitOnlyTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_BF16>;  // K and V of one type, D = 64 / 128 / 256
 using StageTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // block types: staged to f16 for prefill, quantize / dequantize
 using SetRowsTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // (no BF16)
+using KShiftTypes = RowTypes;  // fattn_k_shift rotates every row type in place, an F32 view included
 
 // TypeInfo by run-time type: the row of type t, or the empty row (block_elems = 0)
 struct TypeDesc {

@@ -39,7 +39,9 @@ EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
     "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows", "fattn_ext_lse", "fattn_lse_merge",
+    "fattn_k_shift",
 )
+ROPE_NORMAL, ROPE_NEOX = 0, 2   # fattn_rope.mode: ggml's GGML_ROPE_TYPE_NORMAL / GGML_ROPE_TYPE_NEOX
 OPT_MQ_ROWS_PER_WAVE = 1
 OPT_MQ_DISABLE = 2
 OPT_SPLIT_STEPS = 3
@@ -90,6 +92,21 @@ class FattnParams(C.Structure):
                 # ggml's op_params[1], [2] and the global head numbering of the ALiBi slopes (zeros: off)
                 ("max_bias", C.c_float), ("logit_softcap", C.c_float),
                 ("n_head_total", C.c_int32), ("head_first", C.c_int32)]
+
+
+class FattnRope(C.Structure):
+    """ggml_rope_ext's parameters (include/fattn.h fattn_rope)."""
+    _fields_ = [("n_dims", C.c_int32), ("mode", C.c_int32), ("n_ctx_orig", C.c_int32),
+                ("freq_base", C.c_float), ("freq_scale", C.c_float), ("ext_factor", C.c_float),
+                ("attn_factor", C.c_float), ("beta_fast", C.c_float), ("beta_slow", C.c_float)]
+
+
+def rope_params(n_dims: int, mode: int = ROPE_NEOX, *, freq_base: float = 10000.0, freq_scale: float = 1.0,
+                ext_factor: float = 0.0, attn_factor: float = 1.0, beta_fast: float = 32.0, beta_slow: float = 1.0,
+                n_ctx_orig: int = 0) -> FattnRope:
+    """A FattnRope with ggml's defaults for everything but n_dims."""
+    return FattnRope(int(n_dims), int(mode), int(n_ctx_orig), float(freq_base), float(freq_scale), float(ext_factor),
+                     float(attn_factor), float(beta_fast), float(beta_slow))
 
 
 _lib = None
@@ -145,6 +162,8 @@ def lib() -> C.CDLL:
         L.fattn_cpy.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp]
         L.fattn_set_rows.restype = C.c_int
         L.fattn_set_rows.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp]
+        L.fattn_k_shift.restype = C.c_int
+        L.fattn_k_shift.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp, C.POINTER(FattnRope), vp]
         L.fattn_describe.restype = C.c_int
         L.fattn_describe.argtypes = [C.POINTER(FattnParams), C.c_char_p, sz]
         _lib = L
@@ -535,6 +554,27 @@ def set_rows(src: View, idx: View, dst: View, stream=None):
     whatever the index tensor then holds."""
     s, i, d = src.c(), idx.c(), dst.c()
     _check(lib().fattn_set_rows(C.byref(s), C.byref(i), C.byref(d), _stream(stream)), "fattn_set_rows")
+
+
+def k_shift(k: View, shift: View, rope: FattnRope, freq_factors=None, stream=None):
+    """The K-shift (include/fattn.h fattn_k_shift): rotate the K cache view k, ne =
+    [ne0 <= 256, n_slots, Hkv, S] of any row type, IN PLACE by the RoPE of the
+    position deltas in shift (TYPE_I32, ne = [n_slots, ns, 1, 1], device memory;
+    sequence i3 reads plane i3 % ns).  rope: a FattnRope (rope_params()).
+    freq_factors: None, a raw device pointer, or a contiguous float32 device
+    tensor of exactly rope.n_dims / 2 values.  Rows whose delta is 0 and blocks at
+    or past n_dims keep their bytes.  The deltas are read on the device, so a
+    captured graph replays with whatever the shift tensor then holds."""
+    fptr = freq_factors
+    if freq_factors is not None and not isinstance(freq_factors, int):
+        import torch
+        if freq_factors.dtype != torch.float32 or not freq_factors.is_contiguous() or not freq_factors.is_cuda:
+            raise ValueError("k_shift: freq_factors must be a contiguous float32 device tensor")
+        if freq_factors.numel() != int(rope.n_dims) // 2:
+            raise ValueError(f"k_shift: {freq_factors.numel()} freq_factors for n_dims / 2 = {int(rope.n_dims) // 2} pairs")
+        fptr = _tptr(freq_factors)
+    kc, sc = k.c(), shift.c()
+    _check(lib().fattn_k_shift(C.byref(kc), C.byref(sc), fptr, C.byref(rope), _stream(stream)), "fattn_k_shift")
 
 
 def dequantize(blocks, typ: int, k: int, stream=None):

@@ -63,6 +63,14 @@
 //                        --kv-type q8_0|q4_0 the cache rows are quantised (fattn_quantize; on the
 //                        host with --cpu-only), V is the view --v-off 0|32|64 elements (whole
 //                        blocks) in, and the reference takes the blocks dequantised on the host
+//   --k-shift DELTA [--rope-mode norm|neox]   llama.cpp's K-shift (fattn_k_shift): the K / V caches of
+//                        --kv-type are encoded on the host, every slot of the K cache is rotated in place by
+//                        the RoPE of DELTA positions on the GPU (n_dims = --head-dim, mode neox by default,
+//                        freq_base 10000), the host recomputes the same in plain C++ (decode, rotate,
+//                        encode) and the CPU reference attends over that cache; one query row;
+//                        --heads / --kv-heads / --kv-size / --head-dim (a multiple of 32, <= 256) / --mask /
+//                        --iters / --tol / --cpu-only apply.  Prints how many cache bytes differ from the
+//                        host's shift (sinf / cosf ulps may flip a code) and the verification line
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -596,9 +604,255 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     return worst_rel <= tol && lse_ok ? 0 : 1;
 }
 
+// ggml's quantize_row_q4_1_ref / _q5_0_ref / _q5_1_ref in plain C++ (every
+// operation rounded on its own; the strict-compare scans keep the first of equals)
+void quant_host_ext(int type, const float* src, uint8_t* dst, int D, int64_t rows) {
+    const bool has_m = type != FATTN_TYPE_Q5_0, has_qh = type != FATTN_TYPE_Q4_1;
+    const int bb = 2 + (has_m ? 2 : 0) + (has_qh ? 4 : 0) + 16;
+    for (int64_t i = 0; i < rows * (D / 32); i++) {
+        const float* x = src + i * 32;
+        uint8_t* b = dst + i * bb;
+        float d, mn = 0.0f;
+        if (!has_m) {
+            float amax = 0.0f, mx = 0.0f;
+            for (int j = 0; j < 32; j++)
+                if (amax < fabsf(x[j])) amax = fabsf(x[j]), mx = x[j];
+            d = mx / -16.0f;
+        } else {
+            float mxv = -3.402823466e+38f;
+            mn = 3.402823466e+38f;
+            for (int j = 0; j < 32; j++) {
+                if (x[j] < mn) mn = x[j];
+                if (x[j] > mxv) mxv = x[j];
+            }
+            d = (mxv - mn) / (type == FATTN_TYPE_Q4_1 ? 15.0f : 31.0f);
+            const uint16_t mh = f2h(mn);
+            b[2] = (uint8_t)(mh & 0xFF), b[3] = (uint8_t)(mh >> 8);
+        }
+        const float id = d ? 1.0f / d : 0.0f;
+        const uint16_t dh = f2h(d);
+        b[0] = (uint8_t)(dh & 0xFF), b[1] = (uint8_t)(dh >> 8);
+        auto code = [&](float v) -> uint32_t {
+            if (type == FATTN_TYPE_Q5_0) return (uint32_t)std::min(31, (int)(int8_t)(v * id + 16.5f));
+            if (type == FATTN_TYPE_Q4_1) return (uint32_t)std::min(15, (int)(int8_t)((v - mn) * id + 0.5f));
+            return (uint8_t)((v - mn) * id + 0.5f);
+        };
+        uint32_t qh = 0;
+        uint8_t* qs = b + bb - 16;
+        for (int j = 0; j < 16; j++) {
+            const uint32_t q0 = code(x[j]), q1 = code(x[j + 16]);
+            qs[j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
+            qh |= ((q0 >> 4) & 1u) << j;
+            qh |= ((q1 >> 4) & 1u) << (j + 16);
+        }
+        if (has_qh) {
+            uint8_t* hp = b + (has_m ? 4 : 2);
+            hp[0] = (uint8_t)qh, hp[1] = (uint8_t)(qh >> 8), hp[2] = (uint8_t)(qh >> 16), hp[3] = (uint8_t)(qh >> 24);
+        }
+    }
+}
+
+// rows of any cache type on the host: f32 -> bytes and back
+void encode_host(int type, const float* src, uint8_t* dst, int D, int64_t rows) {
+    if (type == FATTN_TYPE_F16 || type == FATTN_TYPE_BF16) {
+        uint16_t* h = (uint16_t*)dst;
+        for (int64_t i = 0; i < rows * D; i++) {
+            if (type == FATTN_TYPE_F16) {
+                h[i] = f2h(src[i]);
+            } else {
+                const float r = round_bf16(src[i]);
+                uint32_t u;
+                std::memcpy(&u, &r, 4);
+                h[i] = (uint16_t)(u >> 16);
+            }
+        }
+    } else if (is_kv_ext(type)) {
+        quant_host_ext(type, src, dst, D, rows);
+    } else {
+        quant_host_q80_q40(type, src, dst, D, rows);
+    }
+}
+void decode_host(int type, const uint8_t* src, float* dst, int D, int64_t rows) {
+    if (type == FATTN_TYPE_F16 || type == FATTN_TYPE_BF16) {
+        const uint16_t* h = (const uint16_t*)src;
+        for (int64_t i = 0; i < rows * D; i++) {
+            if (type == FATTN_TYPE_F16) {
+                dst[i] = h2f(h[i]);
+            } else {
+                const uint32_t u = (uint32_t)h[i] << 16;
+                std::memcpy(&dst[i], &u, 4);
+            }
+        }
+    } else if (is_kv_ext(type)) {
+        dequant_host(type, src, dst, D, rows);
+    } else {
+        dequant_host_q80_q40(type, src, dst, D, rows);
+    }
+}
+
+// include/fattn.h's rotation of one row by the position delta p, in plain C++
+// (n_dims = D, freq_base 10000, freq_scale 1, no YaRN, attn_factor 1)
+void rope_row_host(float* x, int D, int p, bool neox) {
+    const float theta_scale = powf(10000.0f, -2.0f / (float)D);
+    for (int i = 0; i < D / 2; i++) {
+        const float theta = (float)p * powf(theta_scale, (float)i);
+        const float c = cosf(theta), s = sinf(theta);
+        float& x0 = x[neox ? i : 2 * i];
+        float& x1 = x[neox ? i + D / 2 : 2 * i + 1];
+        const float y0 = x0 * c - x1 * s, y1 = x0 * s + x1 * c;
+        x0 = y0, x1 = y1;
+    }
+}
+
+// the --k-shift flow: inputs from rand() in the order Q, K, V, mask; the K / V
+// caches [Hkv][N][row] of --kv-type encoded on the host; fattn_k_shift rotates
+// every slot of the K cache by DELTA on the GPU (one shift tensor in device
+// memory); the host recomputes the same (decode, rope_row_host, encode) and the
+// CPU reference attends over THAT cache; fattn_ext attends over the GPU's.  The
+// verification line is that of the other branches.  --cpu-only: the host's
+// shift and the reference alone.
+int run_k_shift(int delta, bool neox, int D, int H, int Hkv, int N, int kv_type, const std::string& mask_kind, bool cpu_only,
+                int iters, float tol) {
+    const size_t rb = fattn_row_size(kv_type, D);
+    if (H <= 0 || Hkv <= 0 || N <= 0 || H % Hkv || rb == 0 || D % 32 || D > 256 || D < 32) {
+        fprintf(stderr, "--k-shift: heads a positive multiple of kv-heads, head-dim a multiple of 32 up to 256\n");
+        return 2;
+    }
+    const float scale = 1.0f / sqrtf((float)D);
+    std::vector<float> query((size_t)D * H), key((size_t)D * N * Hkv), value((size_t)D * N * Hkv), mask((size_t)N);
+    random_fill(query);
+    random_fill(key);
+    random_fill(value);
+    random_fill(mask);
+    if (mask_kind != "random") std::fill(mask.begin(), mask.end(), 0.0f);
+    const int64_t nrows = (int64_t)N * Hkv;
+    std::vector<uint8_t> kbytes(rb * nrows), vbytes(rb * nrows), kshift(rb * nrows);
+    encode_host(kv_type, key.data(), kbytes.data(), D, nrows);
+    encode_host(kv_type, value.data(), vbytes.data(), D, nrows);
+    // the host's shift: what the cache holds -> rotated -> what the cache then holds
+    std::vector<float> kref(key.size()), vref(value.size());
+    decode_host(kv_type, kbytes.data(), kref.data(), D, nrows);
+    decode_host(kv_type, vbytes.data(), vref.data(), D, nrows);
+    if (delta != 0) {
+        for (int64_t r = 0; r < nrows; r++) rope_row_host(&kref[(size_t)r * D], D, delta, neox);
+        encode_host(kv_type, kref.data(), kshift.data(), D, nrows);
+        decode_host(kv_type, kshift.data(), kref.data(), D, nrows);
+    } else {
+        kshift = kbytes;  // (a zero delta touches nothing)
+    }
+    const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::vector<float> ref((size_t)D * H), got(ref.size());
+    cpu_reference(query, kref, vref, mask, ref, N, D, H, Hkv, scale, {0}, threads);
+    printf("k-shift: %s cache [%d][%d][%d], every slot by %d, rope mode %s\n", type_name(kv_type), Hkv, N, D, delta,
+           neox ? "neox" : "norm");
+    print_array("Reference", ref.data(), std::min(16, D * H));
+    if (cpu_only) return 0;
+
+    const bool has_mask = mask_kind != "none";
+    const int Np = N + (N & 1);
+    std::vector<uint16_t> mask16((size_t)Np * 32, f2h(0.0f));
+    for (int i = 0; i < N; i++) mask16[i] = f2h(mask[i]);
+    std::vector<int32_t> shift(N, delta);
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    float *d_q, *d_out;
+    void *d_k, *d_v, *d_mask, *d_ws, *d_shift;
+    HIP_CHECK(hipMalloc(&d_q, 4 * query.size()));
+    HIP_CHECK(hipMalloc(&d_out, 4 * got.size()));
+    HIP_CHECK(hipMalloc(&d_k, kbytes.size()));
+    HIP_CHECK(hipMalloc(&d_v, vbytes.size()));
+    HIP_CHECK(hipMalloc(&d_mask, 2 * mask16.size()));
+    HIP_CHECK(hipMalloc(&d_shift, 4 * shift.size()));
+    HIP_CHECK(hipMemcpyAsync(d_q, query.data(), 4 * query.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_k, kbytes.data(), kbytes.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_v, vbytes.data(), vbytes.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_shift, shift.data(), 4 * shift.size(), hipMemcpyHostToDevice, st));
+    const int64_t eb = kv_type == FATTN_TYPE_F16 || kv_type == FATTN_TYPE_BF16 ? 2 : (int64_t)fattn_row_size(kv_type, 32);
+    const fattn_tensor tk = {d_k, kv_type, 0, {D, N, Hkv, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+    const fattn_tensor ts = {d_shift, FATTN_TYPE_I32, 0, {N, 1, 1, 1}, {4, 4 * (int64_t)N, 4 * (int64_t)N, 4 * (int64_t)N}};
+    const fattn_rope rope = {D, neox ? 2 : 0, 0, 10000.0f, 1.0f, 0.0f, 1.0f, 32.0f, 1.0f};
+    hipEvent_t start, stop;
+    HIP_CHECK(hipEventCreate(&start));
+    HIP_CHECK(hipEventCreate(&stop));
+    HIP_CHECK(hipEventRecord(start, st));
+    int rc = fattn_k_shift(&tk, &ts, nullptr, &rope, st);
+    HIP_CHECK(hipEventRecord(stop, st));
+    if (rc) {
+        fprintf(stderr, "k_shift failed: %s\n", fattn_strerror(rc));
+        return 2;
+    }
+    HIP_CHECK(hipEventSynchronize(stop));
+    float shift_ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&shift_ms, start, stop));
+    std::vector<uint8_t> kgot(kbytes.size());
+    HIP_CHECK(hipMemcpy(kgot.data(), d_k, kgot.size(), hipMemcpyDeviceToHost));
+    int64_t differ = 0;
+    for (size_t i = 0; i < kgot.size(); i++) differ += kgot[i] != kshift[i];
+    std::vector<float> kdev(key.size());
+    decode_host(kv_type, kgot.data(), kdev.data(), D, nrows);
+    float max_dx = 0.0f, max_x = 0.0f;
+    for (size_t i = 0; i < kdev.size(); i++) {
+        const float dd = fabsf(kdev[i] - kref[i]);
+        max_dx = std::isnan(dd) ? INFINITY : std::max(max_dx, dd);
+        max_x = std::max(max_x, fabsf(kref[i]));
+    }
+    printf("k-shift: one launch %.4f ms (first call); %lld of %zu cache bytes differ from the host's shift, max |dx| %.3g of max |x| %.3g\n",
+           shift_ms, (long long)differ, kgot.size(), max_dx, max_x);
+
+    fattn_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = {d_q, FATTN_TYPE_F32, 0, {D, 1, H, 1}, {4, (int64_t)H * D * 4, (int64_t)D * 4, (int64_t)H * D * 4}};
+    p.k = tk;
+    p.v = {d_v, kv_type, 0, {D, N, Hkv, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+    if (has_mask) p.mask = {d_mask, FATTN_TYPE_F16, 0, {Np, 32, 1, 1}, {2, (int64_t)Np * 2, (int64_t)Np * 64, (int64_t)Np * 64}};
+    p.dst = d_out;
+    p.scale = scale;
+    const size_t ws_bytes = std::max<size_t>(fattn_workspace_size(&p), 16);
+    HIP_CHECK(hipMalloc(&d_ws, ws_bytes));
+    rc = fattn_workspace_init(d_ws, ws_bytes, st);
+    p.workspace = d_ws;
+    p.workspace_bytes = ws_bytes;
+    std::vector<float> times;
+    for (int it = 0; it < iters && !rc; it++) {
+        HIP_CHECK(hipEventRecord(start, st));
+        rc = fattn_ext(&p, st);
+        HIP_CHECK(hipEventRecord(stop, st));
+        HIP_CHECK(hipEventSynchronize(stop));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+        times.push_back(ms);
+    }
+    if (rc) {
+        fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
+        return 2;
+    }
+    std::sort(times.begin(), times.end());
+    HIP_CHECK(hipMemcpy(got.data(), d_out, 4 * got.size(), hipMemcpyDeviceToHost));
+    print_array("K-shift HIP", got.data(), std::min(16, D * H));
+    float max_diff = 0.0f, max_ref = 0.0f;
+    int head_idx = 0, dim_idx = 0;
+    for (int h = 0; h < H; h++)
+        for (int i = 0; i < D; i++) {
+            const float dd = fabsf(ref[(size_t)h * D + i] - got[(size_t)h * D + i]);
+            max_ref = std::max(max_ref, fabsf(ref[(size_t)h * D + i]));
+            if (dd > max_diff || std::isnan(dd)) {
+                max_diff = std::isnan(dd) ? INFINITY : dd;
+                head_idx = h, dim_idx = i;
+            }
+        }
+    const float worst_rel = max_diff / std::max(max_ref, 1e-30f);
+    printf("\ncuda time: %.4f ms  (attention over the shifted cache; median of %d)\n", times[times.size() / 2], iters);
+    const size_t at = (size_t)head_idx * D + dim_idx;
+    printf("R (%.4f) CUDA(%.4f) diff: %.4f - row = 0, head = %d, dim = %d\n", ref[at], got[at], max_diff, head_idx, dim_idx);
+    printf("checked 1 of 1 query rows x %d heads; n_q 1, 1 GPU(s)\n", H);
+    printf("normwise rel err %.3g (tol %.1g): %s\n", worst_rel, tol, worst_rel <= tol ? "PASS" : "FAIL");
+    return worst_rel <= tol ? 0 : 1;
+}
+
 }  // namespace
 
-#define RCCL_CHECK(x)                                                                            \
+#define RCCL_CHECK(x)                                                                           \
     do {                                                                                          \
         ncclResult_t r_ = (x);                                                                    \
         if (r_ != ncclSuccess) {                                                                  \
@@ -615,7 +869,8 @@ int main(int argc, const char* argv[]) {
     const char* dump = nullptr;
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
     bool use_sinks = false, set_rows = false, mla = false, heads_given = false;
-    int mla_v_off = 0;
+    int mla_v_off = 0, k_shift_delta = 0;
+    bool k_shift = false, rope_neox = true;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -646,6 +901,15 @@ int main(int argc, const char* argv[]) {
         else if (a == "--mla") mla = true;
         else if (a == "--lse") use_lse = true;
         else if (a == "--v-off") mla_v_off = atoi(next());
+        else if (a == "--k-shift") k_shift = true, k_shift_delta = atoi(next());
+        else if (a == "--rope-mode") {
+            const std::string m = next();
+            if (m != "norm" && m != "neox") {
+                fprintf(stderr, "--rope-mode norm|neox\n");
+                return 2;
+            }
+            rope_neox = m == "neox";
+        }
         else if (a == "--mask") {
             mask_kind = next();
             if (mask_kind != "random" && mask_kind != "zero" && mask_kind != "none") {
@@ -681,6 +945,8 @@ int main(int argc, const char* argv[]) {
     if (num_warps != 8 && num_warps != 4 && num_warps != 2 && num_warps != 1)
         printf("invalid num_warps, should be 2, 4, 8\n");  // kernel_test.h:176-178 (informational)
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
+    if (k_shift)
+        return run_k_shift(k_shift_delta, rope_neox, head_dim, num_heads, num_kv_heads, kv_size, kv_type, mask_kind, cpu_only, iters, tol);
     // (the model family's smallest head count unless --heads says otherwise)
     if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump, use_lse);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device

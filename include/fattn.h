@@ -36,6 +36,9 @@
  *                           contiguous view, and GGML_OP_SET_ROWS, rows scattered to
  *                           the slots an index tensor in device memory names (what
  *                           llama.cpp emits since mid-2025); both absent from the reference.
+ *   fattn_k_shift()      the last node of the cache's life cycle: llama.cpp's K-shift
+ *                           (build_rope_shift), the RoPE rotation of a cache of any type in
+ *                           place by per-slot position deltas, one launch; absent from the reference.
  *
  * Conventions:
  *   - every pointer is a device pointer the caller allocated; the library never
@@ -451,6 +454,76 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
  * FATTN_ERR_ALIGNMENT.  Stream-ordered; allocates nothing, does not
  * synchronise, capturable. */
 int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, const fattn_tensor* dst, void* stream);
+
+/* THE K-SHIFT: the RoPE rotation of a K cache IN PLACE by a per-slot position
+ * delta -- the graph llama.cpp's build_rope_shift schedules for context shifting
+ * and llama_memory_seq_add / seq_div (cast to f32 when the cache is quantised,
+ * ggml_rope_ext_inplace, copy back), as ONE launch that reads each cache block
+ * once, dequantises it in registers, rotates it, requantises it and writes it
+ * back: no f32 temporary.  Absent from the reference.  The deltas are data in
+ * device memory, so one captured graph serves every shift.
+ *   k      F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1  ne = [ne0, n_slots, Hkv, S],
+ *          oriented like fattn_set_rows' dst ([N][Hkv][row] and [Hkv][N][row]
+ *          caches are both views); nb[0] = element / block bytes; base and
+ *          nb[1..3] multiples of 2 (4 for F32).  ne0 <= 256, a multiple of 32 for
+ *          the block types and of 4 otherwise; a longer row is passed as the view
+ *          of its leading part (the 64 RoPE dims of an MLA cache row: ne0 = 64,
+ *          nb[1] = 1152 / 612 / 324).  Rows must not overlap (the caller's duty)
+ *   shift  I32  ne = [n_slots, ns, 1, 1] with S % ns == 0: sequence i3 reads plane
+ *          i3 % ns; heads never index it.  Base and strides multiples of 4,
+ *          nb[0] >= 4, nb[1] non-negative (looked at only when ns > 1)
+ *   freq_factors  NULL, or n_dims / 2 f32 values in device memory (ggml's src[2])
+ *   rope   ggml_rope_ext's parameters (below)
+ * For every row (n, h, s) with p = shift[n, s % ns]:
+ *   - p == 0: NO BYTE OF THE ROW IS TOUCHED (ggml would requantise it: the first
+ *     deviation, and the better outcome -- an unshifted row keeps its bits).
+ *   - 32-element blocks that lie wholly at or past n_dims are never touched
+ *     either (the second deviation, same reason); for F32 / F16 / BF16 only the
+ *     elements below n_dims are written.
+ *   - every other block of the row is rewritten: x = ggml's dequantize_row_* of
+ *     it (exact for F32 / F16 / BF16); for pair i < n_dims / 2, with (x0, x1) =
+ *     elements (2i, 2i+1) for mode 0 and (i, i + n_dims/2) for mode 2, all in f32,
+ *     every operation rounded on its own:
+ *         theta_scale  = powf(freq_base, -2.0f / n_dims)
+ *         theta_extrap = p * powf(theta_scale, i) / (freq_factors ? freq_factors[i] : 1)
+ *         theta = freq_scale * theta_extrap,  m = attn_factor
+ *         if (ext_factor != 0) {            -- ggml's rope_yarn
+ *             corr(b) = n_dims * logf(n_ctx_orig / (b * 2 pi)) / (2 * logf(freq_base))
+ *             lo = max(0, floorf(corr(beta_fast))),  hi = min(n_dims - 1, ceilf(corr(beta_slow)))
+ *             mix = (1 - min(1, max(0, (i - lo) / max(0.001f, hi - lo)))) * ext_factor
+ *             theta = theta * (1 - mix) + theta_extrap * mix
+ *             m *= 1 + 0.1f * logf(1 / freq_scale)
+ *         }
+ *         y0 = x0 * cos(theta) * m - x1 * sin(theta) * m
+ *         y1 = x0 * sin(theta) * m + x1 * cos(theta) * m
+ *     (sinf / cosf with full range reduction: |theta| reaches 1e5); elements at
+ *     or past n_dims pass through.  The block then holds exactly the bytes
+ *     fattn_set_rows / fattn_cpy write for y: quantize_row_*_ref with its tie
+ *     rules, f16 round-to-nearest-even, the BF16 rule of fattn_quantize, y itself
+ *     for F32.  The rotation is one function for all eight types: equal x, p and
+ *     parameters give the same f32 y.
+ * Limits: ne0 <= 256; modes 0 (GGML_ROPE_TYPE_NORMAL) and 2 (GGML_ROPE_TYPE_NEOX)
+ * only -- no M-RoPE / vision modes.
+ * Validated before anything launches: NULL k / shift / rope or a NULL data, any
+ * ne <= 0, shift.ne[0] != n_slots, S % ns, shift.ne[2..3] != 1, ne0 no multiple
+ * of 32 (block types) / 4 (others), n_dims outside 8 .. ne0 or n_dims % 8, mode
+ * not 0 / 2, freq_base or freq_scale not finite and positive, ext_factor negative
+ * or not finite, attn_factor / beta_fast / beta_slow not finite, ext_factor != 0
+ * with n_ctx_orig <= 0, more than 2^31 - 1 blocks in one [ne0, n_slots] plane
+ * FATTN_ERR_INVALID_ARG; a k type outside the list or a shift that is not I32
+ * FATTN_ERR_UNSUPPORTED_TYPE; ne0 > 256 FATTN_ERR_UNSUPPORTED_HEAD_DIM; a wrong
+ * k.nb[0], shift.nb[0] < 4 or a negative shift.nb[1] FATTN_ERR_BAD_STRIDE;
+ * alignment (k as above, shift and freq_factors multiples of 4)
+ * FATTN_ERR_ALIGNMENT.  Stream-ordered; allocates nothing, does not synchronise,
+ * capturable. */
+typedef struct fattn_rope {
+    int32_t n_dims;      /* leading elements of each row that are rotated (ggml n_rot) */
+    int32_t mode;        /* 0 = GGML_ROPE_TYPE_NORMAL: pairs (2i, 2i+1); 2 = GGML_ROPE_TYPE_NEOX: pairs (i, i + n_dims/2) */
+    int32_t n_ctx_orig;  /* read only when ext_factor != 0 */
+    float freq_base, freq_scale, ext_factor, attn_factor, beta_fast, beta_slow;
+} fattn_rope;
+int fattn_k_shift(const fattn_tensor* k, const fattn_tensor* shift, const float* freq_factors,
+                  const fattn_rope* rope, void* stream);
 
 const char* fattn_strerror(int status);
 /* bytes of one row of k elements (0 if unsupported; BF16: 2 k) */
