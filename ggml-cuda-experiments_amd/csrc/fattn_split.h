@@ -1087,7 +1087,11 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
     if (__builtin_amdgcn_ballot_w64(tmax > m_run + kRescaleNat)) {
         const float m_new = fmaxf(m_run, tmax);
         if (!first) {  // o, l are still 0 at a wave's first step
-            const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * log2e);  // m_run = -inf: 0
+            // (the branch is the wave's, by ballot: a column that has had no live key yet and has
+            // none in this step comes here with m_run = m_new = -inf, and exp2(-inf - -inf) is NaN,
+            // which 0 * NaN would keep in l and o once a later step brings it a key -- 1 there, as
+            // in fattn_bd.h / fattn_pf.h: l and o are still 0; m_run = -inf with m_new finite: 0)
+            const float alpha = (m_new == kNegInf) ? 1.0f : __builtin_amdgcn_exp2f((m_run - m_new) * log2e);
             l_run *= alpha;
 #pragma unroll
             for (int c = 0; c < NC; c++) o[c] *= alpha;

@@ -133,11 +133,12 @@ def scores64(o: op.OpProblem, round_q: bool = True):
             yield s, h, sc
 
 
-def lse_ref(o: op.OpProblem, sinks=None, f64: bool = False, round_q: bool = False) -> np.ndarray:
-    """float64 [S][NQ][H] (module docstring).  f64: over scores64(o, round_q)."""
+def lse_ref(o: op.OpProblem, sinks=None, f64: bool = False, round_q: bool = False, sc_list=None) -> np.ndarray:
+    """float64 [S][NQ][H] (module docstring).  f64: over scores64(o, round_q);
+    sc_list: list(sinks.scores(o)) when the caller already has it."""
     b = o.base
     out = np.empty((b.S, b.NQ, b.H))
-    for s, h, sc in (scores64(o, round_q) if f64 else sk.scores(o)):
+    for s, h, sc in (sc_list if sc_list is not None else scores64(o, round_q) if f64 else sk.scores(o)):
         r = sk.lse_rows(sc)
         if sinks is not None:
             r = np.logaddexp(r, np.float64(sinks[h]))
@@ -145,12 +146,13 @@ def lse_ref(o: op.OpProblem, sinks=None, f64: bool = False, round_q: bool = Fals
     return out
 
 
-def ref_uncertainty(o: op.OpProblem) -> float:
-    """max |lse over the oracle's f32 scores - lse over the float64 product of the same rounded operands|."""
-    a, b = lse_ref(o), lse_ref(o, f64=True, round_q=True)
+def ref_uncertainty(o: op.OpProblem, lse=None) -> float:
+    """max |lse over the oracle's f32 scores - lse over the float64 product of the same rounded operands|.
+    lse: lse_ref(o) when the caller already has it."""
+    a, b = lse_ref(o) if lse is None else lse, lse_ref(o, f64=True, round_q=True)
     ok = np.isfinite(a)
     assert np.array_equal(ok, np.isfinite(b))
-    return float(np.abs(a - b)[ok].max()) if ok.any() else 0.0
+    return float(np.abs(a[ok] - b[ok]).max()) if ok.any() else 0.0
 
 
 def merge_ref(outs, lses, sinks=None):
@@ -301,10 +303,11 @@ def window_mask(NQ: int, N: int) -> np.ndarray:
     return m
 
 
-def sink_values(H: int, N: int) -> np.ndarray:
-    """ln N + linspace(-2, 3, H), head h taking entry (5 h + 3) % H (tests/test_gpu_sinks.py)."""
-    vals = np.log(np.float64(N)) + np.linspace(-2.0, 3.0, H)
-    return vals[(5 * np.arange(H) + 3) % H].astype(np.float32)
+def sink_values(H: int, N: int, centre=None) -> np.ndarray:
+    """ln N + linspace(-2, 3, H), head h taking entry (5 h + 3) % H (tests/test_gpu_sinks.py).
+    centre (a number, or one per head): what stands for ln N where the scores are not O(1)."""
+    off = np.linspace(-2.0, 3.0, H)[(5 * np.arange(H) + 3) % H]
+    return ((np.log(np.float64(N)) if centre is None else np.asarray(centre, dtype=np.float64)) + off).astype(np.float32)
 
 
 def plane_case(spec, which: str) -> Case:

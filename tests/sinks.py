@@ -89,16 +89,16 @@ def factor(lse: np.ndarray, sink: float) -> np.ndarray:
         return (1.0 / (1.0 + np.exp(np.float64(sink) - lse))).astype(np.float32)
 
 
-def reference(sp: SinkProblem, sinks=None, plain: Optional[np.ndarray] = None) -> np.ndarray:
+def reference(sp: SinkProblem, sinks=None, plain: Optional[np.ndarray] = None, sc_list=None) -> np.ndarray:
     """f32 [S][NQ][H][D].  sinks: other values than sp.sinks (a capped or a
     mis-sliced array, for the CPU preconditions); plain: op_params.reference(sp)
-    when the caller already has it."""
+    and sc_list: list(scores(sp)), when the caller already has them."""
     sk = sp.sinks if sinks is None else np.asarray(sinks, dtype=np.float32)
     out = (op.reference(sp) if plain is None else plain).copy()
     if sk is None:
         return out
     assert sk.shape == (sp.base.H,)
-    for s, h, sc in scores(sp):
+    for s, h, sc in (scores(sp) if sc_list is None else sc_list):
         lse = lse_rows(sc)
         g = factor(lse, sk[h])
         out[s, :, h, :] = out[s, :, h, :] * g[:, None]
