@@ -10,6 +10,13 @@ HARNESS := $(BINDIR)/kernel_test
 
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function \
             -munsafe-fp-atomics -Iinclude
+# The IQ4_NL kernels (new with the type, all in units of their own) are built without the
+# packed-f32 VALU forms v_pk_add / mul / fma_f32, which hipcc otherwise forms from adjacent
+# scalar f32 operations: new kernels for this target do not rely on them (DESIGN.md section
+# 22).  Every other unit, and so every other type's kernel, keeps the flags it had.
+NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
+NOPK_UNITS := fattn_launch_iq4_nl_d64 fattn_launch_iq4_nl_d128 fattn_launch_iq4_nl_d256 fattn_launch_iq4_nl_conv
+unit_flags = $(HIPFLAGS) $(if $(filter $(1),$(NOPK_UNITS)),$(NOPK))
 CSRC := $(wildcard $(PKG)/csrc/*.hip)
 CHDR := $(wildcard $(PKG)/csrc/*.h) include/fattn.h include/fattn_debug.h
 
@@ -25,7 +32,7 @@ OBJS := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/%.o,$(CSRC))
 
 $(OBJDIR)/%.o: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(call unit_flags,$*) -c $< -o $@
 
 $(LIB): $(OBJS)
 	@mkdir -p $(LIBDIR)
@@ -35,7 +42,7 @@ $(LIB): $(OBJS)
 STAMP_OBJS := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/stamps_%.o,$(CSRC))
 $(OBJDIR)/stamps_%.o: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -DFATTN_STAMPS -c $< -o $@
+	$(HIPCC) $(call unit_flags,$*) -DFATTN_STAMPS -c $< -o $@
 stamps: $(LIBDIR)/libfattn_stamps.so
 $(LIBDIR)/libfattn_stamps.so: $(STAMP_OBJS)
 	@mkdir -p $(LIBDIR)
@@ -48,7 +55,7 @@ VFLAGS ?=
 VAR_OBJS := $(patsubst $(PKG)/csrc/%.hip,$(OBJDIR)/$(VAR)_%.o,$(CSRC))
 $(OBJDIR)/$(VAR)_%.o: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) $(VFLAGS) -c $< -o $@
+	$(HIPCC) $(call unit_flags,$*) $(VFLAGS) -c $< -o $@
 variant: $(VAR_OBJS)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -shared $(VAR_OBJS) -o $(LIBDIR)/libfattn_$(VAR).so
@@ -78,7 +85,7 @@ ISAS := $(patsubst $(PKG)/csrc/%.hip,$(ISADIR)/%.s,$(CSRC))
 isa: $(ISAS)
 $(ISADIR)/%.s: $(PKG)/csrc/%.hip $(CHDR)
 	@mkdir -p $(ISADIR)/$*.tmp
-	cd $(ISADIR)/$*.tmp && $(HIPCC) $(subst -Iinclude,-I$(CURDIR)/include,$(HIPFLAGS)) -c $(CURDIR)/$< -save-temps -o $*.o
+	cd $(ISADIR)/$*.tmp && $(HIPCC) $(subst -Iinclude,-I$(CURDIR)/include,$(call unit_flags,$*)) -c $(CURDIR)/$< -save-temps -o $*.o
 	mv $(ISADIR)/$*.tmp/$*-hip-amdgcn-amd-amdhsa-$(ARCH).s $@
 	rm -rf $(ISADIR)/$*.tmp
 

@@ -367,6 +367,7 @@ int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n
     visit(CacheTypes(), type, 0, [&](auto tc) {
         constexpr int T = decltype(tc)::value;
         if constexpr (is_row16(T)) hipLaunchKernelGGL(dequant_row16_kernel<T>, grid256(n), dim3(256), 0, st, (const uint16_t*)src, dst, n);
+        else if constexpr (is_codebook(T)) iq4nl_launch_dequant(grid256(n / QK), st, (const uint8_t*)src, dst, n / QK);
         else hipLaunchKernelGGL(dequant_kernel<T>, grid256(n / QK), dim3(256), 0, st, (const uint8_t*)src, dst, n / QK);
         return 0;
     });
@@ -387,7 +388,8 @@ int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_r
     if (!is_quant(type)) return FATTN_ERR_UNSUPPORTED_TYPE;
     const int64_t nb = k * n_rows / QK;
     visit(StageTypes(), type, 0, [&](auto tc) {
-        hipLaunchKernelGGL(quant_kernel<decltype(tc)::value>, grid256(nb), dim3(256), 0, st, src, (uint8_t*)dst, nb);
+        if constexpr (is_codebook(decltype(tc)::value)) iq4nl_launch_quant(grid256(nb), st, src, (uint8_t*)dst, nb);
+        else hipLaunchKernelGGL(quant_kernel<decltype(tc)::value>, grid256(nb), dim3(256), 0, st, src, (uint8_t*)dst, nb);
         return 0;
     });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;
@@ -415,7 +417,8 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     (void)hipGetLastError();
     visit(CacheTypes(), t, 0, [&](auto tc) {
-        hipLaunchKernelGGL(cpy_f32_kernel<decltype(tc)::value>, grid256(units), dim3(256), 0, st, a, units);
+        if constexpr (is_codebook(decltype(tc)::value)) iq4nl_launch_cpy(grid256(units), st, a, units);
+        else hipLaunchKernelGGL(cpy_f32_kernel<decltype(tc)::value>, grid256(units), dim3(256), 0, st, a, units);
         return 0;
     });
     return hipGetLastError() == hipSuccess ? FATTN_OK : FATTN_ERR_LAUNCH;

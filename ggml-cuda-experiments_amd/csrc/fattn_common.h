@@ -53,12 +53,14 @@ R visit(ValueList<Vs...>, int v, R none, F&& f) {
 // 32 elements {f16 d; [f16 m;] [u8 qh[4];] qs}: element j of a 4- / 5-bit block
 // in the low nibble of qs[j], j + 16 in the high one, bit j of the
 // little-endian u32 qh its fifth bit; x = q d + m (has_min) or (q - code_zero) d.
-template <int BE, int BB, bool MIN = false, bool QH = false, int QHO = 4, int QSO = 2, int ZERO = 0>
+// (CB: the code is no number but an index into the IQ4_NL codebook, x = kv[q] d)
+template <int BE, int BB, bool MIN = false, bool QH = false, int QHO = 4, int QSO = 2, int ZERO = 0, bool CB = false>
 struct RowLayout {
     static constexpr int block_elems = BE, block_bytes = BB;
     static constexpr bool has_min = MIN, has_qh = QH;        // the block holds m / qh
     static constexpr int qh_off = QHO, qs_off = QSO;         // ... byte offsets of qh and qs in it
     static constexpr int code_zero = ZERO;                   // the code's zero point, where the kernels subtract one
+    static constexpr bool codebook = CB;                     // decodes through kIq4nlValues: no kernel may take the code as a number
 };
 template <int T>
 struct TypeInfo;
@@ -72,18 +74,20 @@ template <> struct TypeInfo<FATTN_TYPE_Q4_0> : RowLayout<QK, 18> { static conste
 template <> struct TypeInfo<FATTN_TYPE_Q4_1> : RowLayout<QK, 20, true, false, 4, 4> { static constexpr const char* name = "q4_1"; };
 template <> struct TypeInfo<FATTN_TYPE_Q5_0> : RowLayout<QK, 22, false, true, 2, 6, 16> { static constexpr const char* name = "q5_0"; };
 template <> struct TypeInfo<FATTN_TYPE_Q5_1> : RowLayout<QK, 24, true, true, 4, 8> { static constexpr const char* name = "q5_1"; };
+// IQ4_NL: Q4_0's bytes {f16 d; u8 qs[16]}, x = kv[q] d; code_zero is the bias of the codebook bytes the kernels look up (kv + 128)
+template <> struct TypeInfo<FATTN_TYPE_IQ4_NL> : RowLayout<QK, 18, false, false, 4, 2, 128, true> { static constexpr const char* name = "iq4_nl"; };
 
 // The type lists every dispatch site names (a new cache type joins the ones it belongs to)
-using CacheTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;
-using RowTypes = ValueList<FATTN_TYPE_F32, FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // fattn_row_size
+using CacheTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL>;
+using RowTypes = ValueList<FATTN_TYPE_F32, FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL>;  // fattn_row_size
 using CoreTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0>;  // every kernel family; mixed K / V pairs; MLA
 using QuantTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0>;                 // ... the block types among them
-// the three block types with a fifth bit and / or an affine term (is_kv_ext):
+// the block types with a fifth bit, an affine term or a codebook (is_kv_ext):
 // only the split kernel and the prefill staging take them
-using ExtTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;
-using SplitOnlyTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_BF16>;  // K and V of one type, D = 64 / 128 / 256
-using StageTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // block types: staged to f16 for prefill, quantize / dequantize
-using SetRowsTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1>;  // (no BF16)
+using ExtTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL>;
+using SplitOnlyTypes = ValueList<FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL, FATTN_TYPE_BF16>;  // K and V of one type, D = 64 / 128 / 256
+using StageTypes = ValueList<FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL>;  // block types: staged to f16 for prefill, quantize / dequantize
+using SetRowsTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL>;  // (no BF16)
 using KShiftTypes = RowTypes;  // fattn_k_shift rotates every row type in place, an F32 view included
 
 // TypeInfo by run-time type: the row of type t, or the empty row (block_elems = 0)
@@ -92,15 +96,16 @@ struct TypeDesc {
     int block_elems, block_bytes;
     bool has_min, has_qh;
     int qh_off, qs_off, code_zero;
+    bool codebook;
 };
 template <int T>
 constexpr TypeDesc desc_of() {
     using I = TypeInfo<T>;
-    return {I::name, I::block_elems, I::block_bytes, I::has_min, I::has_qh, I::qh_off, I::qs_off, I::code_zero};
+    return {I::name, I::block_elems, I::block_bytes, I::has_min, I::has_qh, I::qh_off, I::qs_off, I::code_zero, I::codebook};
 }
 template <int... Ts>
 __host__ __device__ constexpr TypeDesc type_desc(ValueList<Ts...>, int t) {
-    TypeDesc d = {"?", 0, 0, false, false, 4, 2, 0};
+    TypeDesc d = {"?", 0, 0, false, false, 4, 2, 0, false};
     ((t == Ts ? (void)(d = desc_of<Ts>()) : (void)0), ...);
     return d;
 }
@@ -115,6 +120,7 @@ __host__ __device__ constexpr bool has_qh(int t) { return type_desc(t).has_qh; }
 __host__ __device__ constexpr int qh_off(int t) { return type_desc(t).qh_off; }
 __host__ __device__ constexpr int qs_off(int t) { return type_desc(t).qs_off; }
 __host__ __device__ constexpr int code_zero(int t) { return type_desc(t).code_zero; }
+__host__ __device__ constexpr bool is_codebook(int t) { return type_desc(t).codebook; }
 constexpr int kQ8Bytes = TypeInfo<FATTN_TYPE_Q8_0>::block_bytes;
 constexpr int kQ4Bytes = TypeInfo<FATTN_TYPE_Q4_0>::block_bytes;
 
@@ -126,7 +132,8 @@ constexpr size_t row_size(int type, int64_t k) {
 
 // waves per SIMD of the split kernel's register budget: its __launch_bounds__
 // and the planner's occupancy figure (size_split)
-// (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4)
+// (Q4_1 / Q5_0 / Q5_1: the qh words and the second accumulator spill at 4;
+// IQ4_NL: the byte-gathered V operand and its table step)
 __host__ __device__ constexpr int split_bounds_wps(int kt, int gran, int D) {
     return (is_row16(kt) || gran == 4 || D == 256 || is_kv_ext(kt)) ? 2 : 4;
 }
@@ -173,6 +180,33 @@ __device__ __forceinline__ void u4x4_to_h2x2(uint32_t w, f16x2& lo, f16x2& hi) {
     const f16x2 off = {(f16)-1032.0f, (f16)-1032.0f};
     lo = as_h2(p0) + off;
     hi = as_h2(p1) + off;
+}
+
+// ---------------------------------------------------------------- IQ4_NL codebook
+// x = kv[q] d.  The kernels hold the table as four dwords of BIASED bytes kv +
+// 128 (1 .. 241; compile-time constants, so SGPRs or literals, never LDS) and
+// decode four codes at once from a dword c of 4-bit codes, one per byte: one
+// v_perm_b32 over table dwords {1, 0} and one over {3, 2}, both selected by c &
+// 7, then a third v_perm picks byte k from the second result where bit 3 of code
+// k is set (selector k + 4) and from the first where it is not (selector k).
+constexpr int kIq4nlValues[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+constexpr uint32_t iq4nl_table_dword(int i) {
+    uint32_t w = 0;
+    for (int k = 0; k < 4; k++) w |= (uint32_t)(kIq4nlValues[4 * i + k] + 128) << (8 * k);
+    return w;
+}
+// four codes (the low 4 bits of each byte of c; the high 4 must be zero) -> their four bytes kv + 128
+__device__ __forceinline__ uint32_t iq4nl_lut4(uint32_t c) {
+    constexpr uint32_t T0 = iq4nl_table_dword(0), T1 = iq4nl_table_dword(1), T2 = iq4nl_table_dword(2), T3 = iq4nl_table_dword(3);
+    const uint32_t s = c & 0x07070707u;
+    const uint32_t lo = perm_b32(T1, T0, s), hi = perm_b32(T3, T2, s);
+    return perm_b32(hi, lo, ((c >> 1) & 0x04040404u) | 0x03020100u);
+}
+// ... -> kv[] of the four codes as f32 (the conversions), by one lookup
+__device__ __forceinline__ void iq4nl_values4(uint32_t c, float (&v)[4]) {
+    const uint32_t t = iq4nl_lut4(c);
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = (float)(int)((t >> (8 * k)) & 0xFFu) - 128.0f;
 }
 
 // ---------------------------------------------------------------- LDS reads

@@ -101,10 +101,13 @@ __device__ __forceinline__ void k_shift_load_block(const uint8_t* blk, int l, fl
         if constexpr (has_qh(T)) hb = ((uint32_t)h[qh_off(T) / 2 + (l >> 2)] >> (4 * (l & 3))) & 0xFu;
         float m = 0.0f;
         if constexpr (has_min(T)) m = (float)__builtin_bit_cast(f16, h[1]);
+        [[maybe_unused]] float kv[4];
+        if constexpr (is_codebook(T)) iq4nl_values4(nib, kv);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int q = (int)(((nib >> (8 * k)) & 0xFu) | (((hb >> k) & 1u) << 4));
-            if constexpr (has_min(T)) x[k] = opaque((float)q * d) + m;
+            if constexpr (is_codebook(T)) x[k] = d * kv[k];
+            else if constexpr (has_min(T)) x[k] = opaque((float)q * d) + m;
             else x[k] = (float)(q - zero) * d;
         }
     }
@@ -253,6 +256,9 @@ __global__ __launch_bounds__(256) void k_shift_kernel(const KShiftArgs a) {
         }
     }
 }
+
+// k_shift_kernel<IQ4_NL, neox, false> (fattn_launch_iq4_nl_conv.hip)
+void iq4nl_launch_k_shift(bool neox, dim3 grid, hipStream_t st, const KShiftArgs& a);
 
 // Waves below which the heads are spread over the grid's y instead of walked by
 // one lane group: 256 CUs x 4 SIMDs x 8 waves.  Past it the chip is full either

@@ -41,7 +41,7 @@ enum class Kernel {
 // (choose_kernel), its LDS sizes (lds_bytes_of) and make_plan's last check all
 // read it.  vt may be VT_F16T; Kernel::Mla: D is K's row length.
 using HeadDims = ValueList<64, 80, 96, 128, 256>;
-using VTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, VT_F16T>;  // CacheTypes and the transposed f16 V
+using VTypes = ValueList<FATTN_TYPE_F16, FATTN_TYPE_BF16, FATTN_TYPE_Q8_0, FATTN_TYPE_Q4_0, FATTN_TYPE_Q4_1, FATTN_TYPE_Q5_0, FATTN_TYPE_Q5_1, FATTN_TYPE_IQ4_NL, VT_F16T>;  // CacheTypes and the transposed f16 V
 // head dims of the split kernel over mixed K / V types and over SplitOnlyTypes
 constexpr bool split_dim3(int D) { return D == 64 || D == 128 || D == 256; }
 // the split kernel's loader-wave form (fattn_split_ld_kernel): one K / V type of CoreTypes, D = 64 / 128
@@ -314,6 +314,7 @@ void launch_prepass(Types, int stage_kt, dim3 grid, hipStream_t st, const PfPrep
 }
 // ... of ExtTypes (instantiated in fattn_launch_kv_ext.hip)
 void launch_prepass_kv_ext(int stage_kt, dim3 grid, hipStream_t st, const PfPrepassArgs& pa);
+void iq4nl_launch_prepass(dim3 grid, hipStream_t st, const PfPrepassArgs& pa);
 
 template <int KT, int D, bool HM, typename A>
 int launch_pf_a(const Plan& pl, hipStream_t st, const Events& ev) {
@@ -412,7 +413,7 @@ extern template int launch_mixed<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_mixed<128>(const Plan&, hipStream_t, const Events&);
 extern template int launch_mixed<256>(const Plan&, hipStream_t, const Events&);
 
-// split kernel over a Q4_1 / Q5_0 / Q5_1 cache (K and V of type T; instantiated
+// split kernel over a Q4_1 / Q5_0 / Q5_1 / IQ4_NL cache (K and V of type T; instantiated
 // once per (T, D) in fattn_launch_<type>_d<D>.hip; D = 64, 128, 256)
 template <int T, int D>
 int launch_kv_ext(const Plan& pl, hipStream_t st, const Events& ev) {
@@ -426,6 +427,7 @@ int launch_kv_ext(const Plan& pl, hipStream_t st, const Events& ev) {
 FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q4_1)
 FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_0)
 FATTN_KV_EXT_EXTERN(FATTN_TYPE_Q5_1)
+FATTN_KV_EXT_EXTERN(FATTN_TYPE_IQ4_NL)
 #undef FATTN_KV_EXT_EXTERN
 
 // split kernel over a BF16 cache (K and V both BF16: raw bf16 rows into

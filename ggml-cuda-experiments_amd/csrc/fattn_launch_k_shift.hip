@@ -15,7 +15,9 @@ namespace {
 
 template <int T, bool NEOX>
 void launch(bool vec, dim3 grid, hipStream_t st, const KShiftArgs& a) {
-    if constexpr (is_quant(T)) {
+    if constexpr (is_codebook(T)) {
+        iq4nl_launch_k_shift(NEOX, grid, st, a);
+    } else if constexpr (is_quant(T)) {
         hipLaunchKernelGGL((k_shift_kernel<T, NEOX, false>), grid, dim3(256), 0, st, a);
     } else {
         if (vec) hipLaunchKernelGGL((k_shift_kernel<T, NEOX, true>), grid, dim3(256), 0, st, a);

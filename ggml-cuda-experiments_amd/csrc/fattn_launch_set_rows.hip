@@ -22,7 +22,8 @@ constexpr int64_t kUnrollMinUnits = 1 << 17;
 template <int T, int K>
 void launch_k(bool vec, dim3 grid, hipStream_t st, const SetRowsArgs& a) {
     grid.x = (a.units + 32u * K - 1u) / (32u * K);
-    if (vec) hipLaunchKernelGGL((set_rows_kernel<T, true, K>), grid, dim3(256), 0, st, a);
+    if constexpr (is_codebook(T)) iq4nl_launch_set_rows(vec, K != 1, grid, st, a);
+    else if (vec) hipLaunchKernelGGL((set_rows_kernel<T, true, K>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((set_rows_kernel<T, false, K>), grid, dim3(256), 0, st, a);
 }
 template <int T>

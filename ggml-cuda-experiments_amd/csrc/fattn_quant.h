@@ -1,10 +1,12 @@
-// fattn_quant.h -- ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 row conversions on gfx950.
+// fattn_quant.h -- ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL row conversions on gfx950.
 //
 // The reference has no quantized code at all; these follow the
 // published upstream-ggml algorithms (ggml-quants.c quantize_row_q8_0_ref,
 // quantize_row_q4_0_ref, dequantize_row_q8_0, dequantize_row_q4_0), restated in
 // oracle/fattn_oracle.c (Q4_1 / Q5_0 / Q5_1: quantize_row_q4_1_ref, _q5_0_ref,
-// _q5_1_ref and their dequantize_row_*, restated in tests/kv_types.py), and are
+// _q5_1_ref and their dequantize_row_*, restated in tests/kv_types.py; IQ4_NL:
+// the cache-write quantiser and dequantize_row_iq4_nl, restated in
+// tests/iq4_nl.py), and are
 // bit-exact with that restatement: every
 // multiply/add is a separately rounded IEEE op (contraction off + barriers),
 // divisions are correctly rounded (hipcc default), f32->f16 is round-to-nearest-even.
@@ -27,7 +29,7 @@ __device__ __forceinline__ float opaque(float x) {
     return x;
 }
 
-// One ggml block -> its 32 f32 values (dequantize_row_q8_0 / _q4_0 / _q4_1 / _q5_0 / _q5_1)
+// One ggml block -> its 32 f32 values (dequantize_row_q8_0 / _q4_0 / _q4_1 / _q5_0 / _q5_1 / _iq4_nl)
 template <int T>
 __device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, float* __restrict__ y) {
 #pragma clang fp contract(off)
@@ -42,6 +44,20 @@ __device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, f
             v.z = (float)(int8_t)blk[4 + j] * d;
             v.w = (float)(int8_t)blk[5 + j] * d;
             *(f32x4*)(y + j) = v;
+        }
+    } else if constexpr (is_codebook(T)) {
+#pragma unroll
+        for (int j = 0; j < QK / 2; j += 4) {  // four bytes of qs: elements j .. j + 3 and j + 16 .. j + 19
+            const uint8_t* q = blk + qs_off(T) + j;
+            const uint32_t w = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+            float lo[4], hi[4];
+            iq4nl_values4(w & 0x0F0F0F0Fu, lo);
+            iq4nl_values4((w >> 4) & 0x0F0F0F0Fu, hi);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                y[j + k] = d * lo[k];
+                y[j + k + QK / 2] = d * hi[k];
+            }
         }
     } else {
         constexpr int zero = T == FATTN_TYPE_Q4_0 ? 8 : code_zero(T);  // (Q4_0's 8: the kernels' nibble trick takes it, not code_zero)
@@ -154,7 +170,7 @@ __device__ __forceinline__ void quant_block_q4_0(const float (&xv)[QK], uint8_t*
 template <int T>
 __device__ __forceinline__ void quant_block_ext(const float (&xv)[QK], uint8_t* blk) {
 #pragma clang fp contract(off)
-    static_assert(is_kv_ext(T), "");
+    static_assert(is_kv_ext(T) && !is_codebook(T), "");
     float d, mn = 0.0f;
     if constexpr (T == FATTN_TYPE_Q5_0) {
         float amax = 0.0f, mx = 0.0f;
@@ -214,11 +230,75 @@ __device__ __forceinline__ void quant_block_ext(const float (&xv)[QK], uint8_t* 
     }
 }
 
+// IQ4_NL, ggml's cache write f32 -> iq4_nl.  iq4nl_code: best_index of v = x * id,
+// the codebook entry nearest to v with a tie going up.  ggml bisects the table
+// on `v < kv[mav]`; the interval that finds, kv[mu - 1] <= v < kv[mu], is the one
+// with mu - 1 = the number of entries kv[1 .. 14] that are not above v (counted
+// with the same compare, negated: a NaN climbs to mu = 15 as it does there).
+// The two ends come back through the codebook; `kvq` is kv[code] for the refit.
+__device__ __forceinline__ uint32_t iq4nl_code(float v, float& kvq) {
+#pragma clang fp contract(off)
+    uint32_t mu = 1;
+#pragma unroll
+    for (int i = 1; i < 15; i++) mu += !(v < (float)kIq4nlValues[i]);
+    const uint32_t t = iq4nl_lut4((mu - 1) | (mu << 8));
+    const float lo = (float)(int)(t & 0xFFu) - 128.0f, hi = (float)(int)((t >> 8) & 0xFFu) - 128.0f;
+    const bool down = opaque(v - lo) < opaque(hi - v);
+    uint32_t q = down ? mu - 1 : mu;
+    kvq = down ? lo : hi;
+    if (v >= 113.0f) q = 15, kvq = 113.0f;
+    if (v <= -127.0f) q = 0, kvq = -127.0f;
+    return q;
+}
+// The refit of d over a block: sumqx, sumq2 are sequential chains over j = 0 .. 15
+// of (w v x)[j] + (w v x)[j + 16] and (w v v)[j] + (w v v)[j + 16], w = x x, every
+// operation rounded on its own.  One element's two products:
+__device__ __forceinline__ void iq4nl_terms(float x, float v, float& qx, float& q2) {
+#pragma clang fp contract(off)
+    const float wv = opaque(opaque(x * x) * v);
+    qx = opaque(wv * x);
+    q2 = opaque(wv * v);
+}
+// ... and the stored scale from the sums (d0: the scale the codes were chosen with)
+__device__ __forceinline__ uint32_t iq4nl_scale_bits(float sumqx, float sumq2, float d0) {
+    const float d = sumq2 > 0.0f ? sumqx / sumq2 : d0;
+    return __builtin_bit_cast(uint16_t, (f16)opaque(d));
+}
+__device__ __forceinline__ void quant_block_iq4_nl(const float (&xv)[QK], uint8_t* blk) {
+#pragma clang fp contract(off)
+    float amax = 0.0f, mx = 0.0f;
+#pragma unroll
+    for (int j = 0; j < QK; j++) {
+        if (amax < fabsf(xv[j])) {
+            amax = fabsf(xv[j]);
+            mx = xv[j];
+        }
+    }
+    const float d0 = mx / -127.0f;
+    const float id = d0 != 0.0f ? 1.0f / d0 : 0.0f;
+    float sumqx = 0.0f, sumq2 = 0.0f;
+#pragma unroll
+    for (int j = 0; j < QK / 2; j++) {
+        float v0, v1, a0, a1, b0, b1;
+        const uint32_t q0 = iq4nl_code(opaque(xv[j] * id), v0);
+        const uint32_t q1 = iq4nl_code(opaque(xv[j + QK / 2] * id), v1);
+        blk[2 + j] = (uint8_t)(q0 | (q1 << 4));
+        iq4nl_terms(xv[j], v0, a0, b0);
+        iq4nl_terms(xv[j + QK / 2], v1, a1, b1);
+        sumqx = opaque(sumqx + opaque(a0 + a1));
+        sumq2 = opaque(sumq2 + opaque(b0 + b1));
+    }
+    const uint32_t dh = iq4nl_scale_bits(sumqx, sumq2, d0);
+    blk[0] = dh & 0xff;
+    blk[1] = dh >> 8;
+}
+
 // the block function of type T
 template <int T>
 __device__ __forceinline__ void quant_block(const float (&xv)[QK], uint8_t* blk) {
     if constexpr (T == FATTN_TYPE_Q8_0) quant_block_q8_0(xv, blk);
     else if constexpr (T == FATTN_TYPE_Q4_0) quant_block_q4_0(xv, blk);
+    else if constexpr (is_codebook(T)) quant_block_iq4_nl(xv, blk);
     else quant_block_ext<T>(xv, blk);
 }
 
@@ -237,7 +317,7 @@ __global__ __launch_bounds__(256) void quant_kernel(const float* __restrict__ sr
     quant_block<T>(xv, dst + i * TypeInfo<T>::block_bytes);
 }
 
-// Strided f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 copy: ggml's GGML_OP_CPY into a KV-cache view
+// Strided f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL copy: ggml's GGML_OP_CPY into a KV-cache view
 // (upstream ggml cpy f32 -> f16/q8_0/q4_0).  src and dst
 // have the same ne (ne0 = row length, a multiple of 32 for the block types)
 // and any byte strides nb1..nb3; rows are contiguous (src nb0 = 4, dst nb0 =
@@ -274,6 +354,13 @@ __global__ __launch_bounds__(256) void cpy_f32_kernel(const CpyArgs a, int64_t u
     }
 }
 
+// The IQ4_NL instantiations of the three kernels above live in fattn_launch_iq4_nl_conv.hip
+// (with those of set_rows_kernel, k_shift_kernel and the staging pre-pass): the type's
+// kernels are built with flags of their own (Makefile NOPK_UNITS), the other types' are not
+void iq4nl_launch_dequant(dim3 grid, hipStream_t st, const uint8_t* src, float* dst, int64_t nblocks);
+void iq4nl_launch_quant(dim3 grid, hipStream_t st, const float* src, uint8_t* dst, int64_t nblocks);
+void iq4nl_launch_cpy(dim3 grid, hipStream_t st, const CpyArgs& a, int64_t units);
+
 // Prefill K/V staging (the prefill planner's default for Q8_0 / Q4_0 caches):
 // the quantised rows of every (sequence, kv head) -- contiguous blocks, head
 // base at ik3 * nb3 + ik2 * nb2 -- become f16 rows [Skv][Hkv][N][D] in the
@@ -295,7 +382,20 @@ __device__ __forceinline__ void kv_stage_f16_block(const uint8_t* __restrict__ s
     const uint8_t* blk8 = src + (int64_t)seq * nb3 + (int64_t)head * nb2 + b * TypeInfo<KT>::block_bytes;
     const uint16_t* blk = (const uint16_t*)blk8;  // (blocks are 2-byte aligned)
     f16x8 h;
-    if constexpr (is_kv_ext(KT)) {
+    if constexpr (is_codebook(KT)) {
+        // IQ4_NL: h(kv[q] d), the exact product rounded once -- the bits of the split
+        // kernel's K operand.  The thread's 8 codes are one nibble of 8 bytes of qs: two lookups
+        const f16 d = __builtin_bit_cast(f16, blk[0]);
+        const uint16_t* qw = blk + 1 + 4 * (j & 1);
+#pragma unroll
+        for (int e = 0; e < 2; e++) {
+            const uint32_t w = (uint32_t)qw[2 * e] | ((uint32_t)qw[2 * e + 1] << 16);
+            float v[4];
+            iq4nl_values4((j < 2 ? w : w >> 4) & 0x0F0F0F0Fu, v);
+#pragma unroll
+            for (int k = 0; k < 4; k++) h[4 * e + k] = (f16)v[k] * d;
+        }
+    } else if constexpr (is_kv_ext(KT)) {
         // Q4_1 / Q5_0 / Q5_1: the f16 the split kernel's K operand (k_operand_ext,
         // fattn_split.h) produces for the same element.  Q5_0: h((q - 16) d), the
         // exact product rounded once.  Q4_1 / Q5_1: the f16 fma h(q d + m) of the

@@ -123,6 +123,54 @@ __device__ __forceinline__ void set_rows_block(const float (&x)[4], int l, bool 
             store_u16(blk + 2 + 4 * l, w);
             store_u16(blk + 4 + 4 * l, w >> 16);
         }
+    } else if constexpr (is_codebook(T)) {
+        // IQ4_NL (quant_block_iq4_nl): the first-wins |max| scan as Q4_0's, each lane's
+        // four codes by the codebook search, then the refit's two 16-term chains.  Term
+        // j of a chain is element j's product plus element (j + 16)'s: lanes l and l ^ 4
+        // hold those two, so after one exchange both quads of the group hold all 16
+        // terms (the sum of two floats does not depend on their order), term 4i + k in
+        // lane i of each quad.  Every lane then walks the chain in order, 16 additions,
+        // each operand a quad_perm broadcast of lane i: no LDS, and all eight lanes end
+        // with the same two sums.
+        float amax = 0.0f, mx = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            if (amax < fabsf(x[k])) {
+                amax = fabsf(x[k]);
+                mx = x[k];
+            }
+        }
+        merge_amax<1>(amax, mx, l);
+        merge_amax<2>(amax, mx, l);
+        merge_amax<4>(amax, mx, l);
+        const float d0 = mx / -127.0f;
+        const float id = d0 != 0.0f ? 1.0f / d0 : 0.0f;
+        uint32_t w = 0;  // the four codes, one per byte
+        float tx[4], t2[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            float v, qx, q2;
+            w |= iq4nl_code(opaque(x[k] * id), v) << (8 * k);
+            iq4nl_terms(x[k], v, qx, q2);
+            tx[k] = opaque(qx + xor_lane<4>(qx));
+            t2[k] = opaque(q2 + xor_lane<4>(q2));
+        }
+        float sumqx = 0.0f, sumq2 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0x00>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0x00>(t2[k]));
+#pragma unroll
+        for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0x55>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0x55>(t2[k]));
+#pragma unroll
+        for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0xAA>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0xAA>(t2[k]));
+#pragma unroll
+        for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0xFF>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0xFF>(t2[k]));
+        const uint32_t dh = iq4nl_scale_bits(sumqx, sumq2, d0);
+        const uint32_t pw = xor_lane<4>(w);
+        const uint32_t qs = (l < 4 ? w : pw) | ((l < 4 ? pw : w) << 4);
+        if (write) {
+            store_u16(blk + 2 + 4 * (l & 3) + (l < 4 ? 0 : 2), l < 4 ? qs : qs >> 16);
+            if (l == 0) store_u16(blk, dh);
+        }
     } else {
         float d, mn = 0.0f;
         if constexpr (!has_min(T)) {
@@ -311,6 +359,9 @@ __global__ __launch_bounds__(256) void set_rows_kernel(const SetRowsArgs a) {
         }
     }
 }
+
+// set_rows_kernel<IQ4_NL, vec, unroll ? kSetRowsUnroll : 1> (fattn_launch_iq4_nl_conv.hip); grid.x as launch_k sets it
+void iq4nl_launch_set_rows(bool vec, bool unroll, dim3 grid, hipStream_t st, const SetRowsArgs& a);
 
 // units per lane group of the large-write form, and the unit count from which the host takes it
 constexpr int kSetRowsUnroll = 4;

@@ -197,7 +197,8 @@ __device__ __forceinline__ void issue_step(const SplitArgs& a, const StepSrc& rs
 // Quantised V: the A operand of P.V is the exact integer code plus the f16
 // magic number 1024 (0x6400 | code), the block scale folded into P; v_code_off
 // is what the epilogue takes off per unit of corr[b] = sum P d_b: 1024 plus the
-// code's zero point (Q8_0: 128 by the sign flip, Q4_0: 8, Q5_0: 16) or, for the
+// code's zero point (Q8_0: 128 by the sign flip, Q4_0: 8, Q5_0: 16, IQ4_NL: the
+// 128 its looked-up codebook bytes are biased by) or, for the
 // unsigned codes of Q4_1 / Q5_1, their centre v_code_centre (8 / 16).  The
 // centre is not in the format: P d is rounded to f16, so the product sum carries
 // sum eps_r P_r d_r (q_r - c) -- half the error with c at the middle of the code
@@ -208,7 +209,7 @@ constexpr int v_code_centre() { return VT == FATTN_TYPE_Q4_1 ? 8 : VT == FATTN_T
 template <int VT>
 constexpr float v_code_off() {
     return VT == FATTN_TYPE_Q8_0 ? 1152.0f : VT == FATTN_TYPE_Q4_0 ? 1032.0f : VT == FATTN_TYPE_Q5_0 ? 1040.0f
-           : 1024.0f + (float)v_code_centre<VT>();
+           : is_codebook(VT) ? 1024.0f + (float)code_zero(VT) : 1024.0f + (float)v_code_centre<VT>();
 }
 // per-block f32 accumulators a wave carries beside O: corr[b], and for Q4_1 /
 // Q5_1 behind them sum P (m_b + c d_b) (plain P, not the rounded P d: exact f16
@@ -230,7 +231,9 @@ constexpr int corr_len() { return (D + QK - 1) / QK * (has_min(VT) ? 2 : 1); }
 // form (same operands, same MFMAs, same order): bit-identical results.
 // EPI: the kernel's epilogue (split_epilogue); 1 and 2 are the one-row forms.
 // (Q4_1 / Q5_0 / Q5_1 keep the plain form: their kernels sit at 2 waves per
-// SIMD by the qh words and the second accumulator, not by the scales.)
+// SIMD by the qh words and the second accumulator, not by the scales.  IQ4_NL
+// keeps it too: its layout is Q4_0's and the packed form would apply, but its V
+// operand is the byte-gathered one of the three, not pv_block_q's.)
 template <int VT, int EPI>
 constexpr bool col_packed() { return EPI != 0 && (VT == FATTN_TYPE_Q8_0 || VT == FATTN_TYPE_Q4_0); }
 // f32 accumulators beside O in the kernel: one corr when column-packed
@@ -354,7 +357,10 @@ __device__ __forceinline__ f16x8 k_operand(const uint8_t* kb, int row, int g, in
 // Q5_0: times d, one f16 rounding of the exact product; Q4_1 / Q5_1: one packed
 // f16 fma q d + m, one rounding of the exact sum.  Rows are whole dwords, so
 // within a row d (and m) share the dword at BB b (Q5_0: BB b & ~3, d in either
-// half), qh and qs sit at a compile-time offset modulo 4 (b is unrolled)
+// half), qh and qs sit at a compile-time offset modulo 4 (b is unrolled).
+// IQ4_NL: the four codes of a dword go through the codebook first (iq4nl_lut4:
+// bytes kv + 128), then the same widening, minus 1024 + 128, times d: h(kv d),
+// one f16 rounding of the exact product, the bits kv_stage_f16_block writes
 template <int KT, int D>
 __device__ __forceinline__ f16x8 k_operand_ext(const uint8_t* kb, int row, int g, int b) {
     constexpr int BB = TypeInfo<KT>::block_bytes;
@@ -372,6 +378,10 @@ __device__ __forceinline__ f16x8 k_operand_ext(const uint8_t* kb, int row, int g
         const uint32_t q8 = (qh >> (8 * g)) & 0xFFu;  // the fifth bits of elements 8g .. 8g + 7
         cx |= bits4_to_bit4(q8 & 0xFu);
         cy |= bits4_to_bit4(q8 >> 4);
+    }
+    if constexpr (is_codebook(KT)) {
+        cx = iq4nl_lut4(cx);
+        cy = iq4nl_lut4(cy);
     }
     constexpr f16 zo = (f16)(-1024.0f - (float)code_zero(KT));
     const f16x2 off = {zo, zo};
@@ -1196,7 +1206,7 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
             if constexpr (!is_kv_ext(C::VTT)) {  // Q8_0 / Q4_0
                 pv_block_q<C::VTT, D>(vb, b, g, i16, pbd, o[2 * b], o[2 * b + 1]);
             } else {
-                // Q4_1 / Q5_0 / Q5_1: byte i of qs carries column i (low nibble) and 16 + i
+                // Q4_1 / Q5_0 / Q5_1 / IQ4_NL: byte i of qs carries column i (low nibble) and 16 + i
                 // (high nibble), bits i and 16 + i of the row's qh their fifth bits
                 constexpr int VTT = C::VTT;
                 if constexpr (has_min(VTT)) {
@@ -1235,14 +1245,28 @@ __device__ __forceinline__ void split_step(const SplitArgs& a, const uint8_t* bu
                     }
                 }
                 u32x4 al, ah;  // f16 pairs 1024 + code (exact)
+                if constexpr (is_codebook(VTT)) {
+                    // IQ4_NL: four rows' bytes to a dword, its low and high nibbles through the
+                    // codebook (bytes kv + 128), each result widened to two f16 pairs 1024 + byte
 #pragma unroll
-                for (int pr = 0; pr < 4; pr++) {
-                    const uint32_t x = w[2 * pr] | (w[2 * pr + 1] << 16);
-                    al[pr] = (x & 0x000F000Fu) | 0x64006400u;
-                    ah[pr] = ((x >> 4) & 0x000F000Fu) | 0x64006400u;
-                    if constexpr (has_qh(VTT)) {
-                        al[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c040c00u) << 4;
-                        ah[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c060c02u) << 4;
+                    for (int h = 0; h < 2; h++) {
+                        const uint32_t x = w[4 * h] | (w[4 * h + 1] << 8) | (w[4 * h + 2] << 16) | (w[4 * h + 3] << 24);
+                        const uint32_t tl = iq4nl_lut4(x & 0x0F0F0F0Fu), th = iq4nl_lut4((x >> 4) & 0x0F0F0F0Fu);
+                        al[2 * h] = perm_b32(0x64646464u, tl, 0x04010400u);
+                        al[2 * h + 1] = perm_b32(0x64646464u, tl, 0x04030402u);
+                        ah[2 * h] = perm_b32(0x64646464u, th, 0x04010400u);
+                        ah[2 * h + 1] = perm_b32(0x64646464u, th, 0x04030402u);
+                    }
+                } else {
+#pragma unroll
+                    for (int pr = 0; pr < 4; pr++) {
+                        const uint32_t x = w[2 * pr] | (w[2 * pr + 1] << 16);
+                        al[pr] = (x & 0x000F000Fu) | 0x64006400u;
+                        ah[pr] = ((x >> 4) & 0x000F000Fu) | 0x64006400u;
+                        if constexpr (has_qh(VTT)) {
+                            al[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c040c00u) << 4;
+                            ah[pr] |= perm_b32(hb[2 * pr + 1], hb[2 * pr], 0x0c060c02u) << 4;
+                        }
                     }
                 }
                 o[2 * b] = mfma16(__builtin_bit_cast(f16x8, al), pbd, o[2 * b]);

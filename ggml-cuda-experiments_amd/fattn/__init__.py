@@ -22,11 +22,12 @@ LIB_PATH = os.path.normpath(os.path.join(_PKG_DIR, "..", "lib", os.environ.get("
 # ggml_type numbering (include/fattn.h)
 TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0 = 0, 1, 2, 8
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
+TYPE_IQ4_NL = 20
 TYPE_I32, TYPE_I64 = 26, 27   # index tensors of set_rows only
 TYPE_BF16 = 30                # 2-byte elements: K / V of flash_attn_ext, dst of cpy / quantize (not of set_rows)
 TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
-              "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1, "bf16": TYPE_BF16}
-BLOCK_TYPES = (TYPE_Q8_0, TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1)
+              "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1, "iq4_nl": TYPE_IQ4_NL, "bf16": TYPE_BF16}
+BLOCK_TYPES = (TYPE_Q8_0, TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1, TYPE_IQ4_NL)
 
 FATTN_OK = 0
 ERRORS = {
@@ -402,7 +403,7 @@ def _tptr(t) -> int:
 
 def kv_view(buf, typ: int, D: int, N: int, Hkv: int, S: int = 1, layout: str = "head") -> View:
     """View of a KV cache held in a byte (or f16) torch tensor; typ: TYPE_F16,
-    TYPE_BF16 or a block type (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1).
+    TYPE_BF16 or a block type (Q8_0, Q4_0, Q4_1, Q5_0, Q5_1, IQ4_NL).
 
     layout "head": [S][Hkv][N][row]   (per-head contiguous; reference decode layout,
                    src/flash_row_float.h:19,58)
@@ -538,14 +539,14 @@ def quantize(x, typ: int, stream=None):
 
 
 def cpy(src: View, dst: View, stream=None):
-    """GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view (the KV-cache
+    """GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL into a strided view (the KV-cache
     write, include/fattn.h fattn_cpy); src/dst are ggml views of device memory."""
     s, d = src.c(), dst.c()
     _check(lib().fattn_cpy(C.byref(s), C.byref(d), _stream(stream)), "fattn_cpy")
 
 
 def set_rows(src: View, idx: View, dst: View, stream=None):
-    """GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: the KV-cache write by slot
+    """GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL: the KV-cache write by slot
     index (include/fattn.h fattn_set_rows).  src: f32 ne = [ne0, nr, ne2, ne3];
     idx: TYPE_I64 or TYPE_I32 ne = [nr, ne11, ne12, 1] in device memory; dst: the
     cache, ne = [ne0, n_slots, ne2, ne3].  Row i of plane (i2, i3) is converted

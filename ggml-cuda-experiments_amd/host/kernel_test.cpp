@@ -19,7 +19,7 @@
 //   --n-warps N          accepted for compatibility (kernel_test.h:9-13); the gfx950
 //                        kernels pick their own wave counts
 //   --kv-size N          KV length, min 256 on the GPU path (kernel_test.h:14-18)
-//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0 | q4_1 | q5_0 | q5_1 | bf16
+//   --kv-type T          f16 (default, as the reference) | q8_0 | q4_0 | q4_1 | q5_0 | q5_1 | iq4_nl | bf16
 //                        (bf16: the cache written by fattn_cpy; the reference over the bf16-rounded
 //                        values, rounded on the host; not with --set-rows, which has no bf16 form)
 //   --cpu-only           the CPU reference alone (BASELINE config 1: no GPU is touched,
@@ -276,7 +276,8 @@ void cpu_reference(const std::vector<float>& q, const std::vector<float>& k, con
 
 const char* type_name(int t) {
     return t == FATTN_TYPE_Q8_0 ? "q8_0" : t == FATTN_TYPE_Q4_0 ? "q4_0" : t == FATTN_TYPE_Q4_1 ? "q4_1"
-           : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == FATTN_TYPE_BF16 ? "bf16" : "f16";
+           : t == FATTN_TYPE_Q5_0 ? "q5_0" : t == FATTN_TYPE_Q5_1 ? "q5_1" : t == FATTN_TYPE_IQ4_NL ? "iq4_nl"
+           : t == FATTN_TYPE_BF16 ? "bf16" : "f16";
 }
 
 // f32 -> the f32 value of its bf16 rounding (ggml_compute_fp32_to_bf16: NaN kept
@@ -290,12 +291,26 @@ float round_bf16(float f) {
     return f;
 }
 
-bool is_kv_ext(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1; }
+bool is_kv_ext(int t) { return t == FATTN_TYPE_Q4_1 || t == FATTN_TYPE_Q5_0 || t == FATTN_TYPE_Q5_1 || t == FATTN_TYPE_IQ4_NL; }
+
+// IQ4_NL: blocks {f16 d; u8 qs[16]}, x = kv[q] d
+const int kIq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+void dequant_host_iq4_nl(const uint8_t* src, float* dst, int64_t nblk) {
+    for (int64_t i = 0; i < nblk; i++) {
+        const uint8_t* b = src + i * 18;
+        const float d = h2f((uint16_t)(b[0] | (b[1] << 8)));
+        for (int j = 0; j < 16; j++) {
+            dst[i * 32 + j] = d * (float)kIq4nl[b[2 + j] & 0x0F];
+            dst[i * 32 + j + 16] = d * (float)kIq4nl[b[2 + j] >> 4];
+        }
+    }
+}
 
 // ggml's dequantize_row_q4_1 / _q5_0 / _q5_1 in plain C++ (this file builds with
 // -ffp-contract=off: every operation rounded on its own): `rows` rows of D values
 // from blocks {f16 d; [f16 m;] [u8 qh[4];] u8 qs[16]}
 void dequant_host(int type, const uint8_t* src, float* dst, int D, int64_t rows) {
+    if (type == FATTN_TYPE_IQ4_NL) return dequant_host_iq4_nl(src, dst, rows * (D / 32));
     const bool has_m = type != FATTN_TYPE_Q5_0, has_qh = type != FATTN_TYPE_Q4_1;
     const int bb = 2 + (has_m ? 2 : 0) + (has_qh ? 4 : 0) + 16;
     const int64_t nblk = rows * (D / 32);
@@ -334,6 +349,7 @@ int parse_type(const std::string& s) {
     if (s == "q4_1") return FATTN_TYPE_Q4_1;
     if (s == "q5_0") return FATTN_TYPE_Q5_0;
     if (s == "q5_1") return FATTN_TYPE_Q5_1;
+    if (s == "iq4_nl") return FATTN_TYPE_IQ4_NL;
     if (s == "bf16") return FATTN_TYPE_BF16;
     fprintf(stderr, "unknown --kv-type %s\n", s.c_str());
     exit(2);
@@ -604,9 +620,47 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     return worst_rel <= tol && lse_ok ? 0 : 1;
 }
 
+// ggml's cache write f32 -> iq4_nl in plain C++: the codes by the nearest codebook
+// entry to x / d0 (bisection, a tie going up), d0 = (first element of largest |x|) /
+// -127, then d refitted as sum(w v x) / sum(w v v), w = x x, over the pairs (j, j + 16)
+int iq4nl_best_index(float v) {
+    if (v <= -127.0f) return 0;
+    if (v >= 113.0f) return 15;
+    int ml = 0, mu = 15;
+    while (mu - ml > 1) {
+        const int mav = (ml + mu) / 2;
+        if (v < (float)kIq4nl[mav]) mu = mav;
+        else ml = mav;
+    }
+    return v - (float)kIq4nl[mu - 1] < (float)kIq4nl[mu] - v ? mu - 1 : mu;
+}
+void quant_host_iq4_nl(const float* src, uint8_t* dst, int64_t nblk) {
+    for (int64_t i = 0; i < nblk; i++) {
+        const float* x = src + i * 32;
+        uint8_t* b = dst + i * 18;
+        float amax = 0.0f, mx = 0.0f;
+        for (int j = 0; j < 32; j++)
+            if (amax < fabsf(x[j])) amax = fabsf(x[j]), mx = x[j];
+        const float d0 = mx / -127.0f;
+        const float id = d0 ? 1.0f / d0 : 0.0f;
+        float sumqx = 0.0f, sumq2 = 0.0f;
+        for (int j = 0; j < 16; j++) {
+            const int q0 = iq4nl_best_index(x[j] * id), q1 = iq4nl_best_index(x[j + 16] * id);
+            b[2 + j] = (uint8_t)(q0 | (q1 << 4));
+            const float v0 = (float)kIq4nl[q0], v1 = (float)kIq4nl[q1];
+            const float w0 = x[j] * x[j], w1 = x[j + 16] * x[j + 16];
+            sumqx += ((w0 * v0) * x[j]) + ((w1 * v1) * x[j + 16]);
+            sumq2 += ((w0 * v0) * v0) + ((w1 * v1) * v1);
+        }
+        const uint16_t dh = f2h(sumq2 > 0.0f ? sumqx / sumq2 : d0);
+        b[0] = (uint8_t)(dh & 0xFF), b[1] = (uint8_t)(dh >> 8);
+    }
+}
+
 // ggml's quantize_row_q4_1_ref / _q5_0_ref / _q5_1_ref in plain C++ (every
 // operation rounded on its own; the strict-compare scans keep the first of equals)
 void quant_host_ext(int type, const float* src, uint8_t* dst, int D, int64_t rows) {
+    if (type == FATTN_TYPE_IQ4_NL) return quant_host_iq4_nl(src, dst, rows * (D / 32));
     const bool has_m = type != FATTN_TYPE_Q5_0, has_qh = type != FATTN_TYPE_Q4_1;
     const int bb = 2 + (has_m ? 2 : 0) + (has_qh ? 4 : 0) + 16;
     for (int64_t i = 0; i < rows * (D / 32); i++) {

@@ -29,7 +29,7 @@
  *                           scratch exactly like d_temporal (kernel_test.h:155).
  *   fattn_workspace_size()  the size of that scratch (kernel_test.h:155 computes
  *                           it inline).
- *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / BF16 row conversion on the
+ *   fattn_dequantize() / fattn_quantize()   ggml Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL / BF16 row conversion on the
  *                           GPU (bit-exact with upstream ggml; absent from the
  *                           reference) -- the KV-cache write side.
  *   fattn_cpy() / fattn_set_rows()   the cache write itself: GGML_OP_CPY into a
@@ -72,6 +72,7 @@ enum fattn_type {
     FATTN_TYPE_Q5_0 = 6,
     FATTN_TYPE_Q5_1 = 7,
     FATTN_TYPE_Q8_0 = 8,
+    FATTN_TYPE_IQ4_NL = 20, /* {f16 d; u8 qs[16]} as Q4_0, the 4-bit code an index into a 16-entry non-linear codebook */
     FATTN_TYPE_I32 = 26,  /* index tensors of fattn_set_rows only: every other entry point rejects them */
     FATTN_TYPE_I64 = 27,
     FATTN_TYPE_BF16 = 30, /* 2 bytes per element; K / V of fattn_ext, dst of fattn_cpy (not of fattn_set_rows) */
@@ -81,7 +82,7 @@ enum fattn_status {
     FATTN_OK = 0,
     FATTN_ERR_INVALID_ARG = -1,     /* NULL pointer, bad shape, ne not divisible */
     FATTN_ERR_UNSUPPORTED_TYPE = -2,
-    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1 / BF16), 128 or 256 -- or the MLA pair, K 576 with V 512 (f16, Q8_0 or Q4_0) */
+    FATTN_ERR_UNSUPPORTED_HEAD_DIM = -3,  /* D must be 64, 80 (f16 K/V only), 96 (not Q4_1 / Q5_0 / Q5_1 / IQ4_NL / BF16), 128 or 256 -- or the MLA pair, K 576 with V 512 (f16, Q8_0 or Q4_0) */
     FATTN_ERR_BAD_STRIDE = -4,       /* layout the kernels cannot address */
     FATTN_ERR_WORKSPACE = -5,        /* workspace too small */
     FATTN_ERR_LAUNCH = -6,           /* HIP launch failure */
@@ -99,7 +100,7 @@ typedef struct fattn_tensor {
 
 /* GGML_OP_FLASH_ATTN_EXT:
  *   q    f32  ne = [D, n_q, H, S]        (any nb with nb[0] == 4)
- *   k    F16/BF16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
+ *   k    F16/BF16/Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL  ne = [D, N, Hkv, Skv]  rows contiguous (nb[0] = type size)
  *   v    the same types  ne = [D, N, Hkv, Skv]; rows contiguous, or for F16 only (not BF16)
  *        transposed (nb[1] == 2, nb[0] == N*2 style strides).  v's type may
  *        differ from k's (llama.cpp's separate K / V cache types) at D = 64,
@@ -113,6 +114,9 @@ typedef struct fattn_tensor {
  *        (FATTN_ERR_UNSUPPORTED_HEAD_DIM: Q5_0 rows would be 66 bytes, no whole
  *        number of dwords) and a pair that mixes one of them with any other
  *        type (FATTN_ERR_UNSUPPORTED_TYPE)
+ *        IQ4_NL (ggml type 20, --cache-type-k/-v iq4_nl: Q4_0's 18-byte block,
+ *        x = h(d) * kv[q] with kv the 16-entry codebook -127 .. 113): under the
+ *        rules of Q4_1 / Q5_0 / Q5_1 above, word for word
  *        BF16 (ggml type 30, llama.cpp's --cache-type-k/-v bf16: the cache of a
  *        bf16-trained model, whose K norms and outlier V channels pass f16's
  *        65504): K and V both BF16, at D = 64, 128 and 256, under the F16 row
@@ -398,9 +402,9 @@ int fattn_row(const float* query, const void* key, const void* value, const void
               int head_stride, int r_kv_heads, void* stream);
 
 /* ggml row conversions on the GPU (n_rows rows of k elements each, contiguous).
- * dequantize: Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/F16/BF16 -> f32 (bit-exact with ggml dequantize_row_*;
+ * dequantize: Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL/F16/BF16 -> f32 (bit-exact with ggml dequantize_row_*;
  *             BF16: exact, the bits shifted up by 16).
- * quantize:   f32 -> Q8_0/Q4_0/Q4_1/Q5_0/Q5_1 (bit-exact with ggml quantize_row_*_ref), or
+ * quantize:   f32 -> Q8_0/Q4_0/Q4_1/Q5_0/Q5_1/IQ4_NL (bit-exact with ggml quantize_row_*_ref), or
  *             f32 -> BF16 (any k >= 1, src 4-byte aligned): ggml_compute_fp32_to_bf16 bit for
  *             bit, in integer arithmetic -- with u the f32 bits, a NaN ((u & 0x7fffffff) >
  *             0x7f800000) gives (u >> 16) | 64 (kept, made quiet), anything else
@@ -409,7 +413,7 @@ int fattn_row(const float* query, const void* key, const void* value, const void
 int fattn_dequantize(int type, const void* src, float* dst, int64_t k, int64_t n_rows, void* stream);
 int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_rows, void* stream);
 
-/* GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 into a strided view: the KV-cache write
+/* GGML_OP_CPY f32 -> F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL into a strided view: the KV-cache write
  * (quantize-on-write; upstream ggml cpy_f32_q /
  * cpy_f32_f16, absent from the reference).  src: f32, nb[0] = 4; dst: same ne,
  * nb[0] = element / block bytes, any nb[1..3] -- e.g. one token's Hkv rows
@@ -419,7 +423,7 @@ int fattn_quantize(int type, const float* src, void* dst, int64_t k, int64_t n_r
  * quantize_row_*_ref / f16 round-to-nearest-even / the BF16 rule of fattn_quantize. */
 int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
 
-/* GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1: the KV-cache write by slot
+/* GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL: the KV-cache write by slot
  * index (upstream ggml_set_rows(a, b, c) with dst = a, src = b, idx = c; absent
  * from the reference).  The slots are data in device memory, not launch
  * arguments: one captured graph serves every decode step.  (No BF16 dst yet:
@@ -432,7 +436,7 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
  *        streams, or one per head / per stream.  Base and nb multiples of the
  *        element size, nb[0] >= the element size; nb[1] / nb[2] any non-negative
  *        multiples (0 repeats a row), looked at only where the count exceeds 1
- *   dst  F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1  ne = [ne0, n_slots, ne2, ne3]; nb[0] = element /
+ *   dst  F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL  ne = [ne0, n_slots, ne2, ne3]; nb[0] = element /
  *        block bytes, nb[1..3] and the base multiples of 2 as for fattn_cpy, so a
  *        [N][Hkv][row] and a [Hkv][N][row] cache are both expressible.  ne0 a
  *        multiple of 32 for the block types, any ne0 >= 1 for F16
@@ -462,7 +466,7 @@ int fattn_set_rows(const fattn_tensor* src, const fattn_tensor* idx, const fattn
  * once, dequantises it in registers, rotates it, requantises it and writes it
  * back: no f32 temporary.  Absent from the reference.  The deltas are data in
  * device memory, so one captured graph serves every shift.
- *   k      F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1  ne = [ne0, n_slots, Hkv, S],
+ *   k      F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL  ne = [ne0, n_slots, Hkv, S],
  *          oriented like fattn_set_rows' dst ([N][Hkv][row] and [Hkv][N][row]
  *          caches are both views); nb[0] = element / block bytes; base and
  *          nb[1..3] multiples of 2 (4 for F32).  ne0 <= 256, a multiple of 32 for
