@@ -1,7 +1,7 @@
 // fattn_k_shift.h -- the K-shift of llama.cpp's build_rope_shift: the RoPE
 // rotation of a K cache IN PLACE by a per-slot position delta, for an F32 / F16 /
-// BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 cache (include/fattn.h fattn_k_shift,
-// DESIGN.md §20).  One launch reads each cache block once, dequantises it into
+// BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL cache (include/fattn.h
+// fattn_k_shift).  One launch reads each cache block once, dequantises it into
 // registers, rotates it, requantises it with ggml's rules and writes it back:
 // no f32 temporary, no LDS memory.
 //
@@ -79,20 +79,18 @@ __device__ __forceinline__ void k_shift_rotate(float x0, float x1, float c, floa
 }
 
 // The load half: the lane's four dequantised elements 4l .. 4l+3 of the block at
-// blk, with the arithmetic of dequant_block<T>.  Blocks are only 2-byte aligned:
-// every access is a 16-bit load.
+// blk, each through block_value<T> as dequant_block<T>'s are.  Blocks are only
+// 2-byte aligned: every access is a 16-bit load.
 template <int T>
 __device__ __forceinline__ void k_shift_load_block(const uint8_t* blk, int l, float (&x)[4]) {
-#pragma clang fp contract(off)
     static_assert(is_quant(T), "");
     const uint16_t* h = (const uint16_t*)blk;
     const float d = (float)__builtin_bit_cast(f16, h[0]);
     if constexpr (T == FATTN_TYPE_Q8_0) {
         const uint32_t w = (uint32_t)h[1 + 2 * l] | ((uint32_t)h[2 + 2 * l] << 16);
 #pragma unroll
-        for (int k = 0; k < 4; k++) x[k] = (float)(int8_t)(w >> (8 * k)) * d;
+        for (int k = 0; k < 4; k++) x[k] = block_value<T>(w >> (8 * k), d, 0.0f);
     } else {
-        constexpr int zero = T == FATTN_TYPE_Q4_0 ? 8 : code_zero(T);
         // elements j and j + 16 share byte qs[j]: lanes l and l ^ 4 read the same four bytes
         const int o = qs_off(T) / 2 + 2 * (l & 3);
         const uint32_t w = (uint32_t)h[o] | ((uint32_t)h[o + 1] << 16);
@@ -105,10 +103,8 @@ __device__ __forceinline__ void k_shift_load_block(const uint8_t* blk, int l, fl
         if constexpr (is_codebook(T)) iq4nl_values4(nib, kv);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
-            const int q = (int)(((nib >> (8 * k)) & 0xFu) | (((hb >> k) & 1u) << 4));
-            if constexpr (is_codebook(T)) x[k] = d * kv[k];
-            else if constexpr (has_min(T)) x[k] = opaque((float)q * d) + m;
-            else x[k] = (float)(q - zero) * d;
+            if constexpr (is_codebook(T)) x[k] = block_value<T>(kv[k], d, m);
+            else x[k] = block_value<T>((int)(((nib >> (8 * k)) & 0xFu) | (((hb >> k) & 1u) << 4)), d, m);
         }
     }
 }

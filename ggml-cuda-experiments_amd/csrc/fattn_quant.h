@@ -6,14 +6,20 @@
 // oracle/fattn_oracle.c (Q4_1 / Q5_0 / Q5_1: quantize_row_q4_1_ref, _q5_0_ref,
 // _q5_1_ref and their dequantize_row_*, restated in tests/kv_types.py; IQ4_NL:
 // the cache-write quantiser and dequantize_row_iq4_nl, restated in
-// tests/iq4_nl.py), and are
-// bit-exact with that restatement: every
+// tests/iq4_nl.py).  They are bit-exact with those restatements: every
 // multiply/add is a separately rounded IEEE op (contraction off + barriers),
 // divisions are correctly rounded (hipcc default), f32->f16 is round-to-nearest-even.
 //
-// Layout: one thread per 32-element block; a wave covers 64 consecutive blocks,
-// so the block reads/writes of a wave are contiguous.  These are the
-// KV-cache write side (ggml cpy f32 -> q8_0/q4_0) and the dequant unit check.
+// Each type's rule is stated once, in the pieces below (scan_*, block_scale,
+// block_code, block_value, iq4nl_*).  A layout holds only what is about the
+// layout -- which elements a thread has, how partial statistics merge, how codes
+// pack into bytes: quant_block / dequant_block here, set_rows_block
+// (fattn_set_rows.h) and k_shift_load_block (fattn_k_shift.h).
+//
+// Layout of this file's kernels: one thread per 32-element block; a wave covers
+// 64 consecutive blocks, so the block reads/writes of a wave are contiguous.
+// These are the KV-cache write side (ggml cpy f32 -> a block type) and the
+// dequant unit check.
 #pragma once
 
 #include "fattn_common.h"
@@ -29,20 +35,121 @@ __device__ __forceinline__ float opaque(float x) {
     return x;
 }
 
-// One ggml block -> its 32 f32 values (dequantize_row_q8_0 / _q4_0 / _q4_1 / _q5_0 / _q5_1 / _iq4_nl)
+// f32 -> the bits of a block's f16 field d or m
+__device__ __forceinline__ uint32_t f16_bits(float x) { return __builtin_bit_cast(uint16_t, (f16)opaque(x)); }
+// ... and the low 16 bits of v into a block, little-endian, as the one-thread-per-block kernels store: by the byte
+__device__ __forceinline__ void store_u8x2(uint8_t* p, uint32_t v) {
+    p[0] = (uint8_t)v;
+    p[1] = (uint8_t)(v >> 8);
+}
+
+// ---- The rule of each block type (quantize_row_*_ref, dequantize_row_*), one step per function
+
+// The block statistics, scanned in element order over a whole block (N = 32) or
+// a lane's share of one (N = 4; fattn_set_rows.h merges the shares).
+// Q8_0: the largest |x|, by value -- no tie rule
+template <int N>
+__device__ __forceinline__ float scan_absmax(const float (&x)[N]) {
+    float amax = 0.0f;
+#pragma unroll
+    for (int j = 0; j < N; j++) amax = fmaxf(amax, fabsf(x[j]));
+    return amax;
+}
+// Q4_0 / Q5_0 / IQ4_NL: mx = the FIRST element of largest |x| (the strict compare
+// keeps the earlier of two equal ones; it gives d its sign); all zero: mx = +0
+template <int N>
+__device__ __forceinline__ void scan_amax(const float (&x)[N], float& amax, float& mx) {
+    amax = 0.0f, mx = 0.0f;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        if (amax < fabsf(x[j])) {
+            amax = fabsf(x[j]);
+            mx = x[j];
+        }
+    }
+}
+// Q4_1 / Q5_1: the first of the smallest and the first of the largest value (-0.0 == +0.0)
+template <int N>
+__device__ __forceinline__ void scan_minmax(const float (&x)[N], float& mn, float& mxv) {
+    mn = 3.402823466e+38f, mxv = -3.402823466e+38f;
+#pragma unroll
+    for (int j = 0; j < N; j++) {
+        if (x[j] < mn) mn = x[j];
+        if (x[j] > mxv) mxv = x[j];
+    }
+}
+
+// The scale from the block's statistics -- mx: what the type's scan gives (Q8_0
+// amax, Q4_1 / Q5_1 the maximum), mn: the minimum of Q4_1 / Q5_1 (its f16 bits are
+// the block's m) -- and its reciprocal for block_code.  f16_bits(d) is the
+// block's d; IQ4_NL: d is the scale its codes are chosen with, the one it stores
+// is refitted (iq4nl_scale_bits).
+struct BlockScale {
+    float d, id;
+};
+template <int T>
+__device__ __forceinline__ BlockScale block_scale(float mx, float mn) {
+#pragma clang fp contract(off)
+    static_assert(is_quant(T), "");
+    BlockScale s;
+    if constexpr (T == FATTN_TYPE_Q8_0) s.d = mx / 127.0f;
+    else if constexpr (T == FATTN_TYPE_Q4_0) s.d = mx * -0.125f;   // == mx / -8 exactly (power of two), keeps -0.0
+    else if constexpr (T == FATTN_TYPE_Q5_0) s.d = mx * -0.0625f;  // == mx / -16, likewise
+    else if constexpr (is_codebook(T)) s.d = mx / -127.0f;
+    else s.d = opaque(mx - mn) / (T == FATTN_TYPE_Q4_1 ? 15.0f : 31.0f);
+    s.id = s.d != 0.0f ? 1.0f / s.d : 0.0f;
+    return s;
+}
+
+// One element's code, 0 .. 255 (IQ4_NL: iq4nl_code).  Q4_0 / Q5_0: min(15 / 31,
+// x id + 8.5 / 16.5 truncated to int8); Q4_1: min(15, (x - mn) id + 0.5 truncated
+// to int8); Q5_1: the same truncated to uint8, no clamp.
+template <int T>
+__device__ __forceinline__ uint32_t block_code(float x, float id, float mn) {
+#pragma clang fp contract(off)
+    static_assert(is_quant(T) && !is_codebook(T), "");
+    if constexpr (T == FATTN_TYPE_Q8_0) {
+        return (uint8_t)(int8_t)roundf(x * id);
+    } else if constexpr (T == FATTN_TYPE_Q4_0) {
+        const int8_t t = (int8_t)(opaque(x * id) + 8.5f);
+        return (uint8_t)(t < 15 ? t : 15);
+    } else if constexpr (T == FATTN_TYPE_Q5_0) {
+        const int8_t t = (int8_t)(opaque(x * id) + 16.5f);
+        return (uint32_t)(t < 31 ? t : 31) & 0xFFu;
+    } else if constexpr (T == FATTN_TYPE_Q4_1) {
+        const int8_t t = (int8_t)(opaque(opaque(x - mn) * id) + 0.5f);
+        return (uint32_t)(t < 15 ? t : 15) & 0xFFu;
+    } else {
+        return (uint8_t)(opaque(opaque(x - mn) * id) + 0.5f);
+    }
+}
+
+// One element of dequantize_row_*: the code q (Q8_0: its byte; IQ4_NL: its
+// codebook entry, a float from iq4nl_values4), the block's d and m -> x
+template <int T, typename Q>
+__device__ __forceinline__ float block_value(Q q, float d, float m) {
+#pragma clang fp contract(off)
+    static_assert(is_quant(T), "");
+    constexpr int zero = T == FATTN_TYPE_Q4_0 ? 8 : code_zero(T);  // (Q4_0's 8: the kernels' nibble trick takes it, not code_zero)
+    if constexpr (is_codebook(T)) return d * q;
+    else if constexpr (T == FATTN_TYPE_Q8_0) return (float)(int8_t)q * d;
+    else if constexpr (has_min(T)) return opaque((float)q * d) + m;
+    else return (float)((int)q - zero) * d;
+}
+
+// One ggml block -> its 32 f32 values: a thread unpacks the codes byte by byte
 template <int T>
 __device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, float* __restrict__ y) {
-#pragma clang fp contract(off)
     static_assert(is_quant(T), "");
     const float d = (float)__builtin_bit_cast(f16, (uint16_t)(blk[0] | (blk[1] << 8)));
     if constexpr (T == FATTN_TYPE_Q8_0) {
 #pragma unroll
         for (int j = 0; j < QK; j += 4) {
             f32x4 v;
-            v.x = (float)(int8_t)blk[2 + j] * d;
-            v.y = (float)(int8_t)blk[3 + j] * d;
-            v.z = (float)(int8_t)blk[4 + j] * d;
-            v.w = (float)(int8_t)blk[5 + j] * d;
+            v.x = block_value<T>(blk[2 + j], d, 0.0f);
+            v.y = block_value<T>(blk[3 + j], d, 0.0f);
+            v.z = block_value<T>(blk[4 + j], d, 0.0f);
+            v.w = block_value<T>(blk[5 + j], d, 0.0f);
             *(f32x4*)(y + j) = v;
         }
     } else if constexpr (is_codebook(T)) {
@@ -55,12 +162,11 @@ __device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, f
             iq4nl_values4((w >> 4) & 0x0F0F0F0Fu, hi);
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                y[j + k] = d * lo[k];
-                y[j + k + QK / 2] = d * hi[k];
+                y[j + k] = block_value<T>(lo[k], d, 0.0f);
+                y[j + k + QK / 2] = block_value<T>(hi[k], d, 0.0f);
             }
         }
     } else {
-        constexpr int zero = T == FATTN_TYPE_Q4_0 ? 8 : code_zero(T);  // (Q4_0's 8: the kernels' nibble trick takes it, not code_zero)
         float m = 0.0f;
         if constexpr (has_min(T)) m = (float)__builtin_bit_cast(f16, (uint16_t)(blk[2] | (blk[3] << 8)));
         uint32_t qh = 0;
@@ -71,15 +177,8 @@ __device__ __forceinline__ void dequant_block(const uint8_t* __restrict__ blk, f
 #pragma unroll
         for (int j = 0; j < QK / 2; j++) {
             const int b = blk[qs_off(T) + j];
-            const int q0 = (b & 0x0F) | (int)(((qh >> j) & 1u) << 4);
-            const int q1 = (b >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4);
-            if constexpr (has_min(T)) {
-                y[j] = opaque((float)q0 * d) + m;
-                y[j + QK / 2] = opaque((float)q1 * d) + m;
-            } else {
-                y[j] = (float)(q0 - zero) * d;
-                y[j + QK / 2] = (float)(q1 - zero) * d;
-            }
+            y[j] = block_value<T>((b & 0x0F) | (int)(((qh >> j) & 1u) << 4), d, m);
+            y[j + QK / 2] = block_value<T>((b >> 4) | (int)(((qh >> (j + 16)) & 1u) << 4), d, m);
         }
     }
 }
@@ -121,115 +220,6 @@ __global__ __launch_bounds__(256) void quant_bf16_kernel(const float* __restrict
     dst[i] = f32_to_bf16_bits(src[i]);
 }
 
-// One ggml block of 32 values -> Q8_0 {f16 d; int8 qs[32]} (quantize_row_q8_0_ref)
-__device__ __forceinline__ void quant_block_q8_0(const float (&xv)[QK], uint8_t* blk) {
-#pragma clang fp contract(off)
-    float amax = 0.0f;
-#pragma unroll
-    for (int j = 0; j < QK; j++) amax = fmaxf(amax, fabsf(xv[j]));
-    const float d = amax / 127.0f;
-    const float id = d != 0.0f ? 1.0f / d : 0.0f;
-    const uint16_t dh = __builtin_bit_cast(uint16_t, (f16)opaque(d));
-    blk[0] = dh & 0xff;
-    blk[1] = dh >> 8;
-#pragma unroll
-    for (int j = 0; j < QK; j++) blk[2 + j] = (uint8_t)(int8_t)roundf(xv[j] * id);
-}
-
-// One ggml block of 32 values -> Q4_0 {f16 d; u8 qs[16]} (quantize_row_q4_0_ref)
-__device__ __forceinline__ void quant_block_q4_0(const float (&xv)[QK], uint8_t* blk) {
-#pragma clang fp contract(off)
-    float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-    for (int j = 0; j < QK; j++) {
-        if (amax < fabsf(xv[j])) {
-            amax = fabsf(xv[j]);
-            mx = xv[j];
-        }
-    }
-    const float d = mx * -0.125f;  // == mx / -8 exactly (power of two), keeps -0.0
-    const float id = d != 0.0f ? 1.0f / d : 0.0f;
-    const uint16_t dh = __builtin_bit_cast(uint16_t, (f16)opaque(d));
-    blk[0] = dh & 0xff;
-    blk[1] = dh >> 8;
-#pragma unroll
-    for (int j = 0; j < QK / 2; j++) {
-        const int8_t t0 = (int8_t)(opaque(xv[j] * id) + 8.5f);
-        const int8_t t1 = (int8_t)(opaque(xv[j + QK / 2] * id) + 8.5f);
-        const uint8_t q0 = (uint8_t)(t0 < 15 ? t0 : 15);
-        const uint8_t q1 = (uint8_t)(t1 < 15 ? t1 : 15);
-        blk[2 + j] = (uint8_t)(q0 | (q1 << 4));
-    }
-}
-
-// One ggml block of 32 values -> Q4_1 / Q5_0 / Q5_1 (quantize_row_q4_1_ref,
-// quantize_row_q5_0_ref, quantize_row_q5_1_ref).  Q4_1 / Q5_1: d = (max - min) /
-// 15 (31), q = (x - min) / d + 0.5 truncated (Q4_1 clamps at 15, Q5_1 does not);
-// Q5_0: d = (the first element of largest |x|) / -16, q = min(31, x / d + 16.5).
-// The low four bits go to qs (element j low nibble, j + 16 high), bit 4 to qh.
-template <int T>
-__device__ __forceinline__ void quant_block_ext(const float (&xv)[QK], uint8_t* blk) {
-#pragma clang fp contract(off)
-    static_assert(is_kv_ext(T) && !is_codebook(T), "");
-    float d, mn = 0.0f;
-    if constexpr (T == FATTN_TYPE_Q5_0) {
-        float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-        for (int j = 0; j < QK; j++) {
-            if (amax < fabsf(xv[j])) {
-                amax = fabsf(xv[j]);
-                mx = xv[j];
-            }
-        }
-        d = mx * -0.0625f;  // == mx / -16 exactly (power of two), keeps -0.0
-    } else {
-        float mxv = -3.402823466e+38f;
-        mn = 3.402823466e+38f;
-#pragma unroll
-        for (int j = 0; j < QK; j++) {
-            if (xv[j] < mn) mn = xv[j];
-            if (xv[j] > mxv) mxv = xv[j];
-        }
-        d = opaque(mxv - mn) / (T == FATTN_TYPE_Q4_1 ? 15.0f : 31.0f);
-        const uint16_t mh = __builtin_bit_cast(uint16_t, (f16)opaque(mn));
-        blk[2] = mh & 0xff;
-        blk[3] = mh >> 8;
-    }
-    const float id = d != 0.0f ? 1.0f / d : 0.0f;
-    const uint16_t dh = __builtin_bit_cast(uint16_t, (f16)opaque(d));
-    blk[0] = dh & 0xff;
-    blk[1] = dh >> 8;
-    uint32_t qh = 0;
-#pragma unroll
-    for (int j = 0; j < QK / 2; j++) {
-        uint32_t q0, q1;
-        if constexpr (T == FATTN_TYPE_Q5_0) {
-            const int8_t t0 = (int8_t)(opaque(xv[j] * id) + 16.5f);
-            const int8_t t1 = (int8_t)(opaque(xv[j + QK / 2] * id) + 16.5f);
-            q0 = (uint32_t)(t0 < 31 ? t0 : 31);
-            q1 = (uint32_t)(t1 < 31 ? t1 : 31);
-        } else if constexpr (T == FATTN_TYPE_Q4_1) {
-            const int8_t t0 = (int8_t)(opaque(opaque(xv[j] - mn) * id) + 0.5f);
-            const int8_t t1 = (int8_t)(opaque(opaque(xv[j + QK / 2] - mn) * id) + 0.5f);
-            q0 = (uint32_t)(t0 < 15 ? t0 : 15);
-            q1 = (uint32_t)(t1 < 15 ? t1 : 15);
-        } else {
-            q0 = (uint8_t)(opaque(opaque(xv[j] - mn) * id) + 0.5f);
-            q1 = (uint8_t)(opaque(opaque(xv[j + QK / 2] - mn) * id) + 0.5f);
-        }
-        blk[qs_off(T) + j] = (uint8_t)((q0 & 0x0F) | ((q1 & 0x0F) << 4));
-        qh |= ((q0 & 0x10u) >> 4) << j;
-        qh |= ((q1 & 0x10u) >> 4) << (j + QK / 2);
-    }
-    if constexpr (has_qh(T)) {
-        uint8_t* h = blk + qh_off(T);
-        h[0] = qh & 0xff;
-        h[1] = (qh >> 8) & 0xff;
-        h[2] = (qh >> 16) & 0xff;
-        h[3] = qh >> 24;
-    }
-}
-
 // IQ4_NL, ggml's cache write f32 -> iq4_nl.  iq4nl_code: best_index of v = x * id,
 // the codebook entry nearest to v with a tie going up.  ggml bisects the table
 // on `v < kv[mav]`; the interval that finds, kv[mu - 1] <= v < kv[mu], is the one
@@ -261,45 +251,56 @@ __device__ __forceinline__ void iq4nl_terms(float x, float v, float& qx, float& 
 }
 // ... and the stored scale from the sums (d0: the scale the codes were chosen with)
 __device__ __forceinline__ uint32_t iq4nl_scale_bits(float sumqx, float sumq2, float d0) {
-    const float d = sumq2 > 0.0f ? sumqx / sumq2 : d0;
-    return __builtin_bit_cast(uint16_t, (f16)opaque(d));
-}
-__device__ __forceinline__ void quant_block_iq4_nl(const float (&xv)[QK], uint8_t* blk) {
-#pragma clang fp contract(off)
-    float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-    for (int j = 0; j < QK; j++) {
-        if (amax < fabsf(xv[j])) {
-            amax = fabsf(xv[j]);
-            mx = xv[j];
-        }
-    }
-    const float d0 = mx / -127.0f;
-    const float id = d0 != 0.0f ? 1.0f / d0 : 0.0f;
-    float sumqx = 0.0f, sumq2 = 0.0f;
-#pragma unroll
-    for (int j = 0; j < QK / 2; j++) {
-        float v0, v1, a0, a1, b0, b1;
-        const uint32_t q0 = iq4nl_code(opaque(xv[j] * id), v0);
-        const uint32_t q1 = iq4nl_code(opaque(xv[j + QK / 2] * id), v1);
-        blk[2 + j] = (uint8_t)(q0 | (q1 << 4));
-        iq4nl_terms(xv[j], v0, a0, b0);
-        iq4nl_terms(xv[j + QK / 2], v1, a1, b1);
-        sumqx = opaque(sumqx + opaque(a0 + a1));
-        sumq2 = opaque(sumq2 + opaque(b0 + b1));
-    }
-    const uint32_t dh = iq4nl_scale_bits(sumqx, sumq2, d0);
-    blk[0] = dh & 0xff;
-    blk[1] = dh >> 8;
+    return f16_bits(sumq2 > 0.0f ? sumqx / sumq2 : d0);
 }
 
-// the block function of type T
+// One ggml block of 32 values -> its bytes: a thread scans all 32, then packs
+// element j with element j + 16 (low nibble, high nibble of qs[j]; the fifth
+// bits into bits j, j + 16 of qh); Q8_0: a byte per element
 template <int T>
 __device__ __forceinline__ void quant_block(const float (&xv)[QK], uint8_t* blk) {
-    if constexpr (T == FATTN_TYPE_Q8_0) quant_block_q8_0(xv, blk);
-    else if constexpr (T == FATTN_TYPE_Q4_0) quant_block_q4_0(xv, blk);
-    else if constexpr (is_codebook(T)) quant_block_iq4_nl(xv, blk);
-    else quant_block_ext<T>(xv, blk);
+#pragma clang fp contract(off)
+    [[maybe_unused]] float amax;
+    float mn = 0.0f, mx;
+    if constexpr (T == FATTN_TYPE_Q8_0) mx = scan_absmax(xv);
+    else if constexpr (has_min(T)) scan_minmax(xv, mn, mx);
+    else scan_amax(xv, amax, mx);
+    const BlockScale s = block_scale<T>(mx, mn);
+    if constexpr (has_min(T)) store_u8x2(blk + 2, f16_bits(mn));
+    if constexpr (T == FATTN_TYPE_Q8_0) {
+        store_u8x2(blk, f16_bits(s.d));
+#pragma unroll
+        for (int j = 0; j < QK; j++) blk[2 + j] = (uint8_t)block_code<T>(xv[j], s.id, mn);
+    } else if constexpr (is_codebook(T)) {
+        float sumqx = 0.0f, sumq2 = 0.0f;
+#pragma unroll
+        for (int j = 0; j < QK / 2; j++) {
+            float v0, v1, a0, a1, b0, b1;
+            const uint32_t q0 = iq4nl_code(opaque(xv[j] * s.id), v0);
+            const uint32_t q1 = iq4nl_code(opaque(xv[j + QK / 2] * s.id), v1);
+            blk[2 + j] = (uint8_t)(q0 | (q1 << 4));
+            iq4nl_terms(xv[j], v0, a0, b0);
+            iq4nl_terms(xv[j + QK / 2], v1, a1, b1);
+            sumqx = opaque(sumqx + opaque(a0 + a1));
+            sumq2 = opaque(sumq2 + opaque(b0 + b1));
+        }
+        store_u8x2(blk, iq4nl_scale_bits(sumqx, sumq2, s.d));
+    } else {
+        store_u8x2(blk, f16_bits(s.d));
+        uint32_t qh = 0;
+#pragma unroll
+        for (int j = 0; j < QK / 2; j++) {
+            const uint32_t q0 = block_code<T>(xv[j], s.id, mn), q1 = block_code<T>(xv[j + QK / 2], s.id, mn);
+            // (Q4_0 keeps the low code whole, as ggml's `q0 | (q1 << 4)` does)
+            blk[qs_off(T) + j] = (uint8_t)((T == FATTN_TYPE_Q4_0 ? q0 : q0 & 0x0F) | ((q1 & 0x0F) << 4));
+            qh |= ((q0 & 0x10u) >> 4) << j;
+            qh |= ((q1 & 0x10u) >> 4) << (j + QK / 2);
+        }
+        if constexpr (has_qh(T)) {
+            store_u8x2(blk + qh_off(T), qh);
+            store_u8x2(blk + qh_off(T) + 2, qh >> 16);
+        }
+    }
 }
 
 template <int T>

@@ -1,5 +1,5 @@
-// fattn_set_rows.h -- GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1:
-// the KV-cache write by slot index (include/fattn.h fattn_set_rows).
+// fattn_set_rows.h -- GGML_OP_SET_ROWS f32 -> F16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 /
+// IQ4_NL: the KV-cache write by slot index (include/fattn.h fattn_set_rows).
 //
 // Layout: EIGHT LANES PER 32-ELEMENT BLOCK.  Lane l of a group holds elements
 // 4l .. 4l+3, one 16-B load, so a wave's load instruction covers 1 KiB of
@@ -14,9 +14,9 @@
 // the sequential reference does, then a 3-step xor butterfly (DPP quad_perm for
 // xor 1 / 2, ds_swizzle for xor 4; no LDS memory) merges the eight partial
 // results.  The merges reproduce the reference's strict-compare scans bit for
-// bit -- see merge_amax / merge_min / merge_max.  The arithmetic after them is
-// that of quant_block_* (fattn_quant.h): contraction off, the same opaque()
-// barriers, the same truncations and clamps.
+// bit -- see merge_amax / merge_min / merge_max.  The scans themselves and the
+// arithmetic after the merges are fattn_quant.h's scan_* / block_scale /
+// block_code / iq4nl_*: the code the one-thread-per-block quant_block runs.
 //
 // Packing: element j shares a byte with j + 16, i.e. lane l with lane l + 4: one
 // exchange of the four packed codes.  qh is an OR-reduction of four bits per
@@ -101,56 +101,49 @@ __device__ __forceinline__ void merge_or(uint32_t& v) {
 __device__ __forceinline__ void store_u16(uint8_t* p, uint32_t v) { *(uint16_t*)p = (uint16_t)v; }
 
 // The lane's share of one block of type T: x = elements 4l .. 4l+3; `write`
-// guards every store (the cross-lane steps run regardless).
+// guards every store (the cross-lane steps run regardless).  The lane's scan,
+// the butterfly, then the type's rule from fattn_quant.h on the merged statistics.
 template <int T>
 __device__ __forceinline__ void set_rows_block(const float (&x)[4], int l, bool write, uint8_t* blk) {
 #pragma clang fp contract(off)
+    [[maybe_unused]] float amax;
+    float mn = 0.0f, mx;
     if constexpr (T == FATTN_TYPE_Q8_0) {
-        float amax = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) amax = fmaxf(amax, fabsf(x[k]));
-        amax = fmaxf(amax, xor_lane<1>(amax));  // by value: no tie rule
-        amax = fmaxf(amax, xor_lane<2>(amax));
-        amax = fmaxf(amax, xor_lane<4>(amax));
-        const float d = amax / 127.0f;
-        const float id = d != 0.0f ? 1.0f / d : 0.0f;
-        const uint32_t dh = __builtin_bit_cast(uint16_t, (f16)opaque(d));
-        uint32_t w = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) w |= (uint32_t)(uint8_t)(int8_t)roundf(x[k] * id) << (8 * k);
-        if (write) {
-            if (l == 0) store_u16(blk, dh);
-            store_u16(blk + 2 + 4 * l, w);
-            store_u16(blk + 4 + 4 * l, w >> 16);
-        }
-    } else if constexpr (is_codebook(T)) {
-        // IQ4_NL (quant_block_iq4_nl): the first-wins |max| scan as Q4_0's, each lane's
-        // four codes by the codebook search, then the refit's two 16-term chains.  Term
-        // j of a chain is element j's product plus element (j + 16)'s: lanes l and l ^ 4
-        // hold those two, so after one exchange both quads of the group hold all 16
-        // terms (the sum of two floats does not depend on their order), term 4i + k in
-        // lane i of each quad.  Every lane then walks the chain in order, 16 additions,
-        // each operand a quad_perm broadcast of lane i: no LDS, and all eight lanes end
-        // with the same two sums.
-        float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (amax < fabsf(x[k])) {
-                amax = fabsf(x[k]);
-                mx = x[k];
-            }
-        }
+        mx = scan_absmax(x);
+        mx = fmaxf(mx, xor_lane<1>(mx));  // by value: no tie rule
+        mx = fmaxf(mx, xor_lane<2>(mx));
+        mx = fmaxf(mx, xor_lane<4>(mx));
+    } else if constexpr (has_min(T)) {
+        scan_minmax(x, mn, mx);
+        merge_min<1>(mn, l);
+        merge_max<1>(mx, l);
+        merge_min<2>(mn, l);
+        merge_max<2>(mx, l);
+        merge_min<4>(mn, l);
+        merge_max<4>(mx, l);
+    } else {
+        scan_amax(x, amax, mx);
         merge_amax<1>(amax, mx, l);
         merge_amax<2>(amax, mx, l);
         merge_amax<4>(amax, mx, l);
-        const float d0 = mx / -127.0f;
-        const float id = d0 != 0.0f ? 1.0f / d0 : 0.0f;
-        uint32_t w = 0;  // the four codes, one per byte
+    }
+    const BlockScale s = block_scale<T>(mx, mn);
+    uint32_t dh = 0;
+    if constexpr (!is_codebook(T)) dh = f16_bits(s.d);
+    uint32_t w = 0;  // the four codes, one per byte
+    if constexpr (is_codebook(T)) {
+        // IQ4_NL: each lane's four codes by the codebook search, then the refit's two
+        // 16-term chains.  Term j of a chain is element j's product plus element
+        // (j + 16)'s: lanes l and l ^ 4 hold those two, so after one exchange both quads
+        // of the group hold all 16 terms (the sum of two floats does not depend on their
+        // order), term 4i + k in lane i of each quad.  Every lane then walks the chain
+        // in order, 16 additions, each operand a quad_perm broadcast of lane i: no LDS,
+        // and all eight lanes end with the same two sums.
         float tx[4], t2[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             float v, qx, q2;
-            w |= iq4nl_code(opaque(x[k] * id), v) << (8 * k);
+            w |= iq4nl_code(opaque(x[k] * s.id), v) << (8 * k);
             iq4nl_terms(x[k], v, qx, q2);
             tx[k] = opaque(qx + xor_lane<4>(qx));
             t2[k] = opaque(q2 + xor_lane<4>(q2));
@@ -164,69 +157,25 @@ __device__ __forceinline__ void set_rows_block(const float (&x)[4], int l, bool 
         for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0xAA>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0xAA>(t2[k]));
 #pragma unroll
         for (int k = 0; k < 4; k++) sumqx = opaque(sumqx + dpp_mov<0xFF>(tx[k])), sumq2 = opaque(sumq2 + dpp_mov<0xFF>(t2[k]));
-        const uint32_t dh = iq4nl_scale_bits(sumqx, sumq2, d0);
-        const uint32_t pw = xor_lane<4>(w);
-        const uint32_t qs = (l < 4 ? w : pw) | ((l < 4 ? pw : w) << 4);
+        dh = iq4nl_scale_bits(sumqx, sumq2, s.d);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) w |= block_code<T>(x[k], s.id, mn) << (8 * k);
+    }
+    if constexpr (T == FATTN_TYPE_Q8_0) {
         if (write) {
-            store_u16(blk + 2 + 4 * (l & 3) + (l < 4 ? 0 : 2), l < 4 ? qs : qs >> 16);
             if (l == 0) store_u16(blk, dh);
+            store_u16(blk + 2 + 4 * l, w);
+            store_u16(blk + 4 + 4 * l, w >> 16);
         }
     } else {
-        float d, mn = 0.0f;
-        if constexpr (!has_min(T)) {
-            float amax = 0.0f, mx = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (amax < fabsf(x[k])) {
-                    amax = fabsf(x[k]);
-                    mx = x[k];
-                }
-            }
-            merge_amax<1>(amax, mx, l);
-            merge_amax<2>(amax, mx, l);
-            merge_amax<4>(amax, mx, l);
-            d = mx * (T == FATTN_TYPE_Q4_0 ? -0.125f : -0.0625f);  // == mx / -8 (-16) exactly, keeps -0.0
-        } else {
-            float mxv = -3.402823466e+38f;
-            mn = 3.402823466e+38f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                if (x[k] < mn) mn = x[k];
-                if (x[k] > mxv) mxv = x[k];
-            }
-            merge_min<1>(mn, l);
-            merge_max<1>(mxv, l);
-            merge_min<2>(mn, l);
-            merge_max<2>(mxv, l);
-            merge_min<4>(mn, l);
-            merge_max<4>(mxv, l);
-            d = opaque(mxv - mn) / (T == FATTN_TYPE_Q4_1 ? 15.0f : 31.0f);
-        }
-        const float id = d != 0.0f ? 1.0f / d : 0.0f;
-        const uint32_t dh = __builtin_bit_cast(uint16_t, (f16)opaque(d));
-        uint32_t w = 0;  // the four codes, one per byte
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            uint32_t q;
-            if constexpr (T == FATTN_TYPE_Q4_0) {
-                const int8_t t = (int8_t)(opaque(x[k] * id) + 8.5f);
-                q = (uint8_t)(t < 15 ? t : 15);
-            } else if constexpr (T == FATTN_TYPE_Q5_0) {
-                const int8_t t = (int8_t)(opaque(x[k] * id) + 16.5f);
-                q = (uint32_t)(t < 31 ? t : 31) & 0xFFu;
-            } else if constexpr (T == FATTN_TYPE_Q4_1) {
-                const int8_t t = (int8_t)(opaque(opaque(x[k] - mn) * id) + 0.5f);
-                q = (uint32_t)(t < 15 ? t : 15) & 0xFFu;
-            } else {
-                q = (uint8_t)(opaque(opaque(x[k] - mn) * id) + 0.5f);
-            }
-            w |= q << (8 * k);
-        }
         // lanes l and l ^ 4 hold elements j and j + 16 of bytes qs[4(l&3) .. 4(l&3)+3]
         const uint32_t pw = xor_lane<4>(w);
         const uint32_t lo = l < 4 ? w : pw, hi = l < 4 ? pw : w;
-        // (Q4_0 keeps the low code whole, as quant_block_q4_0's `q0 | (q1 << 4)` does)
-        const uint32_t qs = (T == FATTN_TYPE_Q4_0 ? lo : lo & 0x0F0F0F0Fu) | ((hi & 0x0F0F0F0Fu) << 4);
+        // (Q4_0 keeps the low code whole, as ggml's `q0 | (q1 << 4)` does; IQ4_NL's codes have no fifth bit to drop)
+        constexpr uint32_t lo_mask = T == FATTN_TYPE_Q4_0 || is_codebook(T) ? ~0u : 0x0F0F0F0Fu;
+        constexpr uint32_t hi_mask = is_codebook(T) ? ~0u : 0x0F0F0F0Fu;
+        const uint32_t qs = (lo & lo_mask) | ((hi & hi_mask) << 4);
         uint32_t qh = 0;
         if constexpr (has_qh(T)) {
             // bit 4 of code k -> bit 4l + k
@@ -239,7 +188,7 @@ __device__ __forceinline__ void set_rows_block(const float (&x)[4], int l, bool 
             store_u16(blk + qs_off(T) + 4 * (l & 3) + (l < 4 ? 0 : 2), l < 4 ? qs : qs >> 16);
             if (l == 0) store_u16(blk, dh);
             if constexpr (has_min(T)) {
-                const uint32_t mh = __builtin_bit_cast(uint16_t, (f16)opaque(mn));
+                const uint32_t mh = f16_bits(mn);
                 if (l == 1) store_u16(blk + 2, mh);
             }
             if constexpr (has_qh(T)) {

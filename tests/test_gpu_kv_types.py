@@ -15,12 +15,14 @@ import pytest
 
 import bf16
 import fattn
+import iq4_nl as iq
 import kv_types as kt
 import mask_planes as mp
 import op_params as op
 import sinks as sk
 import views
 from gpu_util import graph_replay, run_described, run_kernel_test, upload, views as gpu_views
+from oracle import oracle as orc
 
 pytestmark = pytest.mark.gpu
 NAMES = ("q4_1", "q5_0", "q5_1")
@@ -86,6 +88,66 @@ def test_cpy_into_pos_cache_view(dev, name):
     want = cache0.copy().reshape(N, Hkv, rb)
     want[p0:p0 + ntok] = t.encode(cur)
     assert np.array_equal(cache.cpu().numpy().reshape(N, Hkv, rb), want)
+
+
+@functools.lru_cache(maxsize=None)
+def _writer_rows():
+    """f32 [26][96], three blocks a row: kv_types.edge_blocks(), then |max| ties of
+    opposite sign, each in both orders, at elements 0 / 1 (inside one lane of the
+    eight-lane layout), 1 / 6 (two lanes of a quad) and 15 / 16 (across the xor-4
+    exchange; edge_blocks() has 3 / 20, the same exchange), then 64 random blocks."""
+    rng = np.random.default_rng(97)
+    ties = []
+    for a, b in ((0, 1), (1, 6), (15, 16)):
+        for first in (-2.5, 2.5):
+            t = (0.25 * (1.0 - 2.0 * rng.random(32, dtype=np.float32))).astype(np.float32)
+            t[a], t[b] = np.float32(first), np.float32(-first)
+            ties.append(t)
+    rnd = (3.0 * (1.0 - 2.0 * rng.random((64, 32), dtype=np.float32))).astype(np.float32)
+    x = np.concatenate([kt.edge_blocks(), np.stack(ties), rnd]).reshape(26, 96)
+    x.setflags(write=False)
+    return x
+
+
+# (the type, the suite's encoder of f32 [..., ne0], its decoder of (row bytes, ne0))
+WRITERS = {"q8_0": (fattn.TYPE_Q8_0, lambda x: orc.quantize(x, fattn.TYPE_Q8_0), lambda r, k: orc.dequantize(r, fattn.TYPE_Q8_0, k)),
+           "q4_0": (fattn.TYPE_Q4_0, lambda x: orc.quantize(x, fattn.TYPE_Q4_0), lambda r, k: orc.dequantize(r, fattn.TYPE_Q4_0, k)),
+           **{n: (kt.TYPES[n], kt.KV_TYPES[n].encode, kt.KV_TYPES[n].decode) for n in NAMES},
+           "iq4_nl": (iq.TYPE_IQ4_NL, iq.quantize, iq.dequantize)}
+
+
+@pytest.mark.parametrize("name", list(WRITERS))
+def test_every_writer_same_bytes(dev, name):
+    """One rule per block type, whatever the layout that runs it: fattn_quantize and
+    fattn_cpy (a thread per block) and fattn_set_rows with slots arange (eight lanes
+    per block) write the same bytes, those of the suite's encoder, and
+    fattn_dequantize reads them back to the bits of the suite's decoder.  (The
+    eight-lane decoder is pinned by tests/test_gpu_k_shift.py's byte compares.)"""
+    import torch
+    typ, encode, decode = WRITERS[name]
+    x = _writer_rows()
+    nr, ne0 = x.shape
+    want = encode(x)
+    rb = want.shape[-1]
+    assert rb == fattn.row_size(typ, ne0)
+    src = torch.from_numpy(x.copy()).to(dev)
+    sv = fattn.View(src.data_ptr(), fattn.TYPE_F32, (ne0, nr, 1, 1), (4, ne0 * 4, nr * ne0 * 4, nr * ne0 * 4))
+    got = {"quantize": fattn.quantize(src, typ).cpu().numpy()}
+    idx = torch.arange(nr, dtype=torch.int64, device=dev)
+    for op_name in ("cpy", "set_rows"):
+        dst = torch.zeros(nr * rb, dtype=torch.uint8, device=dev)
+        dv = fattn.View(dst.data_ptr(), typ, (ne0, nr, 1, 1), (fattn.elem_bytes(typ), rb, nr * rb, nr * rb))
+        if op_name == "cpy":
+            fattn.cpy(sv, dv)
+        else:
+            fattn.set_rows(sv, fattn.View(idx.data_ptr(), fattn.TYPE_I64, (nr, 1, 1, 1), (8, 8 * nr, 8 * nr, 8 * nr)), dv)
+        torch.cuda.synchronize()
+        got[op_name] = dst.cpu().numpy().reshape(nr, rb)
+    for op_name, g in got.items():
+        bad = np.argwhere(g.reshape(nr, rb) != want)
+        assert len(bad) == 0, (name, op_name, bad[:8])
+    y = fattn.dequantize(torch.from_numpy(want).to(dev), typ, ne0).cpu().numpy()
+    assert np.array_equal(y.view(np.uint32), decode(want, ne0).view(np.uint32)), name
 
 
 # ------------------------------------------------------------------ attention: the split kernel
