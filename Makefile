@@ -13,9 +13,12 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-functi
 # The IQ4_NL kernels (new with the type, all in units of their own) are built without the
 # packed-f32 VALU forms v_pk_add / mul / fma_f32, which hipcc otherwise forms from adjacent
 # scalar f32 operations: new kernels for this target do not rely on them (DESIGN.md section
-# 22).  Every other unit, and so every other type's kernel, keeps the flags it had.
+# 22).  fattn_launch_rope_set_rows holds set_rows_block<IQ4_NL> among its run-time types and is
+# built the same way as a whole.  Every other unit, and so every other type's kernel, keeps the
+# flags it had.
 NOPK := -Xclang -target-feature -Xclang -packed-fp32-ops
-NOPK_UNITS := fattn_launch_iq4_nl_d64 fattn_launch_iq4_nl_d128 fattn_launch_iq4_nl_d256 fattn_launch_iq4_nl_conv
+NOPK_UNITS := fattn_launch_iq4_nl_d64 fattn_launch_iq4_nl_d128 fattn_launch_iq4_nl_d256 fattn_launch_iq4_nl_conv \
+              fattn_launch_rope_set_rows
 unit_flags = $(HIPFLAGS) $(if $(filter $(1),$(NOPK_UNITS)),$(NOPK))
 CSRC := $(wildcard $(PKG)/csrc/*.hip)
 CHDR := $(wildcard $(PKG)/csrc/*.h) include/fattn.h include/fattn_debug.h

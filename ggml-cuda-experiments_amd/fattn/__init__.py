@@ -24,7 +24,7 @@ TYPE_F32, TYPE_F16, TYPE_Q4_0, TYPE_Q8_0 = 0, 1, 2, 8
 TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1 = 3, 6, 7
 TYPE_IQ4_NL = 20
 TYPE_I32, TYPE_I64 = 26, 27   # index tensors of set_rows only
-TYPE_BF16 = 30                # 2-byte elements: K / V of flash_attn_ext, dst of cpy / quantize (not of set_rows)
+TYPE_BF16 = 30                # 2-byte elements: K / V of flash_attn_ext, dst of cpy / quantize / rope_set_rows (not of set_rows)
 TYPE_NAMES = {"f32": TYPE_F32, "f16": TYPE_F16, "q4_0": TYPE_Q4_0, "q8_0": TYPE_Q8_0,
               "q4_1": TYPE_Q4_1, "q5_0": TYPE_Q5_0, "q5_1": TYPE_Q5_1, "iq4_nl": TYPE_IQ4_NL, "bf16": TYPE_BF16}
 BLOCK_TYPES = (TYPE_Q8_0, TYPE_Q4_0, TYPE_Q4_1, TYPE_Q5_0, TYPE_Q5_1, TYPE_IQ4_NL)
@@ -40,7 +40,7 @@ EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
     "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows", "fattn_ext_lse", "fattn_lse_merge",
-    "fattn_k_shift",
+    "fattn_k_shift", "fattn_rope_set_rows",
 )
 ROPE_NORMAL, ROPE_NEOX = 0, 2   # fattn_rope.mode: ggml's GGML_ROPE_TYPE_NORMAL / GGML_ROPE_TYPE_NEOX
 OPT_MQ_ROWS_PER_WAVE = 1
@@ -165,6 +165,8 @@ def lib() -> C.CDLL:
         L.fattn_set_rows.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp]
         L.fattn_k_shift.restype = C.c_int
         L.fattn_k_shift.argtypes = [C.POINTER(FattnTensor), C.POINTER(FattnTensor), vp, C.POINTER(FattnRope), vp]
+        L.fattn_rope_set_rows.restype = C.c_int
+        L.fattn_rope_set_rows.argtypes = [C.POINTER(FattnTensor)] * 4 + [vp, C.POINTER(FattnRope)] + [C.POINTER(FattnTensor)] * 2 + [vp]
         L.fattn_describe.restype = C.c_int
         L.fattn_describe.argtypes = [C.POINTER(FattnParams), C.c_char_p, sz]
         _lib = L
@@ -557,6 +559,19 @@ def set_rows(src: View, idx: View, dst: View, stream=None):
     _check(lib().fattn_set_rows(C.byref(s), C.byref(i), C.byref(d), _stream(stream)), "fattn_set_rows")
 
 
+def _ff_ptr(freq_factors, rope: FattnRope, what: str):
+    """freq_factors: None, a raw device pointer (taken on trust), or a contiguous
+    float32 device tensor of exactly rope.n_dims / 2 values."""
+    if freq_factors is None or isinstance(freq_factors, int):
+        return freq_factors
+    import torch
+    if freq_factors.dtype != torch.float32 or not freq_factors.is_contiguous() or not freq_factors.is_cuda:
+        raise ValueError(f"{what}: freq_factors must be a contiguous float32 device tensor")
+    if freq_factors.numel() != int(rope.n_dims) // 2:
+        raise ValueError(f"{what}: {freq_factors.numel()} freq_factors for n_dims / 2 = {int(rope.n_dims) // 2} pairs")
+    return _tptr(freq_factors)
+
+
 def k_shift(k: View, shift: View, rope: FattnRope, freq_factors=None, stream=None):
     """The K-shift (include/fattn.h fattn_k_shift): rotate the K cache view k, ne =
     [ne0 <= 256, n_slots, Hkv, S] of any row type, IN PLACE by the RoPE of the
@@ -566,16 +581,28 @@ def k_shift(k: View, shift: View, rope: FattnRope, freq_factors=None, stream=Non
     tensor of exactly rope.n_dims / 2 values.  Rows whose delta is 0 and blocks at
     or past n_dims keep their bytes.  The deltas are read on the device, so a
     captured graph replays with whatever the shift tensor then holds."""
-    fptr = freq_factors
-    if freq_factors is not None and not isinstance(freq_factors, int):
-        import torch
-        if freq_factors.dtype != torch.float32 or not freq_factors.is_contiguous() or not freq_factors.is_cuda:
-            raise ValueError("k_shift: freq_factors must be a contiguous float32 device tensor")
-        if freq_factors.numel() != int(rope.n_dims) // 2:
-            raise ValueError(f"k_shift: {freq_factors.numel()} freq_factors for n_dims / 2 = {int(rope.n_dims) // 2} pairs")
-        fptr = _tptr(freq_factors)
+    fptr = _ff_ptr(freq_factors, rope, "k_shift")
     kc, sc = k.c(), shift.c()
     _check(lib().fattn_k_shift(C.byref(kc), C.byref(sc), fptr, C.byref(rope), _stream(stream)), "fattn_k_shift")
+
+
+def rope_set_rows(k_src: View, pos: Optional[View], idx: View, k_dst: View, rope: Optional[FattnRope], freq_factors=None,
+                  v_src: Optional[View] = None, v_dst: Optional[View] = None, stream=None):
+    """The write side of a decode step in one launch (include/fattn.h
+    fattn_rope_set_rows): k_src f32 [ne0 <= 256, nr, Hkv, S] is rotated by the RoPE
+    of the absolute positions pos (TYPE_I32, ne = [nr, np, 1, 1]; sequence i3 reads
+    plane i3 % np), converted and scattered into the slots idx names of k_dst --
+    F32 / F16 / BF16 or a block type -- and v_src likewise into v_dst without a
+    rotation (both None: K only).  idx is set_rows' index tensor, shared by K and V;
+    a slot out of range writes nothing.  rope: a FattnRope, or None for no rotation
+    (then pos is ignored and may be None: set_rows with BF16 / F32 dst and K and V
+    in one launch).  freq_factors as for k_shift.  Positions and slots are read on
+    the device, so a captured graph replays with what the tensors then hold."""
+    fptr = None if rope is None else _ff_ptr(freq_factors, rope, "rope_set_rows")
+    ts = [None if v is None else v.c() for v in (k_src, pos, idx, k_dst, v_src, v_dst)]
+    ks, ps, ix, kd, vs, vd = (None if t is None else C.byref(t) for t in ts)
+    _check(lib().fattn_rope_set_rows(ks, ps, ix, kd, fptr, None if rope is None else C.byref(rope), vs, vd, _stream(stream)),
+           "fattn_rope_set_rows")
 
 
 def dequantize(blocks, typ: int, k: int, stream=None):

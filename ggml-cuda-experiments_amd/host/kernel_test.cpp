@@ -71,6 +71,13 @@
 //                        --heads / --kv-heads / --kv-size / --head-dim (a multiple of 32, <= 256) / --mask /
 //                        --iters / --tol / --cpu-only apply.  Prints how many cache bytes differ from the
 //                        host's shift (sinf / cosf ulps may flip a code) and the verification line
+//   --rope-set-rows [--rope-mode norm|neox]   the write side of a decode step (fattn_rope_set_rows): f32
+//                        k_cur / v_cur of --kv-size tokens, token n at position n and bound for slot n, go
+//                        through ONE launch that rotates K, converts both to --kv-type and scatters them
+//                        into [Hkv][N][row] caches; the host does the same in plain C++ (rotate, encode) and
+//                        the CPU reference attends over that cache; one query row; the flags of --k-shift
+//                        apply.  Prints how many K / V cache bytes differ from the host's write and the
+//                        verification line
 //   --ngpu G             head-shard over G GPUs of this host (kv heads Hkv/G and their q
 //                        heads per device, fattn_ext on each, one RCCL all-gather of the
 //                        outputs, permuted into the ggml dst layout): BASELINE config 5's
@@ -904,9 +911,164 @@ int run_k_shift(int delta, bool neox, int D, int H, int Hkv, int N, int kv_type,
     return worst_rel <= tol ? 0 : 1;
 }
 
+// the --rope-set-rows flow: inputs from rand() in the order Q, K, V, mask; k_cur /
+// v_cur are the f32 [Hkv][N][D] arrays, token n at position n and bound for slot
+// n.  ONE fattn_rope_set_rows rotates K, converts both and scatters them into
+// [Hkv][N][row] caches of --kv-type that held 0xA5 bytes; the host does the same
+// (rope_row_host, encode) and the CPU reference attends over THAT cache;
+// fattn_ext attends over the GPU's.  --cpu-only: the host's side alone.
+int run_rope_set_rows(bool neox, int D, int H, int Hkv, int N, int kv_type, const std::string& mask_kind, bool cpu_only, int iters,
+                      float tol) {
+    const size_t rb = fattn_row_size(kv_type, D);
+    if (H <= 0 || Hkv <= 0 || N <= 0 || H % Hkv || rb == 0 || D % 32 || D > 256 || D < 32) {
+        fprintf(stderr, "--rope-set-rows: heads a positive multiple of kv-heads, head-dim a multiple of 32 up to 256\n");
+        return 2;
+    }
+    const float scale = 1.0f / sqrtf((float)D);
+    std::vector<float> query((size_t)D * H), key((size_t)D * N * Hkv), value((size_t)D * N * Hkv), mask((size_t)N);
+    random_fill(query);
+    random_fill(key);
+    random_fill(value);
+    random_fill(mask);
+    if (mask_kind != "random") std::fill(mask.begin(), mask.end(), 0.0f);
+    const int64_t nrows = (int64_t)N * Hkv;
+    // the host's write: rotate row (h, n) by n, encode; the reference reads what the cache then holds
+    std::vector<float> kref(key), vref(value.size());
+    for (int64_t r = 0; r < nrows; r++) rope_row_host(&kref[(size_t)r * D], D, (int)(r % N), neox);
+    std::vector<uint8_t> kbytes(rb * nrows), vbytes(rb * nrows);
+    encode_host(kv_type, kref.data(), kbytes.data(), D, nrows);
+    encode_host(kv_type, value.data(), vbytes.data(), D, nrows);
+    decode_host(kv_type, kbytes.data(), kref.data(), D, nrows);
+    decode_host(kv_type, vbytes.data(), vref.data(), D, nrows);
+    const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
+    std::vector<float> ref((size_t)D * H), got(ref.size());
+    cpu_reference(query, kref, vref, mask, ref, N, D, H, Hkv, scale, {0}, threads);
+    printf("rope-set-rows: %d tokens x %d heads of %d into %s caches [%d][%d][%d], rope mode %s\n", N, Hkv, D, type_name(kv_type),
+           Hkv, N, D, neox ? "neox" : "norm");
+    print_array("Reference", ref.data(), std::min(16, D * H));
+    if (cpu_only) return 0;
+
+    const bool has_mask = mask_kind != "none";
+    const int Np = N + (N & 1);
+    std::vector<uint16_t> mask16((size_t)Np * 32, f2h(0.0f));
+    for (int i = 0; i < N; i++) mask16[i] = f2h(mask[i]);
+    std::vector<int32_t> pos(N);
+    std::vector<int64_t> slots(N);
+    for (int i = 0; i < N; i++) pos[i] = i, slots[i] = i;
+    hipStream_t st;
+    HIP_CHECK(hipStreamCreate(&st));
+    float *d_q, *d_out, *d_ksrc, *d_vsrc;
+    void *d_k, *d_v, *d_mask, *d_ws, *d_pos, *d_idx;
+    HIP_CHECK(hipMalloc(&d_q, 4 * query.size()));
+    HIP_CHECK(hipMalloc(&d_out, 4 * got.size()));
+    HIP_CHECK(hipMalloc(&d_ksrc, 4 * key.size()));
+    HIP_CHECK(hipMalloc(&d_vsrc, 4 * value.size()));
+    HIP_CHECK(hipMalloc(&d_k, kbytes.size()));
+    HIP_CHECK(hipMalloc(&d_v, vbytes.size()));
+    HIP_CHECK(hipMalloc(&d_mask, 2 * mask16.size()));
+    HIP_CHECK(hipMalloc(&d_pos, 4 * pos.size()));
+    HIP_CHECK(hipMalloc(&d_idx, 8 * slots.size()));
+    const std::vector<uint8_t> stale(kbytes.size(), 0xA5);
+    HIP_CHECK(hipMemcpyAsync(d_q, query.data(), 4 * query.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_ksrc, key.data(), 4 * key.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_vsrc, value.data(), 4 * value.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_k, stale.data(), stale.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_v, stale.data(), stale.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_mask, mask16.data(), 2 * mask16.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_pos, pos.data(), 4 * pos.size(), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(d_idx, slots.data(), 8 * slots.size(), hipMemcpyHostToDevice, st));
+    const int64_t eb = kv_type == FATTN_TYPE_F16 || kv_type == FATTN_TYPE_BF16 ? 2 : (int64_t)fattn_row_size(kv_type, 32);
+    const int64_t sb = (int64_t)D * 4;
+    const fattn_tensor tks = {d_ksrc, FATTN_TYPE_F32, 0, {D, N, Hkv, 1}, {4, sb, sb * N, sb * N * Hkv}};
+    const fattn_tensor tvs = {d_vsrc, FATTN_TYPE_F32, 0, {D, N, Hkv, 1}, {4, sb, sb * N, sb * N * Hkv}};
+    const fattn_tensor tk = {d_k, kv_type, 0, {D, N, Hkv, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+    const fattn_tensor tv = {d_v, kv_type, 0, {D, N, Hkv, 1}, {eb, (int64_t)rb, (int64_t)rb * N, (int64_t)rb * N * Hkv}};
+    const fattn_tensor tp = {d_pos, FATTN_TYPE_I32, 0, {N, 1, 1, 1}, {4, 4 * (int64_t)N, 4 * (int64_t)N, 4 * (int64_t)N}};
+    const fattn_tensor ti = {d_idx, FATTN_TYPE_I64, 0, {N, 1, 1, 1}, {8, 8 * (int64_t)N, 8 * (int64_t)N, 8 * (int64_t)N}};
+    const fattn_rope rope = {D, neox ? 2 : 0, 0, 10000.0f, 1.0f, 0.0f, 1.0f, 32.0f, 1.0f};
+    hipEvent_t start, stop;
+    HIP_CHECK(hipEventCreate(&start));
+    HIP_CHECK(hipEventCreate(&stop));
+    HIP_CHECK(hipEventRecord(start, st));
+    int rc = fattn_rope_set_rows(&tks, &tp, &ti, &tk, nullptr, &rope, &tvs, &tv, st);
+    HIP_CHECK(hipEventRecord(stop, st));
+    if (rc) {
+        fprintf(stderr, "rope_set_rows failed: %s\n", fattn_strerror(rc));
+        return 2;
+    }
+    HIP_CHECK(hipEventSynchronize(stop));
+    float write_ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&write_ms, start, stop));
+    std::vector<uint8_t> kgot(kbytes.size()), vgot(vbytes.size());
+    HIP_CHECK(hipMemcpy(kgot.data(), d_k, kgot.size(), hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(vgot.data(), d_v, vgot.size(), hipMemcpyDeviceToHost));
+    int64_t kdiffer = 0, vdiffer = 0;
+    for (size_t i = 0; i < kgot.size(); i++) kdiffer += kgot[i] != kbytes[i], vdiffer += vgot[i] != vbytes[i];
+    std::vector<float> kdev(key.size());
+    decode_host(kv_type, kgot.data(), kdev.data(), D, nrows);
+    float max_dx = 0.0f, max_x = 0.0f;
+    for (size_t i = 0; i < kdev.size(); i++) {
+        const float dd = fabsf(kdev[i] - kref[i]);
+        max_dx = std::isnan(dd) ? INFINITY : std::max(max_dx, dd);
+        max_x = std::max(max_x, fabsf(kref[i]));
+    }
+    printf("rope-set-rows: one launch %.4f ms (first call); %lld of %zu K bytes and %lld V bytes differ from the host's write, max |dk| %.3g of max |k| %.3g\n",
+           write_ms, (long long)kdiffer, kgot.size(), (long long)vdiffer, max_dx, max_x);
+
+    fattn_params p;
+    std::memset(&p, 0, sizeof(p));
+    p.q = {d_q, FATTN_TYPE_F32, 0, {D, 1, H, 1}, {4, (int64_t)H * D * 4, (int64_t)D * 4, (int64_t)H * D * 4}};
+    p.k = tk;
+    p.v = tv;
+    if (has_mask) p.mask = {d_mask, FATTN_TYPE_F16, 0, {Np, 32, 1, 1}, {2, (int64_t)Np * 2, (int64_t)Np * 64, (int64_t)Np * 64}};
+    p.dst = d_out;
+    p.scale = scale;
+    const size_t ws_bytes = std::max<size_t>(fattn_workspace_size(&p), 16);
+    HIP_CHECK(hipMalloc(&d_ws, ws_bytes));
+    rc = fattn_workspace_init(d_ws, ws_bytes, st);
+    p.workspace = d_ws;
+    p.workspace_bytes = ws_bytes;
+    std::vector<float> times;
+    for (int it = 0; it < iters && !rc; it++) {
+        HIP_CHECK(hipEventRecord(start, st));
+        rc = fattn_ext(&p, st);
+        HIP_CHECK(hipEventRecord(stop, st));
+        HIP_CHECK(hipEventSynchronize(stop));
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, start, stop));
+        times.push_back(ms);
+    }
+    if (rc) {
+        fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
+        return 2;
+    }
+    std::sort(times.begin(), times.end());
+    HIP_CHECK(hipMemcpy(got.data(), d_out, 4 * got.size(), hipMemcpyDeviceToHost));
+    print_array("Rope-set-rows HIP", got.data(), std::min(16, D * H));
+    float max_diff = 0.0f, max_ref = 0.0f;
+    int head_idx = 0, dim_idx = 0;
+    for (int h = 0; h < H; h++)
+        for (int i = 0; i < D; i++) {
+            const float dd = fabsf(ref[(size_t)h * D + i] - got[(size_t)h * D + i]);
+            max_ref = std::max(max_ref, fabsf(ref[(size_t)h * D + i]));
+            if (dd > max_diff || std::isnan(dd)) {
+                max_diff = std::isnan(dd) ? INFINITY : dd;
+                head_idx = h, dim_idx = i;
+            }
+        }
+    const float worst_rel = max_diff / std::max(max_ref, 1e-30f);
+    printf("\ncuda time: %.4f ms  (attention over the written caches; median of %d)\n", times[times.size() / 2], iters);
+    const size_t at = (size_t)head_idx * D + dim_idx;
+    printf("R (%.4f) CUDA(%.4f) diff: %.4f - row = 0, head = %d, dim = %d\n", ref[at], got[at], max_diff, head_idx, dim_idx);
+    printf("checked 1 of 1 query rows x %d heads; n_q 1, 1 GPU(s)\n", H);
+    const bool ok = worst_rel <= tol;
+    printf("normwise rel err %.3g (tol %.1g): %s\n", worst_rel, tol, ok ? "PASS" : "FAIL");
+    return ok ? 0 : 1;
+}
+
 }  // namespace
 
-#define RCCL_CHECK(x)                                                                           \
+#define RCCL_CHECK(x)                                                                          \
     do {                                                                                          \
         ncclResult_t r_ = (x);                                                                    \
         if (r_ != ncclSuccess) {                                                                  \
@@ -924,7 +1086,7 @@ int main(int argc, const char* argv[]) {
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
     bool use_sinks = false, set_rows = false, mla = false, heads_given = false;
     int mla_v_off = 0, k_shift_delta = 0;
-    bool k_shift = false, rope_neox = true;
+    bool k_shift = false, rope_neox = true, rope_set_rows = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         auto next = [&]() -> const char* {
@@ -956,6 +1118,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--lse") use_lse = true;
         else if (a == "--v-off") mla_v_off = atoi(next());
         else if (a == "--k-shift") k_shift = true, k_shift_delta = atoi(next());
+        else if (a == "--rope-set-rows") rope_set_rows = true;
         else if (a == "--rope-mode") {
             const std::string m = next();
             if (m != "norm" && m != "neox") {
@@ -1001,6 +1164,8 @@ int main(int argc, const char* argv[]) {
     if (!cpu_only) kv_size = std::max(256, kv_size);      // kernel_test.h:14-18
     if (k_shift)
         return run_k_shift(k_shift_delta, rope_neox, head_dim, num_heads, num_kv_heads, kv_size, kv_type, mask_kind, cpu_only, iters, tol);
+    if (rope_set_rows)
+        return run_rope_set_rows(rope_neox, head_dim, num_heads, num_kv_heads, kv_size, kv_type, mask_kind, cpu_only, iters, tol);
     // (the model family's smallest head count unless --heads says otherwise)
     if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump, use_lse);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device

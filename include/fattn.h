@@ -39,6 +39,9 @@
  *   fattn_k_shift()      the last node of the cache's life cycle: llama.cpp's K-shift
  *                           (build_rope_shift), the RoPE rotation of a cache of any type in
  *                           place by per-slot position deltas, one launch; absent from the reference.
+ *   fattn_rope_set_rows()   the write side of a decode step: ggml_rope_ext + ggml_set_rows for
+ *                           K and ggml_set_rows for V, one launch, no f32 temporary; absent from
+ *                           the reference.
  *
  * Conventions:
  *   - every pointer is a device pointer the caller allocated; the library never
@@ -427,7 +430,8 @@ int fattn_cpy(const fattn_tensor* src, const fattn_tensor* dst, void* stream);
  * index (upstream ggml_set_rows(a, b, c) with dst = a, src = b, idx = c; absent
  * from the reference).  The slots are data in device memory, not launch
  * arguments: one captured graph serves every decode step.  (No BF16 dst yet:
- * FATTN_ERR_UNSUPPORTED_TYPE; a BF16 cache is written with fattn_cpy.)
+ * FATTN_ERR_UNSUPPORTED_TYPE; a BF16 cache is written with fattn_cpy, or by
+ * slot index with fattn_rope_set_rows, rope = NULL, below.)
  *   src  F32  ne = [ne0, nr, ne2, ne3]; nb[0] == 4, nb[1..3] any multiples of 4,
  *        4-byte aligned base (a 16-byte aligned base with nb[1..3] multiples of
  *        16 reads 16 B per lane, anything else 4 B at a time: same bytes written)
@@ -528,6 +532,64 @@ typedef struct fattn_rope {
 } fattn_rope;
 int fattn_k_shift(const fattn_tensor* k, const fattn_tensor* shift, const float* freq_factors,
                   const fattn_rope* rope, void* stream);
+
+/* THE WRITE SIDE OF A DECODE STEP IN ONE LAUNCH: ggml_rope_ext + ggml_set_rows for
+ * K and ggml_set_rows for V --
+ *     k_cur (f32) -> rope -> set_rows(K cache)      v_cur (f32) -> set_rows(V cache)
+ * (upstream ggml's CUDA backend fuses ROPE -> VIEW -> SET_ROWS the same way; absent
+ * from the reference).  K is rotated in registers and requantised with ggml's
+ * rules; no f32 row is written.  Positions and slots are data in device memory, so
+ * one captured graph serves every step.
+ *   k_src  F32  ne = [ne0, nr, ne2, ne3] under fattn_set_rows' src rules: nb[0] == 4,
+ *          nb[1..3] any multiples of 4, 4-byte aligned base -- llama.cpp's
+ *          [D][Hkv][n_tokens] k_cur is the view nb[1] = Hkv*D*4, nb[2] = D*4.  A
+ *          16-byte aligned base with nb[1..3] multiples of 16 (of K and of V) reads
+ *          16 B per lane, anything else 4 B at a time: same bytes written
+ *   idx    I64 or I32  ne = [nr, ne11, ne12, 1]: fattn_set_rows' index tensor and
+ *          broadcast (ne2 % ne11 == 0, ne3 % ne12 == 0), read at full width.  AN
+ *          OUT-OF-RANGE SLOT WRITES NOTHING, in K and in V; the call still returns 0
+ *   k_dst  F32 / F16 / BF16 / Q8_0 / Q4_0 / Q4_1 / Q5_0 / Q5_1 / IQ4_NL
+ *          ne = [ne0, n_slots, ne2, ne3]; strides and alignment as fattn_set_rows'
+ *          dst (multiples of 2; 4 for F32).  BF16 by the rule of fattn_quantize; F32
+ *          stores y itself
+ *   pos    I32  ne = [nr, np, 1, 1] with ne3 % np == 0: row (i, i2, i3) rotates by
+ *          p = pos[i, i3 % np] -- ggml's absolute positions; heads never index it.
+ *          Base and strides multiples of 4, nb[0] >= 4, nb[1] non-negative (looked
+ *          at only when np > 1)
+ *   rope, freq_factors  exactly as fattn_k_shift reads them: modes 0 and 2, n_dims
+ *          in 8 .. ne0 and a multiple of 8; ne0 <= 256, a multiple of 32 for the
+ *          block types and of 4 otherwise.  The rotation is the formula written out
+ *          under fattn_k_shift with p the position, computed by the same device
+ *          functions: THE SAME f32 y FOR EVERY DST TYPE, and equal x, p and
+ *          parameters give the very y fattn_k_shift computes over an F32 cache
+ *          holding x.  Unlike the K-shift this is a write: every row with a valid
+ *          slot is written whole, p == 0 included (the formula is computed, not
+ *          skipped: attn_factor still scales); elements at or past n_dims pass
+ *          through and are written too
+ *   rope == NULL  no rotation; pos and freq_factors are ignored, ne0 follows
+ *          fattn_set_rows' rules (no 256 limit; any ne0 >= 1 for F32 / F16 / BF16) and
+ *          the bytes are those fattn_set_rows writes -- this is its BF16 / F32 form
+ *   v_src / v_dst  both NULL (a K-only launch) or both given: F32 [ne0v, nr, ne2v,
+ *          ne3] into any of the dst types [ne0v, n_slots_v, ne2v, ne3].  Never
+ *          rotated; ne0v follows fattn_set_rows' rules and may differ from ne0.  The
+ *          same idx (ne2v % ne11 == 0), slots compared with v_dst.ne[1].  K's and
+ *          V's types are independent.  K and V dst rows must not overlap each other
+ *          or themselves (the caller's duty)
+ * Out of scope: M-RoPE / vision modes; rows longer than 256 with a rope (the MLA
+ * row keeps fattn_set_rows, its RoPE dims a view); rotating Q.
+ * Validated before anything launches, K (with pos, idx and rope) before V: NULL
+ * k_src / idx / k_dst (pos with a rope) or a NULL data, one of v_src / v_dst
+ * without the other, any ne <= 0, ne / nr / ne3 that do not match between the
+ * tensors, ne0 no multiple of the type's unit, more than 2^31 - 1 blocks in one
+ * [ne0, nr] plane and the rope ranges listed under fattn_k_shift
+ * FATTN_ERR_INVALID_ARG; a type (pos not I32 included) FATTN_ERR_UNSUPPORTED_TYPE;
+ * ne0 > 256 with a rope FATTN_ERR_UNSUPPORTED_HEAD_DIM; a wrong nb[0] or a negative
+ * idx / pos stride FATTN_ERR_BAD_STRIDE; alignment (freq_factors a multiple of 4)
+ * FATTN_ERR_ALIGNMENT.  Stream-ordered; allocates nothing, needs no workspace,
+ * does not synchronise, capturable. */
+int fattn_rope_set_rows(const fattn_tensor* k_src, const fattn_tensor* pos, const fattn_tensor* idx,
+                        const fattn_tensor* k_dst, const float* freq_factors, const fattn_rope* rope,
+                        const fattn_tensor* v_src, const fattn_tensor* v_dst, void* stream);
 
 const char* fattn_strerror(int status);
 /* bytes of one row of k elements (0 if unsupported; BF16: 2 k) */
