@@ -278,7 +278,34 @@ int fattn_ext_lse(const fattn_params* p, const float* sinks, float* lse, void* s
     return launch_ext(p, sinks, lse, stream, nullptr, nullptr);
 }
 
-int fattn_ext_f16_launch(const void* q, const void* k, const void* v, const void* mask, float* dst, float scale,
+// MLA attention over per-query slot lists.  A plan of its own (plan_mla_sparse):
+// the plan of `p`, fattn_describe and fattn_workspace_size are not involved
+size_t fattn_ext_sparse_workspace_size(const fattn_params* p, const fattn_tensor* idx) {
+    Plan pl;
+    SparseIdx sx;
+    if (plan_mla_sparse(p, idx, current_options(), device_cus(), pl, sx) != FATTN_OK) return 0;
+    return pl.ws_bytes;
+}
+
+int fattn_ext_sparse(const fattn_params* p, const fattn_tensor* idx, const float* sinks, float* lse, void* stream) {
+    Plan pl;
+    SparseIdx sx;
+    const int rc = plan_mla_sparse(p, idx, current_options(), device_cus(), pl, sx);
+    if (rc != FATTN_OK) return rc;
+    if ((uintptr_t)sinks % 4) return FATTN_ERR_ALIGNMENT;
+    if ((uintptr_t)lse % 4) return FATTN_ERR_ALIGNMENT;
+    pl.a.sinks = sinks;
+    pl.lse = lse;
+    if (pl.ws_bytes) {  // (f32 partials behind their (m, l) pairs: no arrival words)
+        if (!p->workspace || p->workspace_bytes < pl.ws_bytes || (uintptr_t)p->workspace % 16) return FATTN_ERR_WORKSPACE;
+        uint8_t* w = (uint8_t*)p->workspace;
+        pl.a.ws_ml = (float*)w;
+        pl.a.ws_o = (float*)(w + pl.ml_bytes);
+    }
+    return launch_mla_sparse(pl, sx, (hipStream_t)stream);
+}
+
+int fattn_ext_f16_launch(const void* q,const void* k, const void* v, const void* mask, float* dst, float scale,
                          int ne00, int ne01, int ne02, int ne03, int ne10, int ne11, int ne12, int ne13, int ne31,
                          int nb31, int nb01, int nb02, int nb03, int nb11, int nb12, int nb13, int ne0, int ne1,
                          int ne2, int ne3, int k_type, int v_type, void* workspace, size_t workspace_bytes,

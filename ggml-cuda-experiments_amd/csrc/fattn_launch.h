@@ -487,6 +487,9 @@ int launch_types(const Plan& pl, hipStream_t st, const Events& ev) {
 int launch_mla(const Plan& pl, hipStream_t st, const Events& ev);
 // ... over a Q8_0 / Q4_0 cache (instantiated in fattn_launch_mla_q.hip)
 int launch_mla_q(const Plan& pl, hipStream_t st, const Events& ev);
+// ... over per-query slot lists (fattn_ext_sparse; instantiated in fattn_launch_mla_sparse.hip)
+struct SparseIdx;
+int launch_mla_sparse(const Plan& pl, const SparseIdx& sx, hipStream_t st);
 
 extern template int launch_types<64>(const Plan&, hipStream_t, const Events&);
 extern template int launch_types<80>(const Plan&, hipStream_t, const Events&);

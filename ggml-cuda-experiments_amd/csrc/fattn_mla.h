@@ -60,6 +60,26 @@ struct MlaArgsT {
 };
 using MlaArgs = MlaArgsT<SplitArgs>;
 
+// fattn_ext_sparse (SPARSE): the keys of a query row are the cache rows its
+// slot list names -- idx I32 [topk][n_q][e2][e3], shared by the heads of a kv
+// head.  Here a.N is the LIST's length (the tile walk's), n_kv the cache's rows:
+// an entry outside [0, n_kv) is no key.  raw16 is 0.
+template <typename A>
+struct MlaSparseArgsT : MlaArgsT<A> {
+    const uint8_t* idx;
+    int64_t i_nb1, i_nb2, i_nb3;
+    int i_ne2, i_ne3;  // list planes: kv head ik2 of sequence iq3 reads (ik2 % i_ne2, iq3 % i_ne3); i_ne2 is 1 or Hkv
+    int n_kv;
+};
+template <typename A, bool SPARSE>
+using MlaKernArgs = typename std::conditional<SPARSE, MlaSparseArgsT<A>, MlaArgsT<A>>::type;
+
+// SPARSE: every wave keeps its own copy of the slot lists of the tiles between
+// their fetch and their compute -- a ring of 4 tiles behind the tile ring, one
+// dword DMA of the wave per tile (lanes 32 - 63 past the descriptor): 4 KiB
+constexpr int kMlaIdxRing = 4;
+constexpr int kMlaIdxBytes = kMlaIdxRing * kMlaWaves * kWave * 4;
+
 // KT: the cache's type.  F16: the ring holds f16 tiles as they come from HBM.
 // Q8_0 / Q4_0 (V a view of K only): the ring holds RAW tiles -- 32 rows of 18
 // blocks, landed in dword pieces -- and two f16 images that all 256 threads
@@ -232,11 +252,22 @@ __device__ __forceinline__ void mla_wait_tiles(int pending) {
 // SOLO (quantised cache only; the launcher's choice): no tile of the launch has
 // more than one wave's 16 rows (H = 16 decode), so wave 0 computes and waves
 // 1 - 3 load and convert -- the conversion leaves the computing wave's chain.
-template <bool VOWN, bool HM, int KT = FATTN_TYPE_F16, bool SOLO = false, typename A = SplitArgs>
-__global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const MlaArgsT<A> ma) {
+//
+// SPARSE (fattn_ext_sparse): the tile walk runs over the
+// query row's slot list instead of the cache's rows -- tile s is list positions
+// c_lo + 32 s ... and its K / V rows are the cache rows they name.  A tile's 32
+// slot numbers reach LDS by one dword DMA per wave (issue_idx), one tile ahead
+// of the deepest K prefetch, so that the lanes' gather offsets (slot * nb1
+// where the dense form has (n0 + row) * nb1) are LDS reads of landed data.
+// An entry outside the cache, like a position past the chunk's end, is
+// requested past the descriptor and its score set to -inf by selection, in
+// every tile (the validity word: a ballot of the same test).
+template <bool VOWN, bool HM, int KT = FATTN_TYPE_F16, bool SOLO = false, typename A = SplitArgs, bool SPARSE = false>
+__global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const MlaKernArgs<A, SPARSE> ma) {
     using C = MlaCfg<VOWN, KT>;
     constexpr bool QUANT = C::QUANT;
     static_assert(QUANT || !SOLO, "");
+    static_assert(!SPARSE || !HM, "the list is the mask");
     const A& a = ma.a;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     constexpr int NB = kMlaDK / QK;   // 18 k-steps
@@ -288,6 +319,28 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
 
     const StepSrc rs = kv_sources<HM>(a, ik2, ik3, iq3, VOWN ? a.v_span : 0);
 
+    // ---- SPARSE: the row's slot list (QPT = 1: the tile's query row is qt) and
+    // this wave's ring of tile lists.  list_of(t): tile t's 32 entries (dwords);
+    // slot_at(t, row, e): entry `row` of it is a key -- inside the chunk and
+    // naming a cache row (-1, the usual padding, is 0xFFFFFFFF here)
+    i32x4 isrd = {};
+    uint32_t n_kv = 0;
+    const uint32_t i_span = (uint32_t)a.N * 4u;
+    if constexpr (SPARSE) {
+        const int i2 = ma.i_ne2 == 1 ? 0 : ik2, i3 = ma.i_ne3 == 1 ? 0 : iq3 % ma.i_ne3;
+        isrd = make_srd(ma.idx + (int64_t)qt * ma.i_nb1 + (int64_t)i2 * ma.i_nb2 + (int64_t)i3 * ma.i_nb3, i_span);
+        n_kv = (uint32_t)ma.n_kv;
+    }
+    auto list_of = [&](int t) { return smem + C::ldsBytes + ((t & (kMlaIdxRing - 1)) * kMlaWaves + wave) * (kWave * 4); };
+    auto issue_idx = [&](int t) {
+        const int pos = c_lo + t * kStep + lane;
+        dma<4>(isrd, lds_addr(list_of(t)), lane < kStep && pos < c_hi ? (uint32_t)pos * 4u : i_span);
+    };
+    auto slot_at = [&](int t, int row, uint32_t& e) -> bool {
+        e = *(const uint32_t*)(list_of(t) + row * 4);
+        return c_lo + t * kStep + row < c_hi && e < n_kv;
+    };
+
     // ---- Q^T operands (B of S^T = K.Q^T), rounded to f16 like src/utils.h:10;
     // k-step b of lane group g holds the dims of chunk mla_kchunk(b, g)
     f16x8 qop[NB];
@@ -328,15 +381,20 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     // Copy tile [n0, n0 + 32) into `buf`: K image | V image (VOWN) | mask rows.
     // Lane-linear LDS-DMA: LDS slot (row, cs) takes the row's chunk cs ^ swizzle.
     // Rows from c_hi on are requested past the descriptor: zeros, no traffic.
+    // SPARSE: the row's cache row is the list's entry (key_row)
+    auto key_row = [&](int n0, int row, uint32_t& r) -> bool {
+        if constexpr (SPARSE) return slot_at((n0 - c_lo) / kStep, row, r);
+        r = (uint32_t)(n0 + row);
+        return n0 + row < c_hi;
+    };
     auto issue = [&](int n0, uint8_t* buf) {
         const uint32_t lb = __builtin_amdgcn_readfirstlane(lds_addr(buf) + wave * kWave * 16);
 #pragma unroll
         for (int i = 0; i < C::NIK; i++) {
             const int pc = i * C::NT + tid;
             const int row = pc / C::CPK, cs = pc - row * C::CPK;
-            const uint32_t off = n0 + row < c_hi
-                                     ? (uint32_t)(n0 + row) * (uint32_t)a.k_nb1 + (uint32_t)((cs ^ mla_ksw(row)) * 16)
-                                     : a.k_span;
+            uint32_t r;
+            const uint32_t off = key_row(n0, row, r) ? r * (uint32_t)a.k_nb1 + (uint32_t)((cs ^ mla_ksw(row)) * 16) : a.k_span;
             dma<16>(rs.k, lb + i * C::NT * 16, off);
         }
         if constexpr (VOWN) {
@@ -344,9 +402,8 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
             for (int i = 0; i < C::NIV; i++) {
                 const int pc = i * C::NT + tid;
                 const int row = pc / C::CPV, cs = pc - row * C::CPV;
-                const uint32_t off = n0 + row < c_hi
-                                         ? (uint32_t)(n0 + row) * (uint32_t)a.v_nb1 + (uint32_t)((cs ^ ((row & 7) << 1)) * 16)
-                                         : a.v_span;
+                uint32_t r;
+                const uint32_t off = key_row(n0, row, r) ? r * (uint32_t)a.v_nb1 + (uint32_t)((cs ^ ((row & 7) << 1)) * 16) : a.v_span;
                 dma<16>(rs.v, lb + C::kBytes + i * C::NT * 16, off);
             }
         }
@@ -368,6 +425,10 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
     auto raw_off = [&](int w, int n0) -> uint32_t {
         constexpr int RD = QUANT ? C::rawRow / 4 : 1;
         const int row = w / RD, col = w - row * RD;
+        if constexpr (SPARSE) {
+            uint32_t r = 0;
+            return w < C::rawDw && key_row(n0, row, r) ? r * (uint32_t)a.k_nb1 + (uint32_t)(col * 4) : a.k_span;
+        }
         return w < C::rawDw && n0 + row < c_hi ? (uint32_t)(n0 + row) * (uint32_t)a.k_nb1 + (uint32_t)(col * 4) : a.k_span;
     };
     auto issue_raw = [&](int n0, uint8_t* slot) {
@@ -382,7 +443,7 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
             // Not the part-filled last tile of N: its rows from N on must read as
             // zeros, and a 16-B piece can straddle the end of a 612-B row.
             constexpr int NP16 = (kStep * C::rawRow / 16 + kWave - 1) / kWave;
-            if (ma.raw16 && n0 + kStep <= c_hi) {
+            if (!SPARSE && ma.raw16 && n0 + kStep <= c_hi) {  // (gathered rows are no run)
 #pragma unroll
                 for (int jj = 0; jj < (NP16 + 2) / 3; jj++) {
                     const int j = 3 * jj + h;
@@ -442,6 +503,11 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
         // of tile 1; waiting down to the smallest count is safe for all three)
         // (16-B pieces: 6 or 7 (3 or 4) of them; the smaller count is safe for both forms)
         constexpr int NI_SOLO = (kStep * C::rawRow / 16 + kWave - 1) / kWave / 3 + (HM ? kRows / 4 / 3 : 0);
+        if constexpr (SPARSE) {  // the lists of tiles 0 .. 2, landed before the first gather reads them
+#pragma unroll
+            for (int t = 0; t < 3; t++) issue_idx(t);
+            wait_vmcnt_c<0>();
+        }
         issue_raw(c_lo, raw_of(0));
         if (ntiles > 1) {
             issue_raw(c_lo + kStep, raw_of(1));
@@ -453,6 +519,11 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
         __syncthreads();
         mla_convert_tile<KT, SOLO>(raw_of(0), img_of(0), tid);
     } else {
+        if constexpr (SPARSE) {  // the lists of tiles 0 .. PRE
+#pragma unroll
+            for (int t = 0; t <= PRE; t++) issue_idx(t);
+            wait_vmcnt_c<0>();
+        }
         for (int s = 0; s < PRE && s < ntiles; s++) issue(c_lo + s * kStep, buf_of(s));
     }
 
@@ -475,12 +546,18 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
         if constexpr (QUANT) {
             wait_vmcnt_c<0>();
             __syncthreads();
-            if (s + 2 < ntiles) issue_raw(c_lo + (s + 2) * kStep, raw_of(s + 2));
+            if (s + 2 < ntiles) {
+                if constexpr (SPARSE) issue_idx(s + 3);
+                issue_raw(c_lo + (s + 2) * kStep, raw_of(s + 2));
+            }
             if (s + 1 < ntiles) mla_convert_tile<KT, SOLO>(raw_of(s + 1), img_of(s + 1), tid);
         } else {
             mla_wait_tiles<(PRE - 1) * NI>(min(PRE - 1, ntiles - 1 - s));
             __syncthreads();
-            if (s + PRE < ntiles) issue(c_lo + (s + PRE) * kStep, buf_of(s + PRE));
+            if (s + PRE < ntiles) {
+                if constexpr (SPARSE) issue_idx(s + PRE + 1);
+                issue(c_lo + (s + PRE) * kStep, buf_of(s + PRE));
+            }
         }
         if (!active) continue;
         const uint8_t* kb = QUANT ? img_of(s) : buf_of(s);
@@ -556,8 +633,14 @@ __global__ __launch_bounds__(kMlaWaves* kWave, 1) void fattn_mla_kernel(const Ml
 #pragma unroll
                 for (int j = 0; j < 8; j++) sv[j] = st[j >> 2][j & 3] * a.scale_log2 + mk[j] * log2e;
             }
-            // keys past the chunk's end (the last tile of N): zero-filled rows, no score
-            if (n0 + kStep > c_hi) {
+            if constexpr (SPARSE) {
+                // the tile's validity word: zero-filled rows have no score, in any tile
+                uint32_t e;
+                const uint32_t vw = (uint32_t)__builtin_amdgcn_ballot_w64(slot_at(s, lane & (kStep - 1), e));
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    if (!((vw >> (16 * (j >> 2) + 4 * g + (j & 3))) & 1u)) sv[j] = kNegInf;
+            } else if (n0 + kStep > c_hi) {  // keys past the chunk's end (the last tile of N): zero-filled rows, no score
 #pragma unroll
                 for (int j = 0; j < 8; j++)
                     if (n0 + 16 * (j >> 2) + 4 * g + (j & 3) >= c_hi) sv[j] = kNegInf;

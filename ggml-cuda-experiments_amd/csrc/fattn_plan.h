@@ -898,4 +898,62 @@ inline int make_plan(const fattn_params* p, const Options& o, int cus, Plan& pl)
     return FATTN_OK;
 }
 
+// ---------------------------------------------------------------- fattn_ext_sparse
+// The slot lists of a sparse MLA launch: idx I32 [topk][n_q][e2][e3] (include/fattn.h)
+struct SparseIdx {
+    const uint8_t* data = nullptr;
+    int64_t nb1 = 0, nb2 = 0, nb3 = 0;
+    int ne2 = 1, ne3 = 1;
+    int n_kv = 0;  // the cache's rows: an entry outside [0, n_kv) is no key
+};
+
+inline int check_sparse_idx(const fattn_tensor* idx, int64_t NQ, int64_t Hkv, int64_t S, SparseIdx& sx) {
+    if (!idx || !idx->data) return FATTN_ERR_INVALID_ARG;
+    const int64_t topk = idx->ne[0], e2 = idx->ne[2], e3 = idx->ne[3];
+    if (topk < 1 || topk > (int64_t)1 << 24 || idx->ne[1] != NQ) return FATTN_ERR_INVALID_ARG;
+    if ((e2 != 1 && e2 != Hkv) || e3 < 1 || S % e3) return FATTN_ERR_INVALID_ARG;
+    if (idx->type != FATTN_TYPE_I32) return FATTN_ERR_UNSUPPORTED_TYPE;
+    // (a count of 1 has no stride to look at)
+    sx.nb1 = NQ > 1 ? idx->nb[1] : 0;
+    sx.nb2 = e2 > 1 ? idx->nb[2] : 0;
+    sx.nb3 = e3 > 1 ? idx->nb[3] : 0;
+    if (idx->nb[0] != 4 || sx.nb1 < 0 || sx.nb2 < 0 || sx.nb3 < 0) return FATTN_ERR_BAD_STRIDE;
+    if ((uintptr_t)idx->data % 4 || sx.nb1 % 4 || sx.nb2 % 4 || sx.nb3 % 4) return FATTN_ERR_ALIGNMENT;
+    sx.data = (const uint8_t*)idx->data;
+    sx.ne2 = (int)e2, sx.ne3 = (int)e3;
+    return FATTN_OK;
+}
+
+// Sparse MLA sizing: the dense plan of `p` (validation, views, score transform,
+// V form) re-tiled -- a tile is the heads of one kv head for ONE query row (only
+// those rows share a list), so QPT = 1 and n_qt = n_q -- and size_mla's chunk
+// rule over the LIST: tiles = ceil(topk / 32), kv_chunk in list positions.  The
+// LDS figure gains the slot-list ring.  No contiguous-tile (raw16) form.
+inline int size_mla_sparse(Plan& pl, int kv_chunk, int64_t NQ, int64_t Hkv, int64_t S, int64_t topk) {
+    SplitArgs& a = pl.a;
+    a.QPT = 1;
+    a.n_qt = (int)NQ;
+    pl.mla_solo = pl.kt != FATTN_TYPE_F16 && a.R <= kRows;
+    pl.mla_raw16 = false;
+    const int64_t Y = Hkv * a.n_hsub * NQ;
+    if (Y > 65535 || S > 65535) return FATTN_ERR_INVALID_ARG;
+    a.N = (int)topk;
+    pl.ws_bytes = pl.cnt_bytes = pl.ml_bytes = 0;
+    const int rc = size_mla(pl, kv_chunk, Y, S, topk);
+    pl.lds += kMlaIdxBytes;
+    return rc;
+}
+
+// validate (p, idx) in the header's order and plan the sparse launch
+inline int plan_mla_sparse(const fattn_params* p, const fattn_tensor* idx, const Options& o, int cus, Plan& pl, SparseIdx& sx) {
+    const int rc = make_plan(p, o, cus, pl);
+    if (rc != FATTN_OK) return rc;
+    if (pl.kernel != Kernel::Mla) return FATTN_ERR_UNSUPPORTED_HEAD_DIM;
+    if (p->mask.data) return FATTN_ERR_INVALID_ARG;
+    const int64_t NQ = p->q.ne[1], S = p->q.ne[3], Hkv = p->k.ne[2];
+    if (const int rx = check_sparse_idx(idx, NQ, Hkv, S, sx)) return rx;
+    sx.n_kv = (int)p->k.ne[1];
+    return size_mla_sparse(pl, p->kv_chunk, NQ, Hkv, S, idx->ne[0]);
+}
+
 }  // namespace fattn

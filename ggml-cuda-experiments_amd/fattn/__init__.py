@@ -40,7 +40,7 @@ EXPORTS = (
     "fattn_workspace_size", "fattn_workspace_init", "fattn_ext", "fattn_ext_events", "fattn_ext_f16_launch", "fattn_row_workspace_size", "fattn_row",
     "fattn_dequantize", "fattn_quantize", "fattn_strerror", "fattn_row_size", "fattn_version", "fattn_set_option",
     "fattn_describe", "fattn_cpy", "fattn_ext_sinks", "fattn_set_rows", "fattn_ext_lse", "fattn_lse_merge",
-    "fattn_k_shift", "fattn_rope_set_rows",
+    "fattn_k_shift", "fattn_rope_set_rows", "fattn_ext_sparse_workspace_size", "fattn_ext_sparse",
 )
 ROPE_NORMAL, ROPE_NEOX = 0, 2   # fattn_rope.mode: ggml's GGML_ROPE_TYPE_NORMAL / GGML_ROPE_TYPE_NEOX
 OPT_MQ_ROWS_PER_WAVE = 1
@@ -138,6 +138,10 @@ def lib() -> C.CDLL:
         L.fattn_ext_sinks.argtypes = [C.POINTER(FattnParams), vp, vp]
         L.fattn_ext_lse.restype = C.c_int
         L.fattn_ext_lse.argtypes = [C.POINTER(FattnParams), vp, vp, vp]
+        L.fattn_ext_sparse_workspace_size.restype = sz
+        L.fattn_ext_sparse_workspace_size.argtypes = [C.POINTER(FattnParams), C.POINTER(FattnTensor)]
+        L.fattn_ext_sparse.restype = C.c_int
+        L.fattn_ext_sparse.argtypes = [C.POINTER(FattnParams), C.POINTER(FattnTensor), vp, vp, vp]
         L.fattn_lse_merge.restype = C.c_int
         L.fattn_lse_merge.argtypes = [vp, vp, C.c_int32, i64, C.c_int32, i64, i64, vp, C.c_int32, vp, vp, vp]
         L.fattn_ext_events.restype = C.c_int
@@ -357,6 +361,28 @@ def flash_attn_ext(p: FattnParams, stream=None, ev_begin=None, ev_end=None, sink
         _check(lib().fattn_ext(C.byref(p), _stream(stream)), "fattn_ext")
     else:
         _check(lib().fattn_ext_events(C.byref(p), _stream(stream), ev_begin, ev_end), "fattn_ext_events")
+
+
+def _idx_tensor(idx) -> FattnTensor:
+    return idx.c() if isinstance(idx, View) else idx
+
+
+def sparse_workspace_size(p: FattnParams, idx) -> int:
+    """fattn_ext_sparse_workspace_size: the workspace of flash_attn_ext_sparse(p, idx), a
+    function of p and idx's ne alone (0: one chunk, or invalid arguments)."""
+    return int(lib().fattn_ext_sparse_workspace_size(C.byref(p), C.byref(_idx_tensor(idx))))
+
+
+def flash_attn_ext_sparse(p: FattnParams, idx, stream=None, sinks=None, lse=None):
+    """MLA attention over per-query slot lists (include/fattn.h, fattn_ext_sparse):
+    p in the MLA shape without a mask; idx a View (or FattnTensor) of TYPE_I32 device
+    memory, ne = (topk, n_q, e2, e3) -- row (iq3, iq1, head of kv head ik2) attends to the
+    cache rows idx[:, iq1, ik2 % e2, iq3 % e3], entries outside the cache (-1) being no
+    keys.  The lists are read by the kernel: a captured launch follows the buffer's
+    contents.  sinks / lse as flash_attn_ext's."""
+    sptr = _sinks_ptr(sinks, int(p.q.ne[2]))
+    lptr = _lse_ptr(lse, int(p.q.ne[1]) * int(p.q.ne[2]) * int(p.q.ne[3]))
+    _check(lib().fattn_ext_sparse(C.byref(p), C.byref(_idx_tensor(idx)), sptr, lptr, _stream(stream)), "fattn_ext_sparse")
 
 
 def lse_merge(outs, lses, dst, sinks=None, lse_out=None, n_head=None, stream=None):

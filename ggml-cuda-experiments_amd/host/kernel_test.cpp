@@ -58,7 +58,9 @@
 //                        of 576 f16, V the 512 elements of the same rows from element 0 (latent
 //                        first) or 64 (RoPE dims first, llama.cpp's order) -- a view of K, so each
 //                        cache row is read once; --heads (default 16) / --kv-size / --n-q / --mask
-//                        / --iters / --tol / --cpu-only / --dump apply, scale = 1 / sqrt(192); the
+//                        / --iters / --tol / --cpu-only / --dump apply, scale = 1 / sqrt(192);
+//                        --sparse TOPK: fattn_ext_sparse over per-query-row slot lists of TOPK entries
+//                        (some -1, some repeated), the reference over the gathered rows, no mask; the
 //                        CPU reference is plain C++ over K dim 576 and V dim 512.  With
 //                        --kv-type q8_0|q4_0 the cache rows are quantised (fattn_quantize; on the
 //                        host with --cpu-only), V is the view --v-off 0|32|64 elements (whole
@@ -467,8 +469,13 @@ void dequant_host_q80_q40(int type, const uint8_t* src, float* dst, int D, int64
 // line of the other branches.  --kv-type q8_0 | q4_0: the cache rows are
 // quantised (fattn_quantize; on the host with --cpu-only), the reference takes
 // the blocks dequantised on the host, and V is the view v_off / 32 blocks in.
-int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mask_kind, bool cpu_only, int iters, float tol,
-            const char* dump, bool use_lse) {
+// --sparse topk: fattn_ext_sparse -- every query row attends to its own list of
+// topk cache slots (rand() % N, every 13th entry -1, every 17th a repeat of the
+// entry before it); the reference runs per query row over the gathered rows of
+// the list's valid entries, in list order.  No mask.
+int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mask_kind_in, bool cpu_only, int iters, float tol,
+            const char* dump, bool use_lse, int sparse) {
+    const std::string mask_kind = sparse > 0 ? "none" : mask_kind_in;
     const bool quant = kv_type == FATTN_TYPE_Q8_0 || kv_type == FATTN_TYPE_Q4_0;
     if (kv_type != FATTN_TYPE_F16 && !quant) {
         fprintf(stderr, "--mla: --kv-type f16|q8_0|q4_0\n");
@@ -511,7 +518,24 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     const int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
     std::vector<float> ref((size_t)kMlaDV * H * NQ), got(ref.size());
     std::vector<float> lse_ref((size_t)H * NQ), lse_got(lse_ref.size());
-    cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads, use_lse ? &lse_ref : nullptr);
+    std::vector<int32_t> lists((size_t)std::max(sparse, 0) * NQ);
+    if (sparse > 0) {
+        for (size_t j = 0; j < lists.size(); j++) lists[j] = j % 13 == 5 ? -1 : j % 17 == 3 ? lists[j - 1] : rand() % N;
+        for (int r = 0; r < NQ; r++) {
+            std::vector<float> rows, q1(query.begin() + (size_t)r * H * kMlaDK, query.begin() + (size_t)(r + 1) * H * kMlaDK);
+            for (int j = 0; j < sparse; j++) {
+                const int e = lists[(size_t)r * sparse + j];
+                if (e >= 0 && e < N) rows.insert(rows.end(), kv.begin() + (size_t)e * kMlaDK, kv.begin() + (size_t)(e + 1) * kMlaDK);
+            }
+            const int n = (int)(rows.size() / kMlaDK);
+            std::vector<float> zero(n, 0.0f), o1((size_t)H * kMlaDV), l1(H);
+            cpu_reference_mla(q1, rows, zero, o1, n, H, 1, v_off, scale, threads, &l1);
+            std::copy(o1.begin(), o1.end(), ref.begin() + (size_t)r * H * kMlaDV);
+            std::copy(l1.begin(), l1.end(), lse_ref.begin() + (size_t)r * H);
+        }
+    } else {
+        cpu_reference_mla(query, kv, mask, ref, N, H, NQ, v_off, scale, threads, use_lse ? &lse_ref : nullptr);
+    }
     print_array("Reference", ref.data(), 16);
     if (use_lse) print_array("Reference LSE", lse_ref.data(), std::min(16, H * NQ));
     if (cpu_only) {
@@ -561,12 +585,20 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
                   {2, (int64_t)Np * 2, (int64_t)Np * 2 * mask_rows, (int64_t)Np * 2 * mask_rows}};
     p.dst = d_out;
     p.scale = scale;
-    const size_t ws_bytes = std::max<size_t>(fattn_workspace_size(&p), 16);
+    void* d_idx = nullptr;
+    fattn_tensor idx = {nullptr, FATTN_TYPE_I32, 0, {sparse, NQ, 1, 1}, {4, 4 * (int64_t)sparse, 4 * (int64_t)sparse * NQ, 4 * (int64_t)sparse * NQ}};
+    if (sparse > 0) {
+        HIP_CHECK(hipMalloc(&d_idx, 4 * lists.size()));
+        HIP_CHECK(hipMemcpyAsync(d_idx, lists.data(), 4 * lists.size(), hipMemcpyHostToDevice, st));
+        idx.data = d_idx;
+    }
+    auto launch = [&] { return sparse > 0 ? fattn_ext_sparse(&p, &idx, nullptr, d_lse, st) : fattn_ext_lse(&p, nullptr, d_lse, st); };
+    const size_t ws_bytes = std::max<size_t>(sparse > 0 ? fattn_ext_sparse_workspace_size(&p, &idx) : fattn_workspace_size(&p), 16);
     HIP_CHECK(hipMalloc(&d_ws, ws_bytes));
     int rc = fattn_workspace_init(d_ws, ws_bytes, st);
     p.workspace = d_ws;
     p.workspace_bytes = ws_bytes;
-    rc = rc ? rc : fattn_ext_lse(&p, nullptr, d_lse, st);  // (d_lse null: fattn_ext)
+    rc = rc ? rc : launch();  // (d_lse null: fattn_ext)
     if (rc) {
         fprintf(stderr, "launch failed: %s\n", fattn_strerror(rc));
         return 2;
@@ -578,7 +610,7 @@ int run_mla(int H, int N, int NQ, int v_off, int kv_type, const std::string& mas
     std::vector<float> times;
     for (int it = 0; it < iters; it++) {
         HIP_CHECK(hipEventRecord(start, st));
-        rc = fattn_ext_lse(&p, nullptr, d_lse, st);
+        rc = launch();
         HIP_CHECK(hipEventRecord(stop, st));
         HIP_CHECK(hipEventSynchronize(stop));
         if (rc) {
@@ -1085,7 +1117,7 @@ int main(int argc, const char* argv[]) {
     const char* dump = nullptr;
     float tol = 1e-3f, max_bias = 0.0f, softcap = 0.0f, sink_base = 0.0f;
     bool use_sinks = false, set_rows = false, mla = false, heads_given = false;
-    int mla_v_off = 0, k_shift_delta = 0;
+    int mla_v_off = 0, k_shift_delta = 0, mla_sparse = 0;
     bool k_shift = false, rope_neox = true, rope_set_rows = false;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
@@ -1117,6 +1149,7 @@ int main(int argc, const char* argv[]) {
         else if (a == "--mla") mla = true;
         else if (a == "--lse") use_lse = true;
         else if (a == "--v-off") mla_v_off = atoi(next());
+        else if (a == "--sparse") mla_sparse = atoi(next());
         else if (a == "--k-shift") k_shift = true, k_shift_delta = atoi(next());
         else if (a == "--rope-set-rows") rope_set_rows = true;
         else if (a == "--rope-mode") {
@@ -1167,7 +1200,7 @@ int main(int argc, const char* argv[]) {
     if (rope_set_rows)
         return run_rope_set_rows(rope_neox, head_dim, num_heads, num_kv_heads, kv_size, kv_type, mask_kind, cpu_only, iters, tol);
     // (the model family's smallest head count unless --heads says otherwise)
-    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump, use_lse);
+    if (mla) return run_mla(heads_given ? num_heads : 16, kv_size, n_q, mla_v_off, kv_type, mask_kind, cpu_only, iters, tol, dump, use_lse, mla_sparse);
     if (n_q > 1 || ngpu > 1) parallel_kv = false;        // flash_attn_row is one query row on one device
     const bool op_xf = max_bias != 0.0f || softcap != 0.0f;
     if (op_xf) parallel_kv = false;                      // (neither positional list carries the two scalars)

@@ -383,6 +383,51 @@ int fattn_lse_merge(const float* outs, const float* lses, int32_t n_parts, int64
                     int64_t out_part_stride, int64_t lse_part_stride, const float* sinks, int32_t n_head,
                     float* dst, float* lse_out, void* stream);
 
+/* MLA attention over per-query slot lists (DeepSeek-V3.2's sparse attention and
+ * its kin: an indexer picks, per query token, the topk cache slots that matter,
+ * one list for all heads of the token).  The launch reads the listed rows only.
+ *   p    read as fattn_ext reads it, in the MLA shape alone: q.ne[0] = k.ne[0] =
+ *        576, v.ne[0] = 512, K / V f16 (V a view of K 0 .. 128 bytes in, or of
+ *        its own) or Q8_0 / Q4_0 (V the view 0 / 1 / 2 blocks in); every view,
+ *        alignment and span rule of that shape holds, dst is [S][n_q][H][512].
+ *        Any other head dim: FATTN_ERR_UNSUPPORTED_HEAD_DIM.  mask.data must be
+ *        NULL (the list is the mask), else FATTN_ERR_INVALID_ARG; max_bias is
+ *        validated and inert.  scale, logit_softcap, n_head_total and head_first
+ *        keep their meaning; sinks and lse those of fattn_ext_lse (NULL: off).
+ *   idx  I32, ne = [topk, n_q, e2, e3], e2 = 1 or Hkv, S % e3 == 0, nb[0] == 4,
+ *        base and nb[1..3] non-negative multiples of 4 (nb[2] / nb[3] looked at
+ *        only where the count exceeds 1), 1 <= topk <= 2^24.  Device memory,
+ *        read by the kernel: the call is capturable and a replay follows the
+ *        buffer's contents.
+ * Output row (sequence iq3, query row iq1, q head h of kv head ik2) attends to
+ *     e_j = idx[j, iq1, ik2 % e2, iq3 % e3],  j = 0 .. topk - 1:
+ *     dst = softmax_j(score(q, K[e_j])) . V[e_j],
+ * score being fattn_ext's (scale, then soft cap), K / V rows of the query's kv
+ * plane (ik2, iq3 % Skv).  An entry outside 0 <= e < k.ne[1] is no key (-1: the
+ * usual padding): it contributes nothing, reads nothing and never fails the
+ * call.  A slot named twice is two keys.  A row with no valid entry is
+ * fattn_ext's row masked -inf everywhere: NaN and lse = -inf without sinks,
+ * zeros and lse = sinks[h] with sinks.
+ *   kv_chunk  a hint in LIST positions, rounded up to 32-entry tiles, at most 64
+ *        chunks; 0: the MLA plan's own rule over ceil(topk / 32) tiles.
+ *   workspace  fattn_ext_sparse_workspace_size(p, idx) bytes, a function of p
+ *        and idx->ne alone (idx->data is not looked at), 0 for one chunk; the
+ *        rules of fattn_workspace_size otherwise (caller-owned, no zeroing).
+ * Validated in this order, nothing launched on error: what fattn_ext returns
+ * for p's views and scalars; the head dim; the mask rule; idx -- NULL, ne or
+ * divisibility FATTN_ERR_INVALID_ARG, a type other than I32
+ * FATTN_ERR_UNSUPPORTED_TYPE, nb[0] != 4 or a negative stride
+ * FATTN_ERR_BAD_STRIDE, misalignment FATTN_ERR_ALIGNMENT; more than 65535 tiles
+ * (Hkv x head subgroups x n_q) FATTN_ERR_INVALID_ARG; sinks / lse alignment;
+ * the workspace (FATTN_ERR_WORKSPACE).  The sizing function returns 0 on error.
+ * With n_q = 1 and every list 0, 1, ..., N - 1 the launch is bit for bit
+ * fattn_ext_lse(p, sinks, lse) at the same kv_chunk: same tiles, chunks and
+ * arithmetic order.  A Q8_0 / Q4_0 launch is bit for bit the f16 launch over the
+ * dequantised rows.  fattn_describe / fattn_workspace_size(p) do not describe
+ * this launch.  Stream-ordered, does not synchronise, allocates nothing. */
+size_t fattn_ext_sparse_workspace_size(const fattn_params* p, const fattn_tensor* idx);
+int fattn_ext_sparse(const fattn_params* p, const fattn_tensor* idx, const float* sinks, float* lse, void* stream);
+
 /* flash-llama.h:7-32 argument list (K and V share nb11..nb13, flash-llama.h:123-125;
  * mask rows padded to ne31, nb31 bytes per row; one mask plane -- the list has
  * no ne32 / ne33 -- as for fattn_row below).  The one ne10 is K's and V's row

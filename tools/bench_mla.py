@@ -25,6 +25,15 @@ among the forms, every form rotates over the same R, and each record carries
 fraction of 8 TB/s, `hbm_frac_stored`, next to the algorithmic figures.
 
   python tools/bench_mla.py --kv-type q8_0 --kv-type q4_0 --json profiles/mla_quant/bench.json
+
+--sparse TOPK times fattn_ext_sparse: one decode step of 32 sequences, 128 heads,
+over a 65536-slot cache with TOPK random slots per sequence (R rotated list sets,
+so that no launch finds its rows in the Infinity Cache), on f16 and Q8_0, against
+(a) the dense launch over a contiguous TOPK-key cache of the same type (the same
+bytes: the floor) and (b) the dense launch over the whole cache under a 0 / -inf
+mask per sequence (what a caller does without the op).
+
+  python tools/bench_mla.py --sparse 2048 --json profiles/mla_sparse/bench.json
 """
 import argparse
 import json
@@ -45,6 +54,99 @@ SHAPES = {
 HBM_BPS, MFMA_FLOPS = 8e12, 2.5e15
 
 
+def sparse_main(args):
+    import ctypes as C
+    import torch
+    import fattn
+    from bench import hip_events
+
+    dev = torch.device("cuda", 0)
+    DK, DV, H, S, N, topk, R = fattn.MLA_DK, fattn.MLA_DV, 128, 32, 65536, args.sparse, 8
+    hip, evs = hip_events(2)
+    gs = torch.cuda.Stream(dev)
+    f = C.c_float()
+    g = torch.Generator(device=dev)
+    g.manual_seed(4321)
+    q = torch.randn((S, 1, H, DK), generator=g, device=dev)
+    out = torch.empty((S, 1, H, DV), dtype=torch.float32, device=dev)
+    lists = torch.stack([torch.stack([torch.randperm(N, generator=g, device=dev)[:topk] for _ in range(S)]) for _ in range(R)])
+    lists = lists.to(torch.int32).contiguous()                       # [R][S][topk]
+    masks = torch.full((R, S, 1, N), float("-inf"), dtype=torch.float16, device=dev)
+    masks.scatter_(3, lists.long().unsqueeze(2), 0.0)
+    scale = 1.0 / 192 ** 0.5
+    results = []
+    for tname in ("f16", "q8_0"):
+        ty = fattn.TYPE_NAMES[tname]
+        x = torch.randn((S * N, DK), generator=g, device=dev)
+        full = x.to(torch.float16) if tname == "f16" else fattn.quantize(x, ty)
+        small = [(y.to(torch.float16) if tname == "f16" else fattn.quantize(y, ty))
+                 for y in (torch.randn((S * topk, DK), generator=g, device=dev) for _ in range(R))]
+        del x
+        kf, ks = fattn.kv_view(full, ty, DK, N, 1, S), fattn.kv_view(small[0], ty, DK, topk, 1, S)
+        voff = fattn.row_size(ty, DK - DV) if tname != "f16" else 2 * (DK - DV)
+        steps = {}
+        # sparse: the lists rotate (idx: I32 [topk][1][1][S])
+        ps = fattn.ext_params(fattn.q_view(q), kf, fattn.mla_v_view(kf), None, out.data_ptr(), scale)
+        wsb = fattn.sparse_workspace_size(ps, fattn.View(lists.data_ptr(), fattn.TYPE_I32, (topk, 1, 1, S), (4, 4 * topk, 4 * topk, 4 * topk)))
+        ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+        ps.workspace, ps.workspace_bytes = ws.data_ptr(), wsb
+
+        def sparse_step(i, stream):
+            iv = fattn.View(lists[i % R].data_ptr(), fattn.TYPE_I32, (topk, 1, 1, S), (4, 4 * topk, 4 * topk, 4 * topk))
+            fattn.flash_attn_ext_sparse(ps, iv, stream)
+        steps["sparse"] = sparse_step
+        # (a) dense over a contiguous topk-key cache; (b) dense over the whole cache, masked
+        att_a = fattn.Attention(fattn.q_view(q), ks, fattn.mla_v_view(ks), None, out, scale)
+        att_b = fattn.Attention(fattn.q_view(q), kf, fattn.mla_v_view(kf),
+                                fattn.View(masks.data_ptr(), fattn.TYPE_F16, (N, 1, 1, S), (2, 2 * N, 2 * N, 2 * N)), out, scale)
+
+        def a_step(i, stream):
+            att_a.retarget(k=small[i % R].data_ptr(), v=small[i % R].data_ptr() + voff)
+            att_a()
+
+        def b_step(i, stream):
+            att_b.retarget(mask=masks[i % R].data_ptr())
+            att_b()
+        steps["dense_contiguous_topk"], steps["dense_full_masked"] = a_step, b_step
+        graphs = {}
+        for form, step in steps.items():
+            gs.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(gs):
+                step(0, gs.cuda_stream)
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr, stream=gs):
+                for i in range(args.steps):
+                    step(i, gs.cuda_stream)
+            graphs[form] = gr
+        us = {form: [] for form in graphs}
+        for r in range(args.rounds):
+            for form, gr in graphs.items():
+                with torch.cuda.stream(gs):
+                    gr.replay()
+                torch.cuda.synchronize()
+                hip.hipEventRecord(evs[0], gs.cuda_stream)
+                with torch.cuda.stream(gs):
+                    gr.replay()
+                hip.hipEventRecord(evs[1], gs.cuda_stream)
+                torch.cuda.synchronize()
+                hip.hipEventElapsedTime(C.byref(f), evs[0], evs[1])
+                us[form].append(f.value * 1e3 / args.steps)
+                print(f"round {r} {tname} {form:22s} {us[form][-1]:9.3f} us/step", flush=True)
+        for form, v in us.items():
+            rec = dict(shape=f"sparse_topk{topk}", H=H, N=N, S=S, topk=topk, kv_type=tname, form=form,
+                       median_us=round(statistics.median(v), 3), min_us=round(min(v), 3), max_us=round(max(v), 3), rounds=len(v),
+                       steps=args.steps, rotated=R, sparse_over_this=round(statistics.median(us["sparse"]) / statistics.median(v), 3))
+            results.append(rec)
+            print(json.dumps(rec), flush=True)
+        del full, small, graphs, att_a, att_b
+        torch.cuda.empty_cache()
+    if args.json:
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as fh:
+            json.dump(results, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", action="append", default=[], choices=sorted(SHAPES))
@@ -52,7 +154,10 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--json", default="")
     ap.add_argument("--kv-type", action="append", default=[], choices=["q8_0", "q4_0"])
+    ap.add_argument("--sparse", type=int, default=0, metavar="TOPK")
     args = ap.parse_args()
+    if args.sparse:
+        return sparse_main(args)
     import ctypes as C
     import torch
     import fattn
